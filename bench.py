@@ -12,11 +12,16 @@ Untimed setup on rank 0: synthetic genotypes -> kinship K (this library's SYRK p
 the other ranks (torch.distributed, backend nccl = RCCL).  Ranks then work on disjoint SNP blocks
 with no collective in the timed region (weak scaling: B SNPs per rank per step).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects, among them:
   roofline     -- the dominant kernel (UtX GEMM): algorithmic flops / hipEvent-measured duration
-  cpu_baseline -- the reference's own LMM::Analyze (kind "reference": oracle/_ref/libgemma_ref.so, the reference's
+  cpu_baseline -- (--full) the reference's own LMM::Analyze (kind "reference": oracle/_ref/libgemma_ref.so, the reference's
                   sources compiled unchanged) timed on this box's host cores on a bounded SNP sample; the oracle
                   (kind "port") beside it, and alone when that library is absent.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: setup, warmup, the N timed steps,
+the line.  --full also runs every leg beside it (CPU baselines, the fp64 / dosage / strict-precision / missingness /
+complete-block / low-heritability legs, setup parity, the end-to-end run from files, config 4's piece); a leg's own option,
+given explicitly, runs it either way.  --dump-outputs DIR writes the last timed step's SUMSTAT records as DIR/<field>.npy.
 """
 import argparse
 import json
@@ -31,6 +36,10 @@ FP64_MFMA_PEAK_TFLOPS = 78.6  # MI355X fp64 matrix peak (AMD CDNA4 datasheet; v_
 INT8_MFMA_PEAK_TOPS = 5000.0  # dense int8 = 2 x the 2.5 PFLOP/s bf16 dense peak (MI355X_MICROARCH.md: "i8 ~ 2x bf16
                               # (2xK)"; micro-benchmark ceiling there 4404 TOP/s for 32x32x32)
 HBM_PEAK_GBS = 8000.0
+# the legs beside the headline and their defaults under --full (a plain run leaves each at 0 = skip unless given)
+FULL_LEGS = {"cpu_sample": 2560, "fp64_steps": -1, "dosage_steps": 2, "miss_leg": 0.05, "complete_steps": 4, "lowh2_leg": 3e-4,
+             "cpu_setup": 1, "setup_parity": 1, "digits7_steps": -1, "c4_leg": 1, "e2e_snps": 1000000}
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: at most this much in all (a seeded sample of the SNPs beyond it)
 
 
 def parse():
@@ -42,51 +51,51 @@ def parse():
     ap.add_argument("--batch", type=int, default=20000, help="SNPs per step and per rank")
     ap.add_argument("--kin-snps", type=int, default=100000, help="SNPs used for the kinship matrix (setup; SURVEY 8d: >= 100 000)")
     ap.add_argument("--eigen", default="auto", choices=["auto", "gemma", "torch"])
-    ap.add_argument("--cpu-sample", type=int, default=2560, help="SNPs in the CPU baseline sample (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=None, help="SNPs in the CPU baseline sample (0 = skip; --full: 2560)")
     ap.add_argument("--a-mode", type=int, default=1)
-    ap.add_argument("--fp64-steps", type=int, default=-1,
-                    help="steps of the fp64 MFMA GEMM path beside the timed region, on the same blocks (-1, default: min(--steps, 10); 0 = skip)")
-    ap.add_argument("--dosage-steps", type=int, default=2,
+    ap.add_argument("--fp64-steps", type=int, default=None,
+                    help="steps of the fp64 MFMA GEMM path beside the timed region, on the same blocks (-1, --full: min(--steps, 10); 0 = skip)")
+    ap.add_argument("--dosage-steps", type=int, default=None,
                     help="extra untimed-region steps on BIMBAM-style fixed-point dosages (k/100, fp64 input): the int8-digit "
-                         "dosage path, checked against the fp64 GEMM path on the same block (0 = skip)")
+                         "dosage path, checked against the fp64 GEMM path on the same block (0 = skip; --full: 2)")
     ap.add_argument("--miss", type=float, default=0.01, help="missing-call rate of the synthetic PLINK blocks (timed region)")
-    ap.add_argument("--miss-leg", type=float, default=0.05,
+    ap.add_argument("--miss-leg", type=float, default=None,
                     help="extra untimed-region steps at this missing-call rate (GEMMA's default -miss ceiling is 0.05): every row then "
-                         "has groups of four with 3-4 missing calls, which the sparse mask operand hands to the fp64 fix-up (0 = skip)")
-    ap.add_argument("--complete-steps", type=int, default=4,
+                         "has groups of four with 3-4 missing calls, which the sparse mask operand hands to the fp64 fix-up (0 = skip; --full: 0.05)")
+    ap.add_argument("--complete-steps", type=int, default=None,
                     help="extra untimed-region steps on blocks WITHOUT a missing call (hard calls of an imputed panel): the library "
                          "notices on the device and takes the genotype product alone (include/gemma_hip.h: "
-                         "gemma_hip_dbg_last_block_missing); 0 = skip")
-    ap.add_argument("--lowh2-leg", type=float, default=3e-4,
+                         "gemma_hip_dbg_last_block_missing); 0 = skip; --full: 4")
+    ap.add_argument("--lowh2-leg", type=float, default=None,
                     help="extra untimed-region steps on a second phenotype whose variance ratio lambda is this value (next to no "
                          "heritability: lambda-hat in the decades below 1e-3, the common case in human GWAS) -- the per-SNP stage must "
-                         "not fall off the table path there (0 = skip)")
+                         "not fall off the table path there (0 = skip; --full: 3e-4)")
     ap.add_argument("--ref-procs", type=int, default=8,
                     help="independent processes of the reference's LMM::Analyze in the cpu_baseline leg (each on its own slice of the "
                          "last timed block; 1 = one in-process call as in rounds 1-2)")
-    ap.add_argument("--cpu-setup", type=int, default=1,
+    ap.add_argument("--cpu-setup", type=int, default=None,
                     help="1: also time the reference's setup stages on the host cores -- EigenDecomp_Zeroed (dsyevr) at this n and "
-                         "PlinkKin on one batch -- in a child process beside the GPU legs, reported as cpu_baseline.setup (0 = skip)")
+                         "PlinkKin on one batch -- in a child process beside the GPU legs, reported as cpu_baseline.setup (0 = skip; --full: 1)")
     ap.add_argument("--cpu-setup-n", type=int, default=8192,
                     help="order of the leading principal block of the centred kinship the host eigendecomposition runs on (0 = this "
                          "run's n: 334 s at n = 20000 on the GPU box, profiles/r03_cpu_setup_baseline.json, which is why the default "
                          "run measures a block and cites the full-n measurement)")
     ap.add_argument("--cpu-setup-budget", type=float, default=600.0,
                     help="seconds after which the host eigendecomposition is abandoned and reported as unfinished")
-    ap.add_argument("--setup-parity", type=int, default=1,
+    ap.add_argument("--setup-parity", type=int, default=None,
                     help="1: verify the setup stages at the bench's own size (setup_parity in the JSON line): residual and orthogonality of "
                          "the n x n eigendecomposition through the library's GEMM, its eigenvalues against rocSOLVER's, and -- with "
                          "--cpu-setup -- the kinship of one .bed batch and the eigenvalues of the --cpu-setup-n block against the reference's "
-                         "PlinkKin / dsyevr outputs (0 = skip)")
-    ap.add_argument("--digits7-steps", type=int, default=-1,
+                         "PlinkKin / dsyevr outputs (0 = skip; --full: 1)")
+    ap.add_argument("--digits7-steps", type=int, default=None,
                     help="steps of the STRICT-precision leg beside the timed region's 6 digits at n >= 16384: GEMMA_HIP_I8_FORM=7g6m -- seven "
                          "base-256 digits of U for the genotype product (2^-56 of each column's maximum), the mask product on the upper six: "
-                         "U^T x at or below the fp64 GEMM's own rounding error (tests/test_gpu_at_size.py).  -1 (default): as many steps "
+                         "U^T x at or below the fp64 GEMM's own rounding error (tests/test_gpu_at_size.py).  -1 (--full): as many steps "
                          "as the timed region, the same blocks; reported as value_strict at equal standing (0 = skip)")
-    ap.add_argument("--c4-leg", type=int, default=1,
+    ap.add_argument("--c4-leg", type=int, default=None,
                     help="1: after everything else, BASELINE config 4's per-GPU piece at its real size in a child process (n = 50000, one "
                          "20000-SNP block per step, 2 steps, kinship from 40000 SNPs, its own eigendecomposition, 64 SNPs against the "
-                         "oracle / the reference) -- ~80 s, reported under \"c4_leg\", never part of `value` (0 = skip)")
+                         "oracle / the reference) -- ~80 s, reported under \"c4_leg\", never part of `value` (0 = skip; --full: 1)")
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)
     ap.add_argument("--child-spec", default="", help=argparse.SUPPRESS)
     ap.add_argument("--pipeline", type=int, default=0,
@@ -103,11 +112,22 @@ def parse():
                     help="measurement aid: keep the setup's result (U, eval, UtW, Uty, null scalars) in this file -- written "
                          "when absent, loaded when present -- so that a profiler run (rocprofv3 --pmc crashes inside the "
                          "eigensolver's ~80 000 launches) can start at the timed region")
-    ap.add_argument("--e2e-snps", type=int, default=1000000,
-                    help="end-to-end leg after the timed region (0 = skip; default 1000000 = BASELINE config 3 in full since round 5): a synthetic PLINK set of this many SNPs on disk -> "
+    ap.add_argument("--e2e-snps", type=int, default=None,
+                    help="end-to-end leg after the timed region (0 = skip; --full: 1000000 = BASELINE config 3 in full): a synthetic PLINK set of this many SNPs on disk -> "
                          "tests/cpp/gemma_file_driver -inproc (first pass, kinship, eigen, -lmm, .assoc.txt), wall seconds "
                          "per stage reported under \"e2e\" (0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline, each at its default above (CPU baselines, fp64 / dosage / strict / "
+                         "missingness / complete-block / low-heritability legs, setup parity, end to end from files, config 4's piece); "
+                         "without it those legs are off unless their own option is given")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the SUMSTAT records of the last timed step (what LMM.batch hands its caller) "
+                         "as DIR/<field>.npy, float64, one file per field")
+    args = ap.parse_args()
+    for k, v in FULL_LEGS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v if args.full else 0)
+    return args
 
 
 def ctypes_digits(L, n):
@@ -190,6 +210,20 @@ def run_child(args):
         json.dump(res, open(spec["out"], "w"))
     else:
         raise SystemExit("unknown --child " + args.child)
+
+
+def dump_outputs(d, np, res, names, seed):
+    """--dump-outputs: the records of the last timed step, one float64 file per SUMSTAT field (DIR/beta.npy, ...).  Above
+    DUMP_MAX_BYTES in all, a sorted sample of the SNPs drawn from --seed, with its SNP indices as DIR/snp_index.npy."""
+    os.makedirs(d, exist_ok=True)
+    rows = res.shape[0]
+    keep = DUMP_MAX_BYTES // (8 * (len(names) + 1))
+    if rows > keep:
+        idx = np.sort(np.random.default_rng(seed).choice(rows, size=keep, replace=False))
+        res = res[idx]
+        np.save(os.path.join(d, "snp_index.npy"), idx.astype(np.float64))
+    for j, k in enumerate(names):
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(res[:, j], dtype=np.float64))
 
 
 def shm_dir():
@@ -790,13 +824,15 @@ def main():
     assoc_ms, assoc_n = api.profile_read(L.STAGE_ASSOC)
     ing_ms, ing_n = api.profile_read(L.STAGE_INGEST)
     res = out.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, np, res, api.SUMSTAT_DTYPE.names, args.seed)
     n_nan = int(np.isnan(res[:, 4]).sum())
     i8_path = os.environ.get("GEMMA_HIP_UTX_I8", "1") != "0"
     timed_kernel = api.last_utx_kernel()  # the matrix kernel the timed steps launched, as the library's launch site recorded it
     # the same blocks one at a time on one stream (gemma_hip_lmm_batch_d: what rounds 1-4 timed), outside the timed region: the
     # records kernel on ALL CUs, and a bit-for-bit comparison of the last block's records with the pipelined run's
     one_stream = None
-    if piped and world == 1:
+    if piped and world == 1 and args.full:
         out1 = torch.empty_like(out)
         lmm.batch(blocks[args.warmup], L.GENO_PLINK_2BIT, out=out1)
         torch.cuda.synchronize()
@@ -1420,7 +1456,7 @@ def c4_leg(args, t_bench0):
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--individuals", "50000", "--batch", "20000", "--steps", "2",
            "--warmup", "1", "--kin-snps", "40000", "--cpu-sample", "64", "--ref-procs", "1", "--cpu-setup", "0", "--setup-parity", "1",
            "--fp64-steps", "0", "--dosage-steps", "0", "--miss-leg", "0", "--lowh2-leg", "0", "--digits7-steps", "0", "--e2e-snps", "0",
-           "--c4-leg", "0", "--seed", str(args.seed + 4)]
+           "--c4-leg", "0", "--seed", str(args.seed + 4), "--full"]
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)

@@ -4,7 +4,7 @@
 # Everything goes to gpurun_out/<tag>/.  Steps:
 #   suite      python -m pytest tests -m gpu -x -q           -> pytest_gpu.txt
 #   smoke      __graft_entry__.smoke()                       -> smoke.txt
-#   bench      the driver's command (--gpus 1 --steps 20 --warmup 5, every side leg)   -> bench_driver_cmd.jsonl
+#   bench      the driver's command plus every side leg (--gpus 1 --steps 20 --warmup 5 --full)   -> bench_driver_cmd.jsonl
 #   plain      the same timed region without the side legs   -> bench_plain.jsonl
 #   prof       rocprofv3 --kernel-trace --stats of `plain`   -> bench_kernel_stats.csv (+ the line the profiled run printed)
 #   pmc        scripts/pmc_bench.sh (one counter pass per group on the timed kernels) + scripts/pmc_summarize.py -> pmc/summary.csv, pmc_traffic.json
@@ -39,7 +39,7 @@ for STEP in "$@"; do
   case $STEP in
     suite) timeout 2400 python -m pytest tests -m gpu -x -q --durations=12 > $OUT/pytest_gpu.txt 2>&1; echo "pytest rc=$?" >> $OUT/pytest_gpu.txt; tail -25 $OUT/pytest_gpu.txt ;;
     smoke) timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.txt 2>&1; tail -2 $OUT/smoke.txt ;;
-    bench) timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_cmd.jsonl 2> $OUT/bench_driver_cmd.err; echo "bench rc=$?"; summ $OUT/bench_driver_cmd.jsonl ;;
+    bench) timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_driver_cmd.jsonl 2> $OUT/bench_driver_cmd.err; echo "bench rc=$?"; summ $OUT/bench_driver_cmd.jsonl ;;
     plain) timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 $LEGS > $OUT/bench_plain.jsonl 2> $OUT/bench_plain.err; echo "bench rc=$?"; summ $OUT/bench_plain.jsonl ;;
     prof)
       timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o b -- python bench.py --gpus 1 --steps 20 --warmup 5 $LEGS > $OUT/bench_profiled.jsonl 2> $OUT/bench_profiled.err

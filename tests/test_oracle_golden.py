@@ -1,10 +1,11 @@
 """The oracle against the reference's own known answers (CPU only)."""
+import gzip
 import os
 
 import numpy as np
 import pytest
 
-REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def test_getabindex_kat(oracle):
@@ -74,13 +75,16 @@ def test_oracle_regenerates_fixture(oracle, bxd):
     assert l_mle == pytest.approx(null[0], rel=1e-12) and logl == pytest.approx(null[1], rel=1e-12)
 
 
-@pytest.mark.skipif(not os.path.exists(REF + "/example/BXD_geno.txt.gz"), reason="reference tree not mounted")
-def test_bxd_end_to_end_from_reference_files(oracle):
-    """Full restated pipeline from the reference's example files (build container only)."""
-    ex = REF + "/example/"
-    rs, G = oracle.read_bimbam_geno(ex + "BXD_geno.txt.gz")
-    y, indp = oracle.read_pheno(ex + "BXD_pheno.txt")
-    cvt, indc = oracle.read_cvt(ex + "BXD_covariates2.txt")
+def test_bxd_end_to_end_from_reference_files(oracle, tmp_path):
+    """Full restated pipeline from the reference's example files: example/BXD_geno.txt.gz, BXD_pheno.txt and
+    BXD_covariates2.txt, committed byte for byte (gzipped) as tests/golden/text/bxd_{mean_genotypes,trait,cvt}.txt.gz."""
+    txt = os.path.join(GOLDEN, "text")
+    for src, dst in (("bxd_trait.txt.gz", "BXD_pheno.txt"), ("bxd_cvt.txt.gz", "BXD_covariates2.txt")):
+        with gzip.open(os.path.join(txt, src), "rb") as f:
+            (tmp_path / dst).write_bytes(f.read())
+    rs, G = oracle.read_bimbam_geno(os.path.join(txt, "bxd_mean_genotypes.txt.gz"))
+    y, indp = oracle.read_pheno(str(tmp_path / "BXD_pheno.txt"))
+    cvt, indc = oracle.read_cvt(str(tmp_path / "BXD_covariates2.txt"))
     ind, W = oracle.process_cvt_phen(indp, cvt, indc)
     assert ind.sum() == 67 and W.shape == (67, 3)
     isnp_k, _, _ = oracle.qc_snps(G, ind, W)
@@ -93,10 +97,20 @@ def test_bxd_end_to_end_from_reference_files(oracle):
     assert "%.6e" % np.nanmax(st["p_lrt"]) == "9.997119e-01"
 
 
-@pytest.mark.skipif(not os.path.exists(REF + "/test/data/issue188/2000.bed"), reason="reference tree not mounted")
-def test_plink_decode_and_missing(oracle):
-    """issue188 PLINK set with missing genotypes (test/dev_test_suite.sh:104-119): decode rules."""
-    raw, ni_total, ph, ind = oracle.read_bed(REF + "/test/data/issue188/2000")
+def test_plink_decode_and_missing(oracle, tmp_path):
+    """issue188 PLINK set with missing genotypes (test/dev_test_suite.sh:104-119): decode rules.  The set is rebuilt from
+    tests/golden/ref_issue188.npz: its test/data/issue188/2000.bed byte for byte and the phenotype column of its .fam."""
+    fx = np.load(os.path.join(GOLDEN, "ref_issue188.npz"))
+    pre = str(tmp_path / "2000")
+    open(pre + ".bed", "wb").write(fx["bed"].tobytes())
+    ns = (fx["bed"].size - 3) // ((int(fx["n_total"]) + 3) // 4)
+    with open(pre + ".bim", "w") as f:
+        for t in range(ns):
+            f.write("1\trs%d\t0\t%d\tA\tG\n" % (t, t + 1))
+    with open(pre + ".fam", "w") as f:
+        for i, v in enumerate(fx["pheno_col6"]):
+            f.write("f%d i%d 0 0 1 %s\n" % (i, i, v))
+    raw, ni_total, ph, ind = oracle.read_bed(pre)
     assert ni_total == 1008 and raw.shape == (2000, 252)
     G = oracle.bed_decode(raw[:50], ni_total)
     vals = set(np.unique(G[~np.isnan(G)]).tolist())

@@ -208,10 +208,81 @@ def test_mvlmm_ml_em_three_traits(oracle, mvcases, mode):
     assert np.all(np.isfinite(got["p_lrt"])) and np.all(np.isfinite(got["beta"]))
 
 
-# ----------------------------------------------------------------------------- function by function (needs oracle/_ref)
+# ----------------------------------------------------------------------------- function by function
+# The reference's functions are called live from oracle/_ref/libgemma_ref.so where `make -C oracle ref` built it (the
+# reference's own sources); elsewhere the tests replay what the same calls returned there, kept in
+# tests/golden/ref_calls/<test>.npz (GEMMA_REF_RECORD=1 rewrites them from the live library).  A replayed call first checks that
+# it is handed the inputs the recorded call had (sum and sum of magnitudes of every array, every scalar, to 1e-9).
+CALLS = os.path.join(R.GOLD, "ref_calls")
+
+
+class _Calls:
+    def __init__(self, name, so, orc):
+        self.path = os.path.join(CALLS, name.replace("[", "_").replace("]", "") + ".npz")
+        self.so, self.orc, self.i, self.rec = so, orc, 0, {}
+        self.live = so is not None
+        self.record = self.live and os.environ.get("GEMMA_REF_RECORD") == "1"
+        if not self.live:
+            d = np.load(self.path)
+            self.rec = {k: d[k] for k in d.files}
+
+    def ref(self, name, *args):
+        """so.<name>(*args) (ctypes; numpy arrays go in as double *)"""
+        fn = (lambda *a: getattr(self.so, name)(*[_dp(x) if isinstance(x, np.ndarray) else x for x in a])) if self.live else None
+        return self._call(fn, args, {})
+
+    def oracle(self, name, *args, **kw):
+        """oracle.<name>(*args, **kw): the in-process bridges to the reference (ref_lmm_analyze, ref_plink_kin, ...)"""
+        return self._call(getattr(self.orc, name) if self.live else None, args, kw)
+
+    def _call(self, fn, args, kw):
+        k = "c%d_" % self.i
+        self.i += 1
+        arrs = [(j, a) for j, a in enumerate(args) if isinstance(a, np.ndarray)]
+        fp = [v for _, a in arrs for v in (float(np.nansum(a)), float(np.nansum(np.abs(a))))]
+        fp += [float(a) for a in list(args) + list(kw.values()) if isinstance(a, (int, float, np.floating, np.integer))]
+        fp = np.array(fp, dtype=np.float64)
+        if not self.live:
+            want = self.rec[k + "fp"]
+            assert want.shape == fp.shape and np.all(np.abs(fp - want) <= 1e-9 * np.abs(want) + 1e-300), (self.path, k, fp, want)
+            for j, a in arrs:
+                if k + "a%d" % j in self.rec:
+                    np.copyto(a, self.rec[k + "a%d" % j])
+            if k + "r" in self.rec:
+                return self.rec[k + "r"][()] if self.rec[k + "r"].ndim == 0 else self.rec[k + "r"]
+            return tuple(self.rec[k + "r%d" % t][()] if self.rec[k + "r%d" % t].ndim == 0 else self.rec[k + "r%d" % t]
+                         for t in range(int(self.rec[k + "nr"])))
+        before = [a.copy() for _, a in arrs]
+        ret = fn(*args, **kw)
+        if self.record:
+            self.rec[k + "fp"] = fp
+            for (j, a), b in zip(arrs, before):
+                if not np.array_equal(a, b, equal_nan=True):
+                    self.rec[k + "a%d" % j] = a.copy()
+            if isinstance(ret, tuple):
+                self.rec[k + "nr"] = np.array(len(ret))
+                for t, r in enumerate(ret):
+                    self.rec[k + "r%d" % t] = np.asarray(r)
+            else:
+                self.rec[k + "r"] = np.asarray(ret)
+        return ret
+
+    def save(self):
+        if self.record:
+            os.makedirs(CALLS, exist_ok=True)
+            np.savez_compressed(self.path, **self.rec)
+
+
+@pytest.fixture
+def refcalls(request, oracle):
+    rc = _Calls(request.node.name, _refso(), oracle)
+    yield rc
+    rc.save()
+
+
 def _refso():
     if not os.path.exists(REF_SO):
-        pytest.skip("oracle/_ref/libgemma_ref.so not built (make -C oracle ref needs /root/reference)")
+        return None
     so = C.CDLL(REF_SO)
     P = C.POINTER(C.c_double)
     so.ref_MphEM.restype = C.c_double
@@ -242,11 +313,10 @@ def _snp_design(c, s):
 
 
 @pytest.mark.parametrize("func,iters", [("R", 1000), ("L", 1), ("L", 2)])
-def test_reference_mph_em_function(oracle, mvcases, func, iters):
+def test_reference_mph_em_function(oracle, mvcases, refcalls, func, iters):
     """MphEM of the reference (src/mvlmm.cpp:599-724) called directly: REML to convergence and one full ML iteration (every
     update formula of the 'L' branch) agree to 1e-9 on every SNP tried; the second ML iteration is the first that mixes two
     eigenbases, so it agrees wherever dsyevr kept its signs between the two (most SNPs) and is off by percents elsewhere."""
-    so = _refso()
     c = mvcases["b"]
     n, d = c["ev"].size, c["d"]
     snps = (0, 3, 7, 18, 27, 100, 500, 900, 1500)
@@ -256,8 +326,7 @@ def test_reference_mph_em_function(oracle, mvcases, func, iters):
         a = [c["null"]["Vg_mle"].copy(), c["null"]["Ve_mle"].copy(), B0.copy()]
         b = [x.copy() for x in a]
         lo = oracle.mph_em(func, iters, 1e-3, c["ev"], Xs, c["UtY"], a[0], a[1], a[2])
-        lr = so.ref_MphEM(func.encode(), iters, 1e-3, n, d, Xs.shape[0], _dp(c["ev"]), _dp(Xs), _dp(c["UtY"]), _dp(b[0]), _dp(b[1]),
-                          _dp(b[2]))
+        lr = refcalls.ref("ref_MphEM", func.encode(), iters, 1e-3, n, d, Xs.shape[0], c["ev"], Xs, c["UtY"], b[0], b[1], b[2])
         assert lo == pytest.approx(lr, rel=1e-11), (func, s)  # the likelihood is evaluated before the update
         ok = all(np.abs(x - y).max() <= 1e-9 * max(1.0, np.abs(y).max()) for x, y in zip(a, b))
         same += ok
@@ -267,8 +336,7 @@ def test_reference_mph_em_function(oracle, mvcases, func, iters):
 
 
 @pytest.mark.parametrize("func", ["R", "L"])
-def test_reference_mph_nr_and_calcp_functions(oracle, mvcases, func):
-    so = _refso()
+def test_reference_mph_nr_and_calcp_functions(oracle, mvcases, refcalls, func):
     c = mvcases["b"]
     n, d = c["ev"].size, c["d"]
     for s in (7, 3, 250):
@@ -277,27 +345,26 @@ def test_reference_mph_nr_and_calcp_functions(oracle, mvcases, func):
         b = [x.copy() for x in a]
         lo, Hi = oracle.mph_nr(func, 10, 1e-3, c["ev"], Xs, c["UtY"], a[0], a[1])
         Hr = np.zeros((d * (d + 1), d * (d + 1)))
-        lr = so.ref_MphNR(func.encode(), 10, 1e-3, n, d, Xs.shape[0], _dp(c["ev"]), _dp(Xs), _dp(c["UtY"]), _dp(b[0]), _dp(b[1]), _dp(Hr))
+        lr = refcalls.ref("ref_MphNR", func.encode(), 10, 1e-3, n, d, Xs.shape[0], c["ev"], Xs, c["UtY"], b[0], b[1], Hr)
         assert lo == pytest.approx(lr, rel=1e-10), (func, s)
         assert np.abs(a[0] - b[0]).max() < 1e-8 and np.abs(a[1] - b[1]).max() < 1e-8
         assert np.abs(Hi - Hr).max() <= 1e-6 * np.abs(Hr).max()
         beta_o, beta_r, Vb_r = np.zeros(d), np.zeros(d), np.zeros((d, d))
         x = np.ascontiguousarray(c["UtX"][s])
         p_o, beta_o, Vb_o = oracle.mph_calcp(c["ev"], x, c["UtW"], c["UtY"], a[0], a[1])
-        p_r = so.ref_MphCalcP(n, d, c["UtW"].shape[0], _dp(c["ev"]), _dp(x), _dp(c["UtW"]), _dp(c["UtY"]), _dp(b[0]), _dp(b[1]),
-                              _dp(beta_r), _dp(Vb_r))
+        p_r = refcalls.ref("ref_MphCalcP", n, d, c["UtW"].shape[0], c["ev"], x, c["UtW"], c["UtY"], b[0], b[1], beta_r, Vb_r)
         assert p_o == pytest.approx(p_r, rel=1e-8)
         assert np.abs(beta_o - beta_r).max() < 1e-9 and np.abs(Vb_o - Vb_r).max() < 1e-9
 
 
 @pytest.mark.parametrize("func", ["R", "L"])
-def test_reference_crt_factors_and_pcrt(oracle, mvcases, func):
+def test_reference_crt_factors_and_pcrt(oracle, mvcases, refcalls, func):
     """-crt (src/mvlmm.cpp:2054-2331 CalcCRT, :2952-2970 PCRT): the Edgeworth correction factors crt_a, crt_b, crt_c that the
     reference's MphNR hands back from its last CalcDev call against the restatement's dense CalcCRT (same point, same Hessian
     inverse), for the REML and the ML likelihood, on both mvLMM fixtures; then PCRT in its three modes (its chi-square
     quantile is an iteration converged to 1e-10)."""
     so = _refso()
-    if not hasattr(so, "ref_MphNR_crt"):
+    if so is not None and not hasattr(so, "ref_MphNR_crt"):
         pytest.skip("oracle/_ref/libgemma_ref.so predates the crt bridge (make -C oracle ref)")
     for key in ("a", "b"):
         c = mvcases[key]
@@ -311,23 +378,22 @@ def test_reference_crt_factors_and_pcrt(oracle, mvcases, func):
             for iters in (1, 10):
                 lo, Hi, crt_o = oracle.mph_nr_crt(func, iters, 1e-3, c["ev"], Xs, c["UtY"], a[0], a[1])
                 Hr, crt_r = np.zeros((d * (d + 1), d * (d + 1))), np.zeros(3)
-                lr = so.ref_MphNR_crt(func.encode(), iters, 1e-3, n, d, Xs.shape[0], _dp(c["ev"]), _dp(Xs), _dp(c["UtY"]), _dp(b[0]),
-                                      _dp(b[1]), _dp(Hr), _dp(crt_r))
+                lr = refcalls.ref("ref_MphNR_crt", func.encode(), iters, 1e-3, n, d, Xs.shape[0], c["ev"], Xs, c["UtY"], b[0], b[1], Hr,
+                                  crt_r)
                 assert lo == pytest.approx(lr, rel=1e-10)
                 assert np.all(np.isfinite(crt_r)) and np.abs(crt_r).max() > 0
                 assert np.abs(crt_o - crt_r).max() <= 1e-6 * np.abs(crt_r).max(), (key, s, iters, crt_o, crt_r)
                 for mode in (1, 2, 3):
                     for pv in (3e-4, 1e-7, 2e-12):
-                        pr = so.ref_PCRT(mode, d, pv, crt_r[0], crt_r[1], crt_r[2])
+                        pr = refcalls.ref("ref_PCRT", mode, d, pv, crt_r[0], crt_r[1], crt_r[2])
                         po = oracle.pcrt(mode, d, pv, crt_r)
                         assert po == pytest.approx(pr, rel=1e-8), (mode, pv)
 
 
-def test_reference_eigenproc_basis_is_unstable(mvcases):
+def test_reference_eigenproc_basis_is_unstable(mvcases, refcalls):
     """The reference's EigenProc (src/mvlmm.cpp:213-282 -> dsyevr) on the V_g, V_e of consecutive EM iterations: an
     eigenvector changes sign between two nearly equal inputs, and under a 1e-15 relative perturbation of one input.  This
     is why the reference's ML EM (which mixes the bases of two iterations) cannot be matched SNP for SNP when d >= 3."""
-    so = _refso()
     c = mvcases["b"]
     n, d = c["ev"].size, c["d"]
     flips = 0
@@ -336,11 +402,11 @@ def test_reference_eigenproc_basis_is_unstable(mvcases):
         prev = None
         for it in range(1, 12):
             Vg, Ve, B = c["null"]["Vg_mle"].copy(), c["null"]["Ve_mle"].copy(), B0.copy()
-            so.ref_MphEM(b"L", it, 1e-3, n, d, Xs.shape[0], _dp(c["ev"]), _dp(Xs), _dp(c["UtY"]), _dp(Vg), _dp(Ve), _dp(B))
+            refcalls.ref("ref_MphEM", b"L", it, 1e-3, n, d, Xs.shape[0], c["ev"], Xs, c["UtY"], Vg, Ve, B)
             for scale in (1.0, 1.0 + 1e-15):
                 Dl, A, Ai = np.zeros(d), np.zeros((d, d)), np.zeros((d, d))
                 Vgp = Vg * scale
-                so.ref_EigenProc(d, _dp(Vgp), _dp(Ve), _dp(Dl), _dp(A), _dp(Ai))
+                refcalls.ref("ref_EigenProc", d, Vgp, Ve, Dl, A, Ai)
                 if prev is not None:
                     # rows of UltVehi are eigen-directions: same direction up to sign, |cos| ~ 1; count sign changes
                     for r in range(d):
@@ -352,15 +418,13 @@ def test_reference_eigenproc_basis_is_unstable(mvcases):
 
 
 @pytest.mark.parametrize("mode", [1, 4])
-def test_reference_lmm_analyze_in_process(oracle, bxd, ref_bxd, mode):
+def test_reference_lmm_analyze_in_process(oracle, bxd, ref_bxd, refcalls, mode):
     """LMM::Analyze of the reference called in-process (oracle/ref_bridge.cpp: ref_lmm_analyze, what bench.py times as
     cpu_baseline kind "reference"): at full precision the restatement follows it to 1e-7 on beta / se / p and 1e-12 on
     logl; its printed output is the fixture."""
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref/libgemma_ref.so not built")
     X = np.ascontiguousarray(bxd["X"], dtype=np.float64)
-    got = oracle.ref_lmm_analyze(mode, bxd["U"], bxd["eval"], bxd["UtW"], bxd["Uty"], X, l_mle_null=bxd["null"][0],
-                                 logl_mle_H0=bxd["null"][1])
+    got = refcalls.oracle("ref_lmm_analyze", mode, bxd["U"], bxd["eval"], bxd["UtW"], bxd["Uty"], X, l_mle_null=float(bxd["null"][0]),
+                          logl_mle_H0=float(bxd["null"][1]))
     mine = bxd["stat_mode%d" % mode]
     for k in ("beta", "se", "p_wald", "logl_H1") + (("p_lrt", "p_score") if mode == 4 else ()):
         e = R.rel_err(mine[k], got[k])
@@ -415,10 +479,9 @@ def test_mvlmm_five_traits_null_and_per_snp(oracle, mv5):
         assert np.median(err) < 1e-2 and err.max() < 6e-2, (mode, float(np.median(err)), float(err.max()))
 
 
-def test_reference_functions_five_traits(oracle, mv5):
+def test_reference_functions_five_traits(oracle, mv5, refcalls):
     """MphEM('R') to convergence, MphNR('R') and MphCalcP of the reference at d = 5 with two covariates + the SNP, from
     identical starting values: 1e-8."""
-    so = _refso()
     c = mv5
     n, d = c["ev"].size, 5
     for s in (0, 17, 101, 249):
@@ -427,20 +490,19 @@ def test_reference_functions_five_traits(oracle, mv5):
         a = [c["null"]["Vg_mle"].copy(), c["null"]["Ve_mle"].copy(), B0.copy()]
         b = [x.copy() for x in a]
         lo = oracle.mph_em("R", 1000, 1e-3, c["ev"], Xs, c["UtY"], a[0], a[1], a[2])
-        lr = so.ref_MphEM(b"R", 1000, 1e-3, n, d, Xs.shape[0], _dp(c["ev"]), _dp(Xs), _dp(c["UtY"]), _dp(b[0]), _dp(b[1]), _dp(b[2]))
+        lr = refcalls.ref("ref_MphEM", b"R", 1000, 1e-3, n, d, Xs.shape[0], c["ev"], Xs, c["UtY"], b[0], b[1], b[2])
         assert lo == pytest.approx(lr, rel=1e-11)
         for x, y in zip(a, b):
             assert np.abs(x - y).max() <= 1e-8 * max(1.0, np.abs(y).max())
         l2, Hi = oracle.mph_nr("R", 10, 1e-3, c["ev"], Xs, c["UtY"], a[0], a[1])
         Hr = np.zeros((d * (d + 1), d * (d + 1)))
-        r2 = so.ref_MphNR(b"R", 10, 1e-3, n, d, Xs.shape[0], _dp(c["ev"]), _dp(Xs), _dp(c["UtY"]), _dp(b[0]), _dp(b[1]), _dp(Hr))
+        r2 = refcalls.ref("ref_MphNR", b"R", 10, 1e-3, n, d, Xs.shape[0], c["ev"], Xs, c["UtY"], b[0], b[1], Hr)
         assert l2 == pytest.approx(r2, rel=1e-10)
         assert np.abs(a[0] - b[0]).max() < 1e-7 and np.abs(a[1] - b[1]).max() < 1e-7
         x = np.ascontiguousarray(c["UtX"][s])
         beta_r, Vb_r = np.zeros(d), np.zeros((d, d))
         p_o, beta_o, Vb_o = oracle.mph_calcp(c["ev"], x, c["UtW"], c["UtY"], a[0], a[1])
-        p_r = so.ref_MphCalcP(n, d, c["UtW"].shape[0], _dp(c["ev"]), _dp(x), _dp(c["UtW"]), _dp(c["UtY"]), _dp(b[0]), _dp(b[1]),
-                              _dp(beta_r), _dp(Vb_r))
+        p_r = refcalls.ref("ref_MphCalcP", n, d, c["UtW"].shape[0], c["ev"], x, c["UtW"], c["UtY"], b[0], b[1], beta_r, Vb_r)
         assert p_o == pytest.approx(p_r, rel=1e-7)
         assert np.abs(beta_o - beta_r).max() < 1e-8 and np.abs(Vb_o - Vb_r).max() < 1e-8
 
@@ -476,11 +538,9 @@ def test_issue188_analyze_gene(oracle, i188, mode):
     R.assert_stats(got, fx, "lmm%d" % mode)
 
 
-def test_reference_setup_stages_through_the_bridge(oracle, tmp_path):
+def test_reference_setup_stages_through_the_bridge(oracle, tmp_path, refcalls):
     """oracle/ref_bridge.cpp: ref_plink_kin = the reference's own PlinkKin on a .bed file, ref_eigen_decomp_zeroed = its own
     EigenDecomp_Zeroed -- what bench.py's cpu_baseline.setup times -- against the restatement."""
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref/libgemma_ref.so not built (no reference tree here)")
     rng = np.random.default_rng(11)
     n, p = 211, 333
     codes = rng.choice([0, 1, 2, 3], size=(p, n), p=[0.3, 0.03, 0.37, 0.3]).astype(np.uint8)
@@ -490,11 +550,11 @@ def test_reference_setup_stages_through_the_bridge(oracle, tmp_path):
     raw = (pad[:, 0::4] | (pad[:, 1::4] << 2) | (pad[:, 2::4] << 4) | (pad[:, 3::4] << 6)).astype(np.uint8)
     bed = tmp_path / "t.bed"
     bed.write_bytes(bytes([0x6C, 0x1B, 0x01]) + raw.tobytes())
-    K = oracle.ref_plink_kin(str(bed), n, p, 1)
+    K = refcalls.oracle("ref_plink_kin", str(bed), n, p, 1)
     K2 = oracle.calc_kin(oracle.bed_decode(raw, n), 1)
     assert np.max(np.abs(K - K2)) <= 1e-13 * np.max(np.abs(K2))
     G = oracle.center_matrix(K2)
-    U, ev, tr = oracle.ref_eigen_decomp_zeroed(G)
+    U, ev, tr = refcalls.oracle("ref_eigen_decomp_zeroed", G)
     U2, ev2, tr2 = oracle.eigen_decomp_zeroed(G)
     assert np.allclose(ev, ev2, rtol=0, atol=1e-12) and tr == pytest.approx(tr2, rel=1e-12)
     assert np.max(np.abs(U @ np.diag(ev) @ U.T - G)) < 1e-11
