@@ -24,10 +24,12 @@ SYMBOLS = [
     "gemma_hip_comm_unique_id", "gemma_hip_comm_init", "gemma_hip_comm_info", "gemma_hip_comm_bcast_d",
     "gemma_hip_comm_allreduce_sum_d", "gemma_hip_comm_finalize", "gemma_hip_comm_selftest", "gemma_hip_comm_stats", "gemma_hip_dbg_i8_digits", "gemma_hip_dbg_last_utx_path", "gemma_hip_lmm_batch_submit", "gemma_hip_lmm_batch_collect",
     "gemma_hip_dbg_last_utx_kernel", "gemma_hip_dbg_last_block_missing", "gemma_hip_reload_env", "gemma_hip_lmm_batch_pipe_d", "gemma_hip_lmm_pipe_flush",
+    "gemma_hip_spd_inverse", "gemma_hip_spd_inverse_d", "gemma_hip_vc_setup", "gemma_hip_vc_setup_d", "gemma_hip_vc_he",
+    "gemma_hip_vc_reml", "gemma_hip_vc_timing", "gemma_hip_vc_release",
 ]
 COMM_ID_BYTES = 128
 
-OK, EINVAL, ENODEV, ENOMEM, ERUNTIME, ESTATE, ENOCONV = range(7)
+OK, EINVAL, ENODEV, ENOMEM, ERUNTIME, ESTATE, ENOCONV, ENOTPD = range(8)
 GENO_F64_SNP_MAJOR, GENO_PLINK_2BIT, GENO_F64_IDV_MAJOR = 0, 1, 2
 STAGE_INGEST, STAGE_UTX_GEMM, STAGE_ASSOC, STAGE_KIN_GEMM, STAGE_EIGH, STAGE_UTX_POST = range(6)
 
@@ -179,6 +181,14 @@ def lib():
     L.gemma_hip_comm_allreduce_sum_d.argtypes = [dp, sz, vp]
     L.gemma_hip_comm_selftest.argtypes = [vp]
     L.gemma_hip_comm_stats.argtypes = [C.POINTER(CommStats)]
+    L.gemma_hip_spd_inverse.argtypes = [dp, sz, sz, C.POINTER(cd), C.POINTER(C.c_long)]
+    L.gemma_hip_spd_inverse_d.argtypes = [dp, sz, sz, C.POINTER(cd), C.POINTER(C.c_long), vp]
+    L.gemma_hip_vc_setup.argtypes = [sz, sz, C.POINTER(dp), sz, dp, sz, dp]
+    L.gemma_hip_vc_setup_d.argtypes = [sz, sz, C.POINTER(dp), sz, dp, sz, dp]
+    L.gemma_hip_vc_he.argtypes = [dp] * 6
+    L.gemma_hip_vc_reml.argtypes = [ci] + [dp] * 6 + [C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_long), dp, sz]
+    L.gemma_hip_vc_timing.argtypes = [dp]
+    L.gemma_hip_vc_release.argtypes = []
     for s in SYMBOLS:
         getattr(L, s)  # AttributeError if the library does not export what the header declares
     _lib = L

@@ -726,3 +726,112 @@ class MVLMM:
                 row += ["%.6e" % x for x in self.sumStat["beta"][t]] + ["%.6e" % x for x in self.sumStat["Vbeta"][t]]
                 row += ["%.6e" % self.sumStat[k][t] for k in pcols]
                 f.write("\t".join(row) + "\n")
+
+
+# ----------------------------------------------------------------------------- variance components (-vc 1 / -vc 2)
+def _torch_square_f64(t, name):
+    import torch
+    if t.dtype != torch.float64 or not t.is_cuda or t.dim() != 2 or t.shape[0] != t.shape[1]:
+        raise ValueError("%s must be a square float64 CUDA tensor" % name)
+    return t
+
+
+def spd_inverse(A, return_logdet=False):
+    """Inverse of a symmetric positive-definite matrix (a new array; torch device tensors in place), and log det A.
+    Raises GemmaHipError with code ENOTPD on the first pivot that is not > 0 (the reference's LU would carry on); the
+    error's `bad_pivot` holds that pivot's 0-based index."""
+    ld, bad = C.c_double(0.0), C.c_long(-1)
+    try:
+        if _is_torch(A):
+            import torch
+            _torch_square_f64(A, "A")
+            # the library works on the stream it is handed: torch's current one
+            L.check(L.lib().gemma_hip_spd_inverse_d(C.c_void_p(A.data_ptr()), A.shape[0], _tld(A), C.byref(ld), C.byref(bad),
+                                                    _stream()), "spd_inverse")
+            out = A
+        else:
+            out = np.array(_np64(np.asarray(A), "A"), dtype=np.float64, order="C", copy=True)
+            if out.ndim != 2 or out.shape[0] != out.shape[1]:
+                raise ValueError("A must be square")
+            L.check(L.lib().gemma_hip_spd_inverse(_ptr(out), out.shape[0], out.shape[0], C.byref(ld), C.byref(bad)),
+                    "spd_inverse")
+    except L.GemmaHipError as e:
+        e.bad_pivot = bad.value if e.code == L.ENOTPD else None
+        raise
+    return (out, ld.value) if return_logdet else out
+
+
+class VC:
+    """Mirror of class VC (src/vc.h): CalcVChe (-vc 1) and CalcVCreml (-vc 2) on one or more kinships.  Ks are the kinships
+    as src/gemma.cpp:2328-2369 hands them over (centred by CenterMatrix(G); v_traceG = their mean diagonals), numpy arrays
+    (copied to the device) or torch device tensors (used in place).  After a call the fields v_sigma2, v_se_sigma2, v_pve,
+    v_se_pve, pve_total, se_pve_total (and for REML iterations, status, evaluations, inverses, iter_sigma2, timing) hold the fit."""
+
+    def _setup(self, Ks, W, y):
+        Ks = list(Ks)
+        n = Ks[0].shape[0]
+        self._W = np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(n, -1))
+        self._y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(n))
+        self.n_vc = len(Ks)
+        arr = (C.c_void_p * self.n_vc)()
+        if _is_torch(Ks[0]):
+            import torch
+            ldk = _tld(Ks[0])
+            for i, K in enumerate(Ks):
+                _torch_square_f64(K, "kinship %d" % i)
+                if K.shape[0] != n or _tld(K) != ldk:
+                    raise ValueError("kinships must be n x n and share one leading dimension")
+                arr[i] = K.data_ptr()
+            fn = L.lib().gemma_hip_vc_setup_d
+            self._keep = Ks
+            torch.cuda.current_stream().synchronize()  # the fit runs on the null stream: the kinships must be complete
+        else:
+            self._keep = [np.ascontiguousarray(_np64(np.asarray(K), "K")) for K in Ks]
+            ldk = n
+            for i, K in enumerate(self._keep):
+                if K.shape != (n, n):
+                    raise ValueError("kinship %d is not %d x %d" % (i, n, n))
+                arr[i] = K.ctypes.data
+            fn = L.lib().gemma_hip_vc_setup
+        L.check(fn(n, self.n_vc, C.cast(arr, C.POINTER(C.c_void_p)), ldk, _ptr(self._W), self._W.shape[1], _ptr(self._y)),
+                "vc_setup")
+
+    def _outs(self):
+        m = self.n_vc
+        return np.zeros(m + 1), np.zeros(m + 1), np.zeros(m), np.zeros(m), C.c_double(0.0), C.c_double(0.0)
+
+    def _store(self, s2, se2, pve, sepve, pt, sept):
+        self.v_sigma2, self.v_se_sigma2, self.v_pve, self.v_se_pve = s2, se2, pve, sepve
+        self.pve_total, self.se_pve_total = pt.value, sept.value
+
+    def CalcVChe(self, Ks, W, y):
+        """src/vc.cpp:1503-1724"""
+        self._setup(Ks, W, y)
+        try:
+            o = self._outs()
+            L.check(L.lib().gemma_hip_vc_he(_ptr(o[0]), _ptr(o[1]), _ptr(o[2]), _ptr(o[3]), C.byref(o[4]), C.byref(o[5])), "vc_he")
+            self._store(*o)
+        finally:
+            L.lib().gemma_hip_vc_release()
+        return self
+
+    def CalcVCreml(self, Ks, W, y, noconstrain=False):
+        """src/vc.cpp:1726-1931"""
+        self._setup(Ks, W, y)
+        try:
+            o = self._outs()
+            it, st, cnt = C.c_int(0), C.c_int(0), (C.c_long * 2)()
+            trace = np.zeros((102, self.n_vc + 1))
+            L.check(L.lib().gemma_hip_vc_reml(1 if noconstrain else 0, _ptr(o[0]), _ptr(o[1]), _ptr(o[2]), _ptr(o[3]),
+                                              C.byref(o[4]), C.byref(o[5]), C.byref(it), C.byref(st), cnt, _ptr(trace),
+                                              trace.shape[0]), "vc_reml")
+            self._store(*o)
+            self.iterations, self.status = it.value, st.value
+            self.evaluations, self.inverses = cnt[0], cnt[1]
+            self.iter_sigma2 = trace[:it.value + 1].copy()
+            t5 = np.zeros(5)
+            L.check(L.lib().gemma_hip_vc_timing(_ptr(t5)), "vc_timing")
+            self.timing = dict(zip(("assembly", "spd_inverse", "p_correction", "matvec", "trace"), t5.tolist()))
+        finally:
+            L.lib().gemma_hip_vc_release()
+        return self

@@ -14,6 +14,7 @@
 #include "../../include/gemma_hip.h"
 #include "dgemm_mfma.hip.h"
 #include "eigh_tu.h"
+#include "vc_tu.h"
 #include "ingest.hip.h"
 #include "lm_assoc.hip.h"
 #include "lmm_assoc.hip.h"
@@ -353,6 +354,7 @@ extern "C" const char *gemma_hip_strerror(int code) {
   case GEMMA_HIP_ERUNTIME: return "HIP runtime error";
   case GEMMA_HIP_ESTATE: return "call sequence violated";
   case GEMMA_HIP_ENOCONV: return "eigensolver did not converge";
+  case GEMMA_HIP_ENOTPD: return "matrix not positive definite";
   default: return "unknown error";
   }
 }
@@ -430,6 +432,7 @@ extern "C" void gemma_hip_shutdown(void) {
   g_ctx.comm.finalize();
   gemm_aux_destroy();
   eigh_tu_shutdown();
+  vc_tu_shutdown();
   g_ctx.inited = false;
 }
 
@@ -530,3 +533,4 @@ extern "C" int gemma_hip_dgemm(char ta, char tb, size_t M, size_t N, size_t K, d
 #include "abi_mvlmm.inc.h"
 #include "abi_gxe_lm.inc.h"
 #include "abi_kept_comm.inc.h"
+#include "abi_vc.inc.h"

@@ -43,7 +43,8 @@ enum {
   GEMMA_HIP_ENOMEM = 3,   /* device allocation failed */
   GEMMA_HIP_ERUNTIME = 4, /* HIP runtime / kernel failure */
   GEMMA_HIP_ESTATE = 5,   /* call sequence violated (e.g. lmm_batch before lmm_setup) */
-  GEMMA_HIP_ENOCONV = 6   /* eigensolver did not converge (INFO != 0, src/lapack.cpp:213,224) */
+  GEMMA_HIP_ENOCONV = 6,  /* eigensolver did not converge (INFO != 0, src/lapack.cpp:213,224) */
+  GEMMA_HIP_ENOTPD = 7    /* matrix not positive definite (gemma_hip_spd_inverse, the REML fit of gemma_hip_vc_reml) */
 };
 
 /* == class SUMSTAT, src/param.h:54-66 (8 doubles per analysed SNP, in SNP order) */
@@ -418,6 +419,42 @@ int gemma_hip_reload_env(void);
 /* base-256 digits of U the int8 product uses at this n: 7 (U to 2^-56 of the column maximum); 6 from n = 16384 up
  * (U rounded to 2^-48 of the column maximum -- see gemma_hip_lmm_batch); GEMMA_HIP_I8_DIGITS=6|7 and GEMMA_HIP_I8_FORM=7g6m override */
 int gemma_hip_dbg_i8_digits(size_t n, int *digits);
+
+/* ---- variance components: -vc 1 (Haseman-Elston) and -vc 2 (REML, AI) ------------------------------------------------ */
+/* Inverse of a symmetric positive-definite matrix in place, with its log determinant: the fast_inverse (LU, src/fastblas.cpp)
+ * of UpdateParam, src/vc.cpp:168-258.  Blocked Cholesky (diagonal blocks in LDS, panels and trailing updates on the fp64 MFMA
+ * GEMM), then U^-1 and U^-1 U^-T on the same GEMM.  The upper triangle of A is read; the full symmetric inverse is written.
+ * Any n >= 1, lda >= n.  On the first pivot that is not > 0 the call returns GEMMA_HIP_ENOTPD, *bad_pivot = its 0-based index
+ * (may be NULL) and computes nothing further; A is then partly overwritten.  Unlike the reference's LU, an indefinite matrix is an
+ * error.  Device form: synchronises `stream` (it reads the pivot flag after every 128-row block). */
+int gemma_hip_spd_inverse(double *A, size_t n, size_t lda, double *logdet, long *bad_pivot);
+int gemma_hip_spd_inverse_d(double *A_d, size_t n, size_t lda, double *logdet, long *bad_pivot, void *stream);
+
+/* The fit of class VC (src/vc.h) on n_vc <= 8 kinships, called where src/gemma.cpp:2378-2388 calls VC::CalcVChe /
+ * VC::CalcVCreml.  K[l] (n x n, leading dimension ldk) are the kinships as the call site hands them over: read by ReadFile_kin /
+ * ReadFile_mk and centred by CenterMatrix(G); v_traceG[l] is taken as the mean diagonal of K[l] (src/gemma.cpp:2341-2369).
+ * W (n x n_cvt, n_cvt <= 64, with the intercept) and y (n) are host arrays.  vc_setup copies host kinships to the device;
+ * vc_setup_d keeps the caller's device pointers (which must stay valid until vc_release); the fit runs on the null stream and
+ * synchronises it, so work on other streams that writes the kinships must be complete first.  One fit state per process. */
+int gemma_hip_vc_setup(size_t n, size_t n_vc, const double *const *K, size_t ldk, const double *W, size_t n_cvt, const double *y);
+int gemma_hip_vc_setup_d(size_t n, size_t n_vc, const double *const *K_d, size_t ldk, const double *W, size_t n_cvt,
+                         const double *y);
+/* Results (caller-sized): sigma2[n_vc + 1], se_sigma2[n_vc + 1] (last = the residual component), pve[n_vc], se_pve[n_vc],
+ * *pve_total, *se_pve_total.  -vc 1: VC::CalcVChe, src/vc.cpp:1503-1724. */
+int gemma_hip_vc_he(double *sigma2, double *se_sigma2, double *pve, double *se_pve, double *pve_total, double *se_pve_total);
+/* -vc 2: VC::CalcVCreml, src/vc.cpp:1726-1931.  Starts from the HE fit (log 0.1 for components <= 0), solves dev1 = 0 by Powell's
+ * hybrid method with the AI matrix as Jacobian (GSL hybridsj restated, include/gemma_vc_hybrid.hpp) on log sigma2 (sigma2 with
+ * noconstrain), until sum |dev1| < 1e-3 or 100 iterations; the Hessian inverse by LU on the host.  *iterations: solver
+ * iterations; *status: 0 converged, 1 iteration limit, 2 / 3 no progress (GSL_ENOPROG / GSL_ENOPROGJ, where the reference's loop
+ * breaks too).  counts[2] (may be NULL): device evaluations of (dev1, dev2) and SPD inverses of the fit (f, J and fdf at one
+ * point share one evaluation).  iter_sigma2 (may be NULL): sigma2 of iteration 0 .. *iterations, (n_vc + 1) each, at most
+ * iter_cap rows -- the reference's per-iteration "sigma2 = " lines.  With noconstrain, a step to where H is not positive
+ * definite ends the fit with GEMMA_HIP_ENOTPD (the reference's LU inverse would carry on with an indefinite H). */
+int gemma_hip_vc_reml(int noconstrain, double *sigma2, double *se_sigma2, double *pve, double *se_pve, double *pve_total,
+                      double *se_pve_total, int *iterations, int *status, long *counts, double *iter_sigma2, size_t iter_cap);
+/* seconds of the last REML fit's evaluations: {H assembly, SPD inverse, P correction, mat-vecs, traces} (HIP events) */
+int gemma_hip_vc_timing(double *t5);
+int gemma_hip_vc_release(void);
 
 #ifdef __cplusplus
 }
