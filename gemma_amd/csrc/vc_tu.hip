@@ -103,6 +103,35 @@ bool small_inverse(std::vector<double> &A, int m) {
   return true;
 }
 
+// true when W^T W (m x m) is numerically rank-deficient, whatever the units of W's columns: the test runs on the equilibrated
+// S = D^-1/2 W^T W D^-1/2 (D = its diagonal, so S_jj = 1), where a pivot of the partially pivoted elimination at or below
+// 16 m eps counts as 0.  An exactly repeated column leaves a pivot of a few eps there, not 0: the pivot row is scaled by the
+// rounded reciprocal 1 / A_kk, so its twin no longer cancels exactly -- small_inverse alone would return the inverse of a
+// singular matrix.  A zero (or NaN) column is rank-deficient.
+bool rank_deficient(const std::vector<double> &A, int m) {
+  std::vector<double> r(m), S(m * m);
+  for (int j = 0; j < m; ++j) {
+    if (!(A[j * m + j] > 0.0)) return true;
+    r[j] = 1.0 / std::sqrt(A[j * m + j]);
+  }
+  for (int i = 0; i < m; ++i)
+    for (int j = 0; j < m; ++j) S[i * m + j] = A[i * m + j] * r[i] * r[j];
+  const double tol = 16.0 * m * 2.220446049250313e-16;
+  for (int k = 0; k < m; ++k) {
+    int p = k;
+    for (int i = k + 1; i < m; ++i)
+      if (std::fabs(S[i * m + k]) > std::fabs(S[p * m + k])) p = i;
+    if (!(std::fabs(S[p * m + k]) > tol)) return true;
+    if (p != k)
+      for (int j = 0; j < m; ++j) std::swap(S[k * m + j], S[p * m + j]);
+    for (int i = k + 1; i < m; ++i) {
+      const double f = S[i * m + k] / S[k * m + k];
+      for (int j = k; j < m; ++j) S[i * m + j] -= f * S[k * m + j];
+    }
+  }
+  return false;
+}
+
 double dot(const double *a, const double *b, long n, long sa = 1, long sb = 1) {
   double s = 0.0;
   for (long i = 0; i < n; ++i) s += a[i * sa] * b[i * sb];
@@ -298,7 +327,7 @@ int vc_he_x(VcResult &R, std::string &msg) {
   std::vector<double> WtW(c * c), Q((size_t)n * c, 0.0);
   for (int a = 0; a < c; ++a)
     for (int e = 0; e < c; ++e) WtW[a * c + e] = dot(&g_vc.W[a], &g_vc.W[e], n, c, c);
-  if (!small_inverse(WtW, c)) {
+  if (rank_deficient(WtW, c) || !small_inverse(WtW, c)) { // no HE fit, no REML start
     msg = "vc: W^T W is singular";
     return GEMMA_HIP_EINVAL;
   }

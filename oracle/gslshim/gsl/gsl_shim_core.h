@@ -7,8 +7,9 @@
  * restated from its documentation (Brent / Newton root solvers, LU, the F and chi-square tails, MT19937) -- so that
  * `oracle/Makefile ref` can compile /root/reference/src/*.cpp UNCHANGED, where they lie, into oracle/_ref/gemma.
  * BLAS/LAPACK calls go to the OpenBLAS that ships inside scipy (symbol prefix scipy_), the same dgemm / dsyevr
- * routines the reference calls.  Routines that only BSLMM / VC / logistic modes need (multiroot, QR, the random
- * variate generators) are declared and abort when called: they are not on the kinship + LMM path.
+ * routines the reference calls.  The multiroot solver of -vc 2 is an adaptor over include/gemma_vc_hybrid.hpp (see
+ * gsl_shim.cpp).  Routines that only BSLMM / logistic modes need (QR, the random variate generators) are declared and
+ * abort when called: they are not on the kinship + LMM + VC path.
  *
  * What this does and does not pin: every line of the reference's own arithmetic (src/lmm.cpp, src/mvlmm.cpp,
  * src/gemma_io.cpp, src/param.cpp, src/mathfunc.cpp, src/lapack.cpp ...) is the reference's; the GSL routines under
@@ -278,7 +279,7 @@ double gsl_ran_gamma(const gsl_rng *r, const double a, const double b);
 double gsl_ran_gaussian(const gsl_rng *r, const double sigma);
 double gsl_ran_geometric_pdf(const unsigned int k, const double p);
 
-/* ---- multiroots (off-path: VC) ---- */
+/* ---- multiroots (VC -vc 2: hybridsj over include/gemma_vc_hybrid.hpp) ---- */
 typedef struct {
   int (*f)(const gsl_vector *x, void *params, gsl_vector *f);
   int (*df)(const gsl_vector *x, void *params, gsl_matrix *df);
@@ -293,6 +294,8 @@ void gsl_multiroot_fdfsolver_free(gsl_multiroot_fdfsolver *s);
 int gsl_multiroot_fdfsolver_set(gsl_multiroot_fdfsolver *s, gsl_multiroot_function_fdf *fdf, const gsl_vector *x);
 int gsl_multiroot_fdfsolver_iterate(gsl_multiroot_fdfsolver *s);
 int gsl_multiroot_test_residual(const gsl_vector *f, double epsabs);
+/* not GSL: the return codes of the last gsl_multiroot_fdfsolver_iterate and gsl_multiroot_test_residual (oracle/ref_bridge.cpp) */
+extern int gsl_shim_multiroot_last[2];
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,9 @@
 #include <cfloat>
 #include <cmath>
 #include <cstdint>
+#include <vector>
+
+#include "../../include/gemma_vc_hybrid.hpp"
 
 extern "C" {
 // scipy's OpenBLAS (LP64) exports
@@ -873,13 +876,120 @@ double gsl_ran_gamma(const gsl_rng *, const double, const double) { off_path("gs
 double gsl_ran_gaussian(const gsl_rng *, const double) { off_path("gsl_ran_gaussian"); return 0; }
 double gsl_ran_geometric_pdf(const unsigned int, const double) { off_path("gsl_ran_geometric_pdf"); return 0; }
 
-// ---------------------------------------------------------------- multiroots (VC only)
+// ---------------------------------------------------------------- multiroots (VC: -vc 2)
+// gsl_multiroot_fdfsolver_hybridsj as an adaptor over gemma_vc::HybridSJ (include/gemma_vc_hybrid.hpp, MINPACK hybrj restated
+// from the published algorithm and pinned on MINPACK by tests/test_vc_cpu.py).  The solver is therefore the one the library's
+// -vc 2 drives: a reference run through this shim checks the reference's own likelihood, derivatives, inverse and se algebra,
+// not the solver.  The function is called as GSL's hybridsj calls it: fdf at the start, f at every trial point, df alone when
+// the Jacobian is refreshed at the current point (whose f is kept).  s->x, s->f, s->J (and s->dx, the last accepted step) hold
+// the current point after every call, as the reference reads them directly.
+namespace {
+struct HybridsjState {
+  gemma_vc::HybridSJ *solver = nullptr;
+  gsl_multiroot_function_fdf *fdf = nullptr;
+  bool started = false;
+};
+void hybridsj_publish(gsl_multiroot_fdfsolver *s) {
+  const gemma_vc::HybridSJ &h = *static_cast<HybridsjState *>(s->state)->solver;
+  const size_t n = s->x->size;
+  for (size_t i = 0; i < n; ++i) {
+    gsl_vector_set(s->dx, i, h.x[i] - gsl_vector_get(s->x, i));
+    gsl_vector_set(s->x, i, h.x[i]);
+    gsl_vector_set(s->f, i, h.f[i]);
+    for (size_t j = 0; j < n; ++j) gsl_matrix_set(s->J, i, j, h.J[i * n + j]);
+  }
+}
+}  // namespace
+
+// the return code of the last iterate and of the last residual test (0 = GSL_SUCCESS), for oracle/ref_bridge.cpp
+int gsl_shim_multiroot_last[2] = {0, 0};
+
 static const gsl_multiroot_fdfsolver_type hybridsj_type = {"hybridsj"};
 const gsl_multiroot_fdfsolver_type *gsl_multiroot_fdfsolver_hybridsj = &hybridsj_type;
-gsl_multiroot_fdfsolver *gsl_multiroot_fdfsolver_alloc(const gsl_multiroot_fdfsolver_type *, size_t) { off_path("gsl_multiroot_fdfsolver"); return 0; }
-void gsl_multiroot_fdfsolver_free(gsl_multiroot_fdfsolver *) {}
-int gsl_multiroot_fdfsolver_set(gsl_multiroot_fdfsolver *, gsl_multiroot_function_fdf *, const gsl_vector *) { off_path("gsl_multiroot_fdfsolver_set"); return 0; }
-int gsl_multiroot_fdfsolver_iterate(gsl_multiroot_fdfsolver *) { off_path("gsl_multiroot_fdfsolver_iterate"); return 0; }
-int gsl_multiroot_test_residual(const gsl_vector *, double) { off_path("gsl_multiroot_test_residual"); return 0; }
+
+gsl_multiroot_fdfsolver *gsl_multiroot_fdfsolver_alloc(const gsl_multiroot_fdfsolver_type *T, size_t n) {
+  if (T != gsl_multiroot_fdfsolver_hybridsj) off_path("gsl_multiroot_fdfsolver (a type other than hybridsj)");
+  gsl_multiroot_fdfsolver *s = (gsl_multiroot_fdfsolver *)calloc(1, sizeof(gsl_multiroot_fdfsolver));
+  s->type = T;
+  s->x = gsl_vector_calloc(n);
+  s->f = gsl_vector_calloc(n);
+  s->dx = gsl_vector_calloc(n);
+  s->J = gsl_matrix_calloc(n, n);
+  HybridsjState *st = new HybridsjState;
+  st->solver = new gemma_vc::HybridSJ(n, [st, n](const std::vector<double> &x, std::vector<double> &f, std::vector<double> &J,
+                                                 bool want_j) {
+    gsl_vector_const_view xv = gsl_vector_const_view_array(x.data(), n);
+    gsl_vector *fv = gsl_vector_alloc(n);
+    gsl_matrix *Jm = gsl_matrix_alloc(n, n);
+    int rc;
+    if (!st->started) {  // gsl_multiroot_fdfsolver_set: GSL_MULTIROOT_FN_EVAL_F_DF
+      rc = st->fdf->fdf(&xv.vector, st->fdf->params, fv, Jm);
+      st->started = true;
+    } else if (want_j) {  // the Jacobian refreshed at the current point: GSL_MULTIROOT_FN_EVAL_DF, f kept
+      rc = st->fdf->df(&xv.vector, st->fdf->params, Jm);
+      for (size_t i = 0; i < n; ++i) gsl_vector_set(fv, i, st->solver->f[i]);
+    } else {  // a trial point: GSL_MULTIROOT_FN_EVAL_F
+      rc = st->fdf->f(&xv.vector, st->fdf->params, fv);
+    }
+    f.resize(n);
+    for (size_t i = 0; i < n; ++i) f[i] = gsl_vector_get(fv, i);
+    if (want_j) {
+      J.resize(n * n);
+      for (size_t i = 0; i < n; ++i)
+        for (size_t j = 0; j < n; ++j) J[i * n + j] = gsl_matrix_get(Jm, i, j);
+    }
+    gsl_vector_free(fv);
+    gsl_matrix_free(Jm);
+    return rc == GSL_SUCCESS ? (int)gemma_vc::HybridSJ::EVAL_OK : (int)gemma_vc::HybridSJ::EVAL_FAIL;
+  });
+  s->state = st;
+  return s;
+}
+
+void gsl_multiroot_fdfsolver_free(gsl_multiroot_fdfsolver *s) {
+  if (!s) return;
+  HybridsjState *st = static_cast<HybridsjState *>(s->state);
+  delete st->solver;
+  delete st;
+  gsl_vector_free(s->x);
+  gsl_vector_free(s->f);
+  gsl_vector_free(s->dx);
+  gsl_matrix_free(s->J);
+  free(s);
+}
+
+int gsl_multiroot_fdfsolver_set(gsl_multiroot_fdfsolver *s, gsl_multiroot_function_fdf *fdf, const gsl_vector *x) {
+  HybridsjState *st = static_cast<HybridsjState *>(s->state);
+  st->fdf = fdf;
+  st->started = false;
+  s->fdf = fdf;
+  std::vector<double> x0(x->size);
+  for (size_t i = 0; i < x->size; ++i) x0[i] = gsl_vector_get(x, i);
+  gsl_vector_set_zero(s->x);
+  const int rc = st->solver->set(x0);
+  if (rc != gemma_vc::HybridSJ::OK) return GSL_EBADFUNC;
+  hybridsj_publish(s);
+  gsl_vector_set_zero(s->dx);
+  return GSL_SUCCESS;
+}
+
+int gsl_multiroot_fdfsolver_iterate(gsl_multiroot_fdfsolver *s) {
+  const int rc = static_cast<HybridsjState *>(s->state)->solver->iterate();
+  hybridsj_publish(s);
+  int g = GSL_SUCCESS;
+  if (rc == gemma_vc::HybridSJ::ENOPROG) g = GSL_ENOPROG;
+  else if (rc == gemma_vc::HybridSJ::ENOPROGJ) g = GSL_ENOPROGJ;
+  else if (rc != gemma_vc::HybridSJ::OK) g = GSL_EBADFUNC;
+  gsl_shim_multiroot_last[0] = g;
+  return g;
+}
+
+int gsl_multiroot_test_residual(const gsl_vector *f, double epsabs) {
+  if (epsabs < 0.0) return GSL_EBADTOL;
+  double r = 0.0;
+  for (size_t i = 0; i < f->size; ++i) r += fabs(gsl_vector_get(f, i));
+  gsl_shim_multiroot_last[1] = r < epsabs ? GSL_SUCCESS : GSL_CONTINUE;
+  return gsl_shim_multiroot_last[1];
+}
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// Test infrastructure only: C entry points onto the REFERENCE's own free functions (src/mvlmm.cpp), so that a test can
+// Test infrastructure only: C entry points onto the REFERENCE's own free functions (src/mvlmm.cpp, src/lmm.cpp, src/vc.cpp), so that a test can
 // call them with plain arrays through ctypes and compare function by function with the restatement in mvlmm_oracle.c.
 // Linked with the reference's objects (oracle/Makefile `ref` -> oracle/_ref/libgemma_ref.so); nothing is copied: the
 // declarations below repeat the signatures the reference defines at the cited lines.
@@ -8,12 +8,14 @@
 #include <iostream>
 #include <set>
 #include <sstream>
+#include <stdexcept>
 #include <string>
 #include <tuple>
 #include <vector>
 #include "gsl/gsl_matrix.h"
 #include "gsl/gsl_vector.h"
 #include "lmm.h"  // the reference's own header (-I/root/reference/src): class LMM, SUMSTAT, SnpNameValues
+#include "vc.h"   // class VC, VC_PARAM
 
 // src/lapack.h:34 (definition src/lapack.cpp:260-291): all eigenpairs through dsyevr_, eval < 1e-10 -> 0
 double EigenDecomp_Zeroed(gsl_matrix *G, gsl_matrix *U, gsl_vector *eval, const size_t flag_largematrix);
@@ -35,6 +37,10 @@ double MphNR(const char func_name, const size_t max_iter, const double max_prec,
              gsl_matrix *V_e, gsl_matrix *Hessian_inv, double &crt_a, double &crt_b, double &crt_c);
 // src/mvlmm.cpp:2952-2953
 double PCRT(const size_t mode, const size_t d_size, const double p_value, const double crt_a, const double crt_b, const double crt_c);
+// src/vc.cpp:325-380: dev1 and the AI matrix dev2 at log sigma2 (sigma2 with noconstrain), through UpdateParam
+int LogRL_dev12(const gsl_vector *log_sigma2, void *params, gsl_vector *dev1, gsl_matrix *dev2);
+// oracle/gslshim: the return codes of the last hybridsj iterate and residual test
+extern "C" int gsl_shim_multiroot_last[2];
 // src/mvlmm.cpp:213-214
 double EigenProc(const gsl_matrix *V_g, const gsl_matrix *V_e, gsl_vector *D_l, gsl_matrix *UltVeh, gsl_matrix *UltVehi);
 
@@ -156,5 +162,162 @@ int ref_plink_kin(const char *file_bed, size_t ni, size_t ns, int k_mode, double
   const bool ok = PlinkKin(std::string(file_bed), ind, k_mode, 100000000, &Km.matrix);
   std::cout.rdbuf(old);
   return ok ? 0 : 1;
+}
+}  // extern "C"
+
+// -vc 1 / -vc 2: class VC as src/gemma.cpp:2328-2388 sets it up.  Ks: n_vc kinships of n x n, row-major, one after the other,
+// as the call site hands them to CalcVChe / CalcVCreml (already centred by CenterMatrix(G)); they are laid side by side into
+// G (n x n n_vc) and v_traceG is the mean diagonal of each.  W: n x n_cvt (intercept included), y: n.
+namespace {
+struct VcInputs {
+  gsl_matrix *G, *W;
+  gsl_vector *y;
+  std::vector<double> traceG;
+  VcInputs(size_t n, size_t n_vc, const double *Ks, const double *W_, size_t n_cvt, const double *y_) {
+    G = gsl_matrix_alloc(n, n * n_vc);
+    W = gsl_matrix_alloc(n, n_cvt);
+    y = gsl_vector_alloc(n);
+    for (size_t l = 0; l < n_vc; l++) {
+      double d = 0.0;
+      for (size_t i = 0; i < n; i++) {
+        for (size_t j = 0; j < n; j++) gsl_matrix_set(G, i, l * n + j, Ks[(l * n + i) * n + j]);
+        d += Ks[(l * n + i) * n + i];
+      }
+      traceG.push_back(d / (double)n);
+    }
+    for (size_t i = 0; i < n; i++) {
+      for (size_t a = 0; a < n_cvt; a++) gsl_matrix_set(W, i, a, W_[i * n_cvt + a]);
+      gsl_vector_set(y, i, y_[i]);
+    }
+  }
+  ~VcInputs() {
+    gsl_matrix_free(G);
+    gsl_matrix_free(W);
+    gsl_vector_free(y);
+  }
+};
+
+// a GSL error inside a call (the reference's main() installs a handler that raises SIGINT) becomes an exception caught at the
+// entry point, which then returns -2
+void vc_gsl_throw(const char *reason, const char *, int, int) { throw std::runtime_error(reason); }
+struct VcGslGuard {
+  gsl_error_handler_t *old = gsl_set_error_handler(&vc_gsl_throw);
+  ~VcGslGuard() { gsl_set_error_handler(old); }
+};
+
+void vc_out(const VC &v, size_t n_vc, double *sigma2, double *se_sigma2, double *pve, double *se_pve, double *totals) {
+  for (size_t i = 0; i <= n_vc; i++) {
+    sigma2[i] = v.v_sigma2[i];
+    se_sigma2[i] = v.v_se_sigma2[i];
+  }
+  for (size_t i = 0; i < n_vc; i++) {
+    pve[i] = v.v_pve[i];
+    se_pve[i] = v.v_se_pve[i];
+  }
+  totals[0] = v.pve_total;
+  totals[1] = v.se_pve_total;
+}
+}  // namespace
+
+extern "C" {
+// VC::CalcVChe (src/vc.cpp:1503-1724).  Out: sigma2[n_vc + 1], se_sigma2[n_vc + 1], pve[n_vc], se_pve[n_vc], totals[2]
+// (pve_total, se_pve_total), at full precision.  0, or -2 on a GSL error.
+int ref_vc_he(size_t n, size_t n_vc, const double *Ks, const double *W, size_t n_cvt, const double *y, double *sigma2,
+              double *se_sigma2, double *pve, double *se_pve, double *totals) {
+  VcInputs in(n, n_vc, Ks, W, n_cvt, y);
+  VC v;
+  v.n_vc = n_vc;
+  v.v_traceG = in.traceG;
+  std::ostringstream sink;
+  std::streambuf *old = std::cout.rdbuf(sink.rdbuf());
+  try {
+    VcGslGuard g;
+    v.CalcVChe(in.G, in.W, in.y);
+  } catch (const std::runtime_error &) {
+    std::cout.rdbuf(old);
+    return -2;
+  }
+  std::cout.rdbuf(old);
+  vc_out(v, n_vc, sigma2, se_sigma2, pve, se_pve, totals);
+  return 0;
+}
+
+// VC::CalcVCreml (src/vc.cpp:1726-1931), the multiroot solver from oracle/gslshim.  Out as ref_vc_he, and
+// iter_sigma2 (iter_cap x (n_vc + 1)): sigma2 of iterations 0 .. the last, parsed from the "iteration k" / "sigma2 = " lines
+// the call prints to std::cout, captured with the stream's precision raised to 17 significant digits (round-trip exact);
+// status[0]: 0 converged (residual test met), 1 iteration limit, 2 / 3 GSL_ENOPROG / GSL_ENOPROGJ.  Returns the
+// iteration count (-1 if the printout cannot be parsed).  A GSL error (where the reference's own run dies) ends the call with
+// status[0] = -1: the count and iter_sigma2 are then those printed before it, the estimates are not written.
+long ref_vc_reml(int noconstrain, size_t n, size_t n_vc, const double *Ks, const double *W, size_t n_cvt, const double *y,
+                 double *sigma2, double *se_sigma2, double *pve, double *se_pve, double *totals, double *iter_sigma2,
+                 size_t iter_cap, double *status) {
+  VcInputs in(n, n_vc, Ks, W, n_cvt, y);
+  VC v;
+  v.n_vc = n_vc;
+  v.v_traceG = in.traceG;
+  gsl_shim_multiroot_last[0] = gsl_shim_multiroot_last[1] = 0;
+  std::ostringstream sink;
+  std::streambuf *old = std::cout.rdbuf(sink.rdbuf());
+  const std::streamsize prec = std::cout.precision(17);
+  bool failed = false;
+  try {
+    VcGslGuard g;
+    v.CalcVCreml(noconstrain != 0, in.G, in.W, in.y);
+  } catch (const std::runtime_error &) {
+    failed = true;
+  }
+  std::cout.precision(prec);
+  std::cout.rdbuf(old);
+  if (!failed) vc_out(v, n_vc, sigma2, se_sigma2, pve, se_pve, totals);
+  std::istringstream lines(sink.str());
+  std::string line;
+  long iter = -1;
+  bool want = false;
+  while (std::getline(lines, line)) {
+    if (line.compare(0, 10, "iteration ") == 0) {
+      iter = std::stol(line.substr(10));
+      want = true;
+    } else if (want && line.compare(0, 9, "sigma2 = ") == 0) {
+      std::istringstream vals(line.substr(9));
+      if (iter < 0 || (size_t)iter >= iter_cap) return -1;
+      for (size_t i = 0; i <= n_vc; i++)
+        if (!(vals >> iter_sigma2[iter * (n_vc + 1) + i])) return -1;
+      want = false;
+    }
+  }
+  if (failed) status[0] = -1;
+  else if (gsl_shim_multiroot_last[0] == GSL_ENOPROG) status[0] = 2;
+  else if (gsl_shim_multiroot_last[0] == GSL_ENOPROGJ) status[0] = 3;
+  else status[0] = gsl_shim_multiroot_last[1] == GSL_SUCCESS ? 0 : 1;
+  return iter;
+}
+
+// LogRL_dev12 (src/vc.cpp:325-380) at x: dev1 (n_vc + 1) and dev2 ((n_vc + 1)^2, row-major); 0, or -2 on a GSL error
+int ref_vc_logrl_dev12(int noconstrain, size_t n, size_t n_vc, const double *Ks, const double *W, size_t n_cvt,
+                        const double *y, const double *x, double *dev1, double *dev2) {
+  VcInputs in(n, n_vc, Ks, W, n_cvt, y);
+  const size_t m = n_vc + 1;
+  gsl_matrix *P = gsl_matrix_alloc(n, n), *KPy = gsl_matrix_alloc(n, m), *PKPy = gsl_matrix_alloc(n, m);
+  gsl_matrix *Hessian = gsl_matrix_alloc(m, m);
+  gsl_vector *Py = gsl_vector_alloc(n);
+  VC_PARAM params = {in.G, in.W, in.y, P, Py, KPy, PKPy, Hessian, noconstrain != 0};
+  gsl_vector_view xv = vview(x, m), d1 = gsl_vector_view_array(dev1, m);
+  gsl_matrix_view d2 = gsl_matrix_view_array(dev2, m, m);
+  std::ostringstream sink;
+  std::streambuf *old = std::cout.rdbuf(sink.rdbuf());
+  int rc = 0;
+  try {
+    VcGslGuard g;
+    LogRL_dev12(&xv.vector, &params, &d1.vector, &d2.matrix);
+  } catch (const std::runtime_error &) {
+    rc = -2;
+  }
+  std::cout.rdbuf(old);
+  gsl_matrix_free(P);
+  gsl_matrix_free(KPy);
+  gsl_matrix_free(PKPy);
+  gsl_matrix_free(Hessian);
+  gsl_vector_free(Py);
+  return rc;
 }
 }

@@ -1,6 +1,8 @@
-"""Shared by test_reference_pin.py (CPU: oracle vs reference) and test_gpu_reference.py (GPU: HIP path vs reference):
-loads tests/golden/ref_*.npz -- outputs of the reference itself (oracle/_ref/gemma, see tests/golden/make_ref_fixtures.py)
--- and the input decoding both need.  Nothing here computes a statistic."""
+"""Shared by test_reference_pin.py (CPU: oracle vs reference) and test_gpu_reference.py / test_gpu_vc.py (GPU: HIP path vs
+reference): loads tests/golden/ref_*.npz -- outputs of the reference itself (oracle/_ref/gemma, see
+tests/golden/make_ref_fixtures.py) -- and the input decoding both need, and records / replays in-process calls of the
+reference (Calls, tests/golden/ref_calls/).  Nothing here computes a statistic."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -103,3 +105,71 @@ def mv_row_err(got, ref):
         scale = np.maximum(np.abs(r).max(axis=1, keepdims=True), 1e-300)
         worst = np.maximum(worst, (np.abs(g - r) / scale).max(axis=1))
     return worst
+
+
+def dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+CALLS = os.path.join(GOLD, "ref_calls")
+
+
+class Calls:
+    """The in-process calls of the reference one test makes: live through oracle/_ref/libgemma_ref.so (so) or the oracle's
+    bridges (orc), or, with so = None, replayed from tests/golden/ref_calls/<name>.npz after checking that each call gets
+    the inputs the recorded one had.  GEMMA_REF_RECORD=1 with a live library rewrites the recording (save())."""
+
+    def __init__(self, name, so, orc):
+        self.path = os.path.join(CALLS, name.replace("[", "_").replace("]", "") + ".npz")
+        self.so, self.orc, self.i, self.rec = so, orc, 0, {}
+        self.live = so is not None
+        self.record = self.live and os.environ.get("GEMMA_REF_RECORD") == "1"
+        if not self.live:
+            d = np.load(self.path)
+            self.rec = {k: d[k] for k in d.files}
+
+    def ref(self, name, *args):
+        """so.<name>(*args) (ctypes; numpy arrays go in as double *)"""
+        fn = (lambda *a: getattr(self.so, name)(*[dp(x) if isinstance(x, np.ndarray) else x for x in a])) if self.live else None
+        return self._call(fn, args, {})
+
+    def oracle(self, name, *args, **kw):
+        """oracle.<name>(*args, **kw): the in-process bridges to the reference (ref_lmm_analyze, ref_plink_kin, ...)"""
+        return self._call(getattr(self.orc, name) if self.live else None, args, kw)
+
+    def _call(self, fn, args, kw):
+        k = "c%d_" % self.i
+        self.i += 1
+        arrs = [(j, a) for j, a in enumerate(args) if isinstance(a, np.ndarray)]
+        fp = [v for _, a in arrs for v in (float(np.nansum(a)), float(np.nansum(np.abs(a))))]
+        fp += [float(a) for a in list(args) + list(kw.values()) if isinstance(a, (int, float, np.floating, np.integer))]
+        fp = np.array(fp, dtype=np.float64)
+        if not self.live:
+            want = self.rec[k + "fp"]
+            assert want.shape == fp.shape and np.all(np.abs(fp - want) <= 1e-9 * np.abs(want) + 1e-300), (self.path, k, fp, want)
+            for j, a in arrs:
+                if k + "a%d" % j in self.rec:
+                    np.copyto(a, self.rec[k + "a%d" % j])
+            if k + "r" in self.rec:
+                return self.rec[k + "r"][()] if self.rec[k + "r"].ndim == 0 else self.rec[k + "r"]
+            return tuple(self.rec[k + "r%d" % t][()] if self.rec[k + "r%d" % t].ndim == 0 else self.rec[k + "r%d" % t]
+                         for t in range(int(self.rec[k + "nr"])))
+        before = [a.copy() for _, a in arrs]
+        ret = fn(*args, **kw)
+        if self.record:
+            self.rec[k + "fp"] = fp
+            for (j, a), b in zip(arrs, before):
+                if not np.array_equal(a, b, equal_nan=True):
+                    self.rec[k + "a%d" % j] = a.copy()
+            if isinstance(ret, tuple):
+                self.rec[k + "nr"] = np.array(len(ret))
+                for t, r in enumerate(ret):
+                    self.rec[k + "r%d" % t] = np.asarray(r)
+            else:
+                self.rec[k + "r"] = np.asarray(ret)
+        return ret
+
+    def save(self):
+        if self.record:
+            os.makedirs(CALLS, exist_ok=True)
+            np.savez_compressed(self.path, **self.rec)

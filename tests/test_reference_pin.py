@@ -213,64 +213,7 @@ def test_mvlmm_ml_em_three_traits(oracle, mvcases, mode):
 # reference's own sources); elsewhere the tests replay what the same calls returned there, kept in
 # tests/golden/ref_calls/<test>.npz (GEMMA_REF_RECORD=1 rewrites them from the live library).  A replayed call first checks that
 # it is handed the inputs the recorded call had (sum and sum of magnitudes of every array, every scalar, to 1e-9).
-CALLS = os.path.join(R.GOLD, "ref_calls")
-
-
-class _Calls:
-    def __init__(self, name, so, orc):
-        self.path = os.path.join(CALLS, name.replace("[", "_").replace("]", "") + ".npz")
-        self.so, self.orc, self.i, self.rec = so, orc, 0, {}
-        self.live = so is not None
-        self.record = self.live and os.environ.get("GEMMA_REF_RECORD") == "1"
-        if not self.live:
-            d = np.load(self.path)
-            self.rec = {k: d[k] for k in d.files}
-
-    def ref(self, name, *args):
-        """so.<name>(*args) (ctypes; numpy arrays go in as double *)"""
-        fn = (lambda *a: getattr(self.so, name)(*[_dp(x) if isinstance(x, np.ndarray) else x for x in a])) if self.live else None
-        return self._call(fn, args, {})
-
-    def oracle(self, name, *args, **kw):
-        """oracle.<name>(*args, **kw): the in-process bridges to the reference (ref_lmm_analyze, ref_plink_kin, ...)"""
-        return self._call(getattr(self.orc, name) if self.live else None, args, kw)
-
-    def _call(self, fn, args, kw):
-        k = "c%d_" % self.i
-        self.i += 1
-        arrs = [(j, a) for j, a in enumerate(args) if isinstance(a, np.ndarray)]
-        fp = [v for _, a in arrs for v in (float(np.nansum(a)), float(np.nansum(np.abs(a))))]
-        fp += [float(a) for a in list(args) + list(kw.values()) if isinstance(a, (int, float, np.floating, np.integer))]
-        fp = np.array(fp, dtype=np.float64)
-        if not self.live:
-            want = self.rec[k + "fp"]
-            assert want.shape == fp.shape and np.all(np.abs(fp - want) <= 1e-9 * np.abs(want) + 1e-300), (self.path, k, fp, want)
-            for j, a in arrs:
-                if k + "a%d" % j in self.rec:
-                    np.copyto(a, self.rec[k + "a%d" % j])
-            if k + "r" in self.rec:
-                return self.rec[k + "r"][()] if self.rec[k + "r"].ndim == 0 else self.rec[k + "r"]
-            return tuple(self.rec[k + "r%d" % t][()] if self.rec[k + "r%d" % t].ndim == 0 else self.rec[k + "r%d" % t]
-                         for t in range(int(self.rec[k + "nr"])))
-        before = [a.copy() for _, a in arrs]
-        ret = fn(*args, **kw)
-        if self.record:
-            self.rec[k + "fp"] = fp
-            for (j, a), b in zip(arrs, before):
-                if not np.array_equal(a, b, equal_nan=True):
-                    self.rec[k + "a%d" % j] = a.copy()
-            if isinstance(ret, tuple):
-                self.rec[k + "nr"] = np.array(len(ret))
-                for t, r in enumerate(ret):
-                    self.rec[k + "r%d" % t] = np.asarray(r)
-            else:
-                self.rec[k + "r"] = np.asarray(ret)
-        return ret
-
-    def save(self):
-        if self.record:
-            os.makedirs(CALLS, exist_ok=True)
-            np.savez_compressed(self.path, **self.rec)
+CALLS, _Calls = R.CALLS, R.Calls  # tests/refcases.py: shared with the GPU tests that replay these recordings
 
 
 @pytest.fixture
@@ -298,11 +241,18 @@ def _refso():
         so.ref_PCRT.argtypes = [C.c_size_t, C.c_size_t] + [C.c_double] * 4
     so.ref_EigenProc.restype = C.c_double
     so.ref_EigenProc.argtypes = [C.c_size_t] + [P] * 5
+    if hasattr(so, "ref_vc_reml"):
+        vc_in = [C.c_size_t, C.c_size_t, P, P, C.c_size_t, P]  # n, n_vc, Ks, W, n_cvt, y
+        so.ref_vc_he.restype = C.c_int
+        so.ref_vc_he.argtypes = vc_in + [P] * 5
+        so.ref_vc_reml.restype = C.c_long
+        so.ref_vc_reml.argtypes = [C.c_int] + vc_in + [P] * 6 + [C.c_size_t, P]
+        so.ref_vc_logrl_dev12.restype = C.c_int
+        so.ref_vc_logrl_dev12.argtypes = [C.c_int] + vc_in + [P] * 3
     return so
 
 
-def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
+_dp = R.dp
 
 
 def _snp_design(c, s):
@@ -641,3 +591,87 @@ def test_mvlmm_six_traits_null_and_per_snp(oracle):
         err = R.mv_row_err(got, R.mv_ref_table(fw, "w", mode, 6))
         print("six traits, mode %d: median %.2e max %.2e" % (mode, float(np.median(err)), float(err.max())))
         assert np.median(err) < 1e-4 and err.max() < 5e-3, (mode, float(np.median(err)), float(err.max()))
+
+
+# ----------------------------------------------------------------------------- -vc 1 / -vc 2: class VC (src/vc.cpp)
+# The reference's VC::CalcVChe, VC::CalcVCreml and LogRL_dev12 in-process (oracle/ref_bridge.cpp ref_vc_*).  -vc 2's multiroot
+# solver there is oracle/gslshim's adaptor over include/gemma_vc_hybrid.hpp -- the solver the library drives, pinned on
+# MINPACK by tests/test_vc_cpu.py -- so what these tests check independently is the reference's own likelihood, derivatives,
+# inverse and se / pve algebra, and the restatement's reading of them (tests/vccases.py, gemma_amd/csrc/vc_tu.hip).
+import vccases as V  # noqa: E402
+
+
+def _vc_so():
+    so = _refso()
+    if so is not None and not hasattr(so, "ref_vc_reml"):
+        pytest.skip("oracle/_ref/libgemma_ref.so predates the VC bridge (make -C oracle ref)")
+
+
+@pytest.mark.parametrize("tag", [c[0] for c in V.HE_CASES])
+def test_reference_vc_logrl_dev12(refcalls, tag):
+    """LogRL_dev12 (UpdateParam's H, H^-1, P, Py, KPy, PKPy; dev1 and the AI matrix) against the numpy restatement at the
+    REML start and at two points around it, on the log scale and (at the start) with noconstrain: within 1e-12 relative,
+    element by element on dev1, on the largest element of dev2 (observed: below 2e-14)"""
+    _vc_so()
+    Ks, W, y = V.inputs(tag)
+    K, Wc, yc = V.ref_args(Ks, W, y)
+    x0 = V.he_start(Ks, W, y)
+    m = len(x0)
+    points = [(x0, False), (x0 + 0.3 * (-1.0) ** np.arange(m), False), (x0 - 0.5, False), (V.he_start(Ks, W, y, True), True)]
+    for x, nc in points:
+        if nc and np.any(x <= 0):  # a negative HE component: H is not a covariance there
+            continue
+        d1, d2 = np.zeros(m), np.zeros((m, m))
+        rc = refcalls.ref("ref_vc_logrl_dev12", int(nc), len(y), len(Ks), K, Wc, W.shape[1], yc, np.ascontiguousarray(x), d1, d2)
+        assert rc == 0
+        e1, e2 = V.reml_dev(x, Ks, W, y) if nc else V.reml_log_dev(x, Ks, W, y)
+        assert np.all(np.abs(e1 - d1) <= 1e-12 * np.abs(d1)), (x, e1, d1)
+        assert np.abs(e2 - d2).max() <= 1e-12 * np.abs(d2).max(), (x, e2, d2)
+        assert np.array_equal(d2, d2.T)
+
+
+@pytest.mark.parametrize("tag", [c[0] for c in V.HE_CASES])
+def test_reference_vc_he(refcalls, tag):
+    """VC::CalcVChe at full precision against the numpy restatement: 1e-10 (the printed fixtures pin 6 digits)"""
+    _vc_so()
+    Ks, W, y = V.inputs(tag)
+    K, Wc, yc = V.ref_args(Ks, W, y)
+    m = len(Ks)
+    out = [np.zeros(m + 1), np.zeros(m + 1), np.zeros(m), np.zeros(m), np.zeros(2)]
+    assert refcalls.ref("ref_vc_he", len(y), m, K, Wc, W.shape[1], yc, *out) == 0
+    r = V.he(Ks, W, y)
+    got = dict(sigma2=out[0], se_sigma2=out[1], pve=out[2], se_pve=out[3], pve_total=out[4][0], se_pve_total=out[4][1])
+    for key in got:
+        assert np.allclose(np.atleast_1d(r[key]), np.atleast_1d(got[key]), rtol=1e-10, atol=0), (key, r[key], got[key])
+
+
+@pytest.fixture(scope="module")
+def hybrid_lib(tmp_path_factory):
+    return V.hybrid_drive_lib(tmp_path_factory.mktemp("hybrid_drive"))
+
+
+@pytest.mark.parametrize("tag,itag,noconstrain", V.REML_CASES, ids=[c[0] for c in V.REML_CASES])
+def test_reference_vc_reml(refcalls, hybrid_lib, tag, itag, noconstrain):
+    """VC::CalcVCreml in-process against (a) the numpy LogRL_dev12 driven by the same host hybridsj in GEMMA's loop: the same
+    status and iteration count, every iterate and every field within 1e-10 relative (observed: below 4e-13; VB1r and VB2r
+    run 56 and 38 iterations with a component near 0); (b) the reference binary's own -vc 2 printout
+    (tests/golden/text/<tag>.log.json, 6 significant digits): the sigma2 of every iteration and the final estimates.
+    V2cr and V3r: the reference dies on its first trial point (H singular, REML_DIES); so do the numpy evaluations there."""
+    _vc_so()
+    Ks, W, y = V.inputs(itag)
+    ref = V.ref_reml(refcalls.ref, Ks, W, y, noconstrain)
+    fx = V.fixture(tag)
+    printed = np.array(fx["iterations"], dtype=float)
+    assert ref["iterations"] == len(printed) - 1
+    assert np.allclose(ref["iter_sigma2"], printed, rtol=5e-6, atol=0), (ref["iter_sigma2"], printed)
+    got = V.numpy_reml(hybrid_lib, Ks, W, y, noconstrain)
+    assert (got["status"], got["iterations"]) == (ref["status"], ref["iterations"])
+    assert np.allclose(got["iter_sigma2"], ref["iter_sigma2"], rtol=1e-10, atol=0)
+    if tag in V.REML_DIES:
+        assert ref["status"] == -1 and fx["error"] == ["GSL ERROR: matrix is singular"]
+        return
+    assert ref["status"] == 0 and "error" not in fx
+    for key in ("sigma2", "se_sigma2", "pve", "se_pve", "pve_total", "se_pve_total"):
+        assert np.allclose(np.atleast_1d(got[key]), np.atleast_1d(ref[key]), rtol=1e-10, atol=0), (key, got[key], ref[key])
+    for key, fk in (("sigma2", "sigma2 estimates"), ("se_sigma2", "se(sigma2)"), ("pve", "pve estimates"), ("se_pve", "se(pve)")):
+        assert np.allclose(ref[key], np.array(fx[fk], dtype=float), rtol=5e-6, atol=0), (key, ref[key], fx[fk])

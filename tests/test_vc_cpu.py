@@ -95,3 +95,22 @@ def test_new_entry_points_fail_without_device():
         api.VC().CalcVCreml([np.eye(4)], np.ones((4, 1)), np.arange(4.0))
     assert lib.gemma_hip_vc_he(None, None, None, None, None, None) != L.OK
     assert lib.gemma_hip_strerror(L.ENOTPD).decode() == "matrix not positive definite"
+
+
+@pytest.mark.parametrize("n", [257, 385])
+@pytest.mark.parametrize("kappa", [1e2, 1e6, 1e10])
+def test_spd_reference_sits_100x_below_the_bound(n, kappa):
+    """the high-precision reference of tests/test_gpu_vc.py's prescribed-spectrum inverses (vccases.spd_spectrum), at its
+    largest sizes.  Its error has two parts, each held below 1 / 100 of the bound SPD_C n eps kappa asserted there:
+    - what one Newton step leaves: measured as the move of a second long-double step (observed: below 2e-3 of the bound);
+    - the floor of the long-double residual I - A X itself, which a further step cannot reveal: estimated as the effect on X
+      of the difference between the residual summed in forward and in reverse order (observed: below 4e-5 of the bound)."""
+    from vccases import SPD_C, spd_spectrum
+    bound = SPD_C * n * np.finfo(float).eps * kappa
+    A, X1 = spd_spectrum(n, kappa, n)
+    _, X2 = spd_spectrum(n, kappa, n, steps=2)
+    moved = np.abs(X2 - X1).max() / np.abs(X2).max()
+    Al, Xl = A.astype(np.longdouble), X1.astype(np.longdouble)
+    d = (Al @ Xl - Al[:, ::-1] @ Xl[::-1, :]).astype(np.float64)
+    floor = np.abs(X1 @ d).max() / np.abs(X1).max()
+    assert moved <= bound / 100 and floor <= bound / 100, (moved / bound, floor / bound)

@@ -165,3 +165,128 @@ def reml_summary(s2, Ks, W, y, noconstrain=False):
             G[k, i] = g * jac[i]
     var = np.array([-(G[k] @ Hi @ G[k]) for k in range(nvc + 1)])
     return dict(se_sigma2=se, pve=pve, se_pve=np.sqrt(var[:nvc]), pve_total=pve.sum(), se_pve_total=np.sqrt(var[nvc]))
+
+
+# -vc 2 on the fixtures: (tag of tests/golden/text/<tag>.log.json, tag of the inputs in HE_CASES, noconstrain)
+REML_CASES = [("V1r", "V1", False), ("V1cr", "V1c", False), ("V2cr", "V2c", False), ("V3r", "V3", False),
+              ("VB1r", "VB1", False), ("VB2r", "VB2", False), ("V1nr", "V1", True)]
+# the reference's own -vc 2 dies on these: its first trial point (the full Gauss-Newton step on log sigma2) sends every sigma2
+# to 0 or to infinity, H is singular and LUInvert raises "matrix is singular" (src/lapack.cpp:323-329)
+REML_DIES = ("V2cr", "V3r")
+ITER_CAP = 102
+SPD_C = 0.01  # the SPD inverse's forward-error bound (tests/test_gpu_vc.py): ||X - A^-1||_max <= SPD_C n eps kappa ||A^-1||_max
+_INPUTS = {}
+
+
+def inputs(tag):
+    """(Ks, W, y) of an HE_CASES tag, built once per process (callers must not modify them)"""
+    if tag not in _INPUTS:
+        _INPUTS[tag] = dict(HE_CASES)[tag]()
+    return _INPUTS[tag]
+
+
+def he_start(Ks, W, y, noconstrain=False):
+    """the REML start of src/vc.cpp:1746-1758: the HE sigma2, log(0.1) for components <= 0 on the log scale"""
+    h = he(Ks, W, y)["sigma2"]
+    return h.copy() if noconstrain else np.log(np.where(h > 0, h, 0.1))
+
+
+def ref_args(Ks, W, y):
+    """the kinships one after the other, W and y as the ref_vc_* entry points of oracle/ref_bridge.cpp take them"""
+    return (np.ascontiguousarray(np.stack(Ks)), np.ascontiguousarray(W, dtype=np.float64),
+            np.ascontiguousarray(y, dtype=np.float64))
+
+
+def ref_reml(call, Ks, W, y, noconstrain=False):
+    """call('ref_vc_reml', ...) (a refcalls.ref of tests/test_reference_pin.py, live or replayed): the reference's
+    VC::CalcVCreml at full precision.  status = -1 where the reference's run dies on a GSL error (iterations = those
+    printed before it)."""
+    n, nvc = len(y), len(Ks)
+    K, W, y = ref_args(Ks, W, y)
+    r = dict(sigma2=np.zeros(nvc + 1), se_sigma2=np.zeros(nvc + 1), pve=np.zeros(nvc), se_pve=np.zeros(nvc),
+             totals=np.zeros(2), iter_sigma2=np.zeros((ITER_CAP, nvc + 1)), status=np.zeros(1))
+    it = call("ref_vc_reml", int(noconstrain), n, nvc, K, W, W.shape[1], y, r["sigma2"], r["se_sigma2"], r["pve"], r["se_pve"],
+              r["totals"], r["iter_sigma2"], ITER_CAP, r["status"])
+    r["iterations"] = int(it)
+    r["status"] = int(r["status"][0])
+    r["pve_total"], r["se_pve_total"] = r["totals"]
+    r["iter_sigma2"] = r["iter_sigma2"][:int(it) + 1]
+    return r
+
+
+def hybrid_drive_lib(tmpdir):
+    """tests/cpp/hybrid_drive.cpp (GEMMA's -vc 2 loop around include/gemma_vc_hybrid.hpp) as a shared library"""
+    import ctypes as C
+    import subprocess
+    so = os.path.join(str(tmpdir), "libhybrid_drive.so")
+    subprocess.check_call(["g++", "-std=c++11", "-O2", "-Wall", "-Werror", "-shared", "-fPIC", "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "hybrid_drive.cpp"), "-o", so])
+    lib = C.CDLL(so)
+    P = C.POINTER(C.c_double)
+    lib.FDF = C.CFUNCTYPE(C.c_int, P, P, P)
+    lib.hybrid_drive.restype = C.c_int
+    lib.hybrid_drive.argtypes = [C.c_int, P, lib.FDF, C.c_int, C.c_double, P, C.c_int, C.POINTER(C.c_int)]
+    return lib
+
+
+def numpy_reml(lib, Ks, W, y, noconstrain=False, outside=False):
+    """the numpy LogRL_dev12 (reml_dev / reml_log_dev) solved by the host hybridsj in GEMMA's loop, and the summary at the
+    solution: the same fields as ref_reml.  An evaluation where H or W^T H^-1 W is singular fails, as the reference's does;
+    with outside, a point where H is not positive definite (Cholesky fails) is a failed step instead, as on the device."""
+    import ctypes as C
+    m = len(Ks) + 1
+    dev = (lambda z: reml_dev(z, Ks, W, y)) if noconstrain else (lambda z: reml_log_dev(z, Ks, W, y))
+
+    def cb(xp, fp, jp):
+        x = np.ctypeslib.as_array(xp, (m,)).copy()
+        if outside:
+            s2 = x if noconstrain else np.exp(x)
+            with np.errstate(all="ignore"):
+                H = sum(s * K for s, K in zip(s2, Ks)) + s2[-1] * np.eye(len(y))
+            try:
+                if not np.all(np.isfinite(H)):
+                    return 2
+                np.linalg.cholesky(H)
+            except np.linalg.LinAlgError:
+                return 2
+        try:
+            with np.errstate(all="ignore"):
+                d1, d2 = dev(x)
+        except np.linalg.LinAlgError:
+            return 1
+        np.ctypeslib.as_array(fp, (m,))[:] = d1
+        np.ctypeslib.as_array(jp, (m * m,))[:] = d2.ravel()
+        return 0
+
+    fdf = lib.FDF(cb)
+    x = np.ascontiguousarray(he_start(Ks, W, y, noconstrain))
+    iters = np.zeros((ITER_CAP, m))
+    st = C.c_int(0)
+    P = C.POINTER(C.c_double)
+    it = lib.hybrid_drive(m, x.ctypes.data_as(P), fdf, 100, 1e-3, iters.ctypes.data_as(P), ITER_CAP, C.byref(st))
+    if st.value < 0:  # the failed iteration printed nothing
+        it -= 1
+    s2 = x if noconstrain else np.exp(x)
+    r = dict(iterations=it, status=st.value, sigma2=s2,
+             iter_sigma2=iters[:it + 1] if noconstrain else np.exp(iters[:it + 1]))
+    if st.value >= 0:
+        r.update(reml_summary(s2, Ks, W, y, noconstrain=noconstrain))
+    return r
+
+
+def spd_spectrum(n, kappa, seed, steps=1):
+    """A = Q diag(ev) Q^T (symmetrised), ev geometric from 1 to kappa, and its inverse: np.linalg.inv refined by `steps`
+    Newton steps X + X (I - A X), the residual I - A X formed in np.longdouble (the correction itself is ~ kappa eps smaller
+    than X, so float64 carries it).  tests/test_vc_cpu.py holds both parts of the refined error -- what the Newton step leaves
+    and the rounding floor of the long-double residual -- below 1 / 100 of the bound the GPU tests assert."""
+    rng = np.random.default_rng(seed)
+    Q, _ = np.linalg.qr(rng.standard_normal((n, n)))
+    A = (Q * np.geomspace(1.0, kappa, n)) @ Q.T
+    A = (A + A.T) / 2
+    X = np.linalg.inv(A)
+    Al = A.astype(np.longdouble)
+    for _ in range(steps):
+        R = -(Al @ X.astype(np.longdouble))
+        R[np.diag_indices(n)] += 1
+        X = X + X @ R.astype(np.float64)
+    return A, X
