@@ -26,6 +26,10 @@ SYMBOLS = [
     "gemma_hip_dbg_last_utx_kernel", "gemma_hip_dbg_last_block_missing", "gemma_hip_reload_env", "gemma_hip_lmm_batch_pipe_d", "gemma_hip_lmm_pipe_flush",
     "gemma_hip_spd_inverse", "gemma_hip_spd_inverse_d", "gemma_hip_vc_setup", "gemma_hip_vc_setup_d", "gemma_hip_vc_he",
     "gemma_hip_vc_reml", "gemma_hip_vc_timing", "gemma_hip_vc_release",
+    "gemma_hip_ridge_setup", "gemma_hip_ridge_setup_d", "gemma_hip_ridge_setup_kept", "gemma_hip_ridge_set_r",
+    "gemma_hip_ridge_set_indicator", "gemma_hip_ridge_batch", "gemma_hip_ridge_batch_d", "gemma_hip_ridge_finish",
+    "gemma_hip_prdt_begin", "gemma_hip_prdt_add", "gemma_hip_prdt_add_d", "gemma_hip_prdt_add_bv", "gemma_hip_prdt_add_bv_d",
+    "gemma_hip_prdt_end", "gemma_hip_prdt_kin",
 ]
 COMM_ID_BYTES = 128
 
@@ -189,6 +193,21 @@ def lib():
     L.gemma_hip_vc_reml.argtypes = [ci] + [dp] * 6 + [C.POINTER(ci), C.POINTER(ci), C.POINTER(C.c_long), dp, sz]
     L.gemma_hip_vc_timing.argtypes = [dp]
     L.gemma_hip_vc_release.argtypes = []
+    L.gemma_hip_ridge_setup.argtypes = [sz, dp, dp, dp, cd, sz, dp]
+    L.gemma_hip_ridge_setup_d.argtypes = [sz, dp, sz, dp, dp, cd, sz, dp, vp]
+    L.gemma_hip_ridge_setup_kept.argtypes = [dp, cd, sz, dp]
+    L.gemma_hip_ridge_set_r.argtypes = [sz, dp, cd]
+    L.gemma_hip_ridge_set_indicator.argtypes = [vp, sz]
+    L.gemma_hip_ridge_batch.argtypes = [ci, vp, sz, sz, dp]
+    L.gemma_hip_ridge_batch_d.argtypes = [ci, vp, sz, sz, dp, vp]
+    L.gemma_hip_ridge_finish.argtypes = []
+    L.gemma_hip_prdt_begin.argtypes = [vp, sz]
+    L.gemma_hip_prdt_add.argtypes = [ci, vp, sz, sz, dp, vp]
+    L.gemma_hip_prdt_add_d.argtypes = [ci, vp, sz, sz, dp, vp, vp]
+    L.gemma_hip_prdt_add_bv.argtypes = [dp, sz, dp, sz]
+    L.gemma_hip_prdt_add_bv_d.argtypes = [dp, sz, sz, dp, sz, vp]
+    L.gemma_hip_prdt_end.argtypes = [cd, ci, dp]
+    L.gemma_hip_prdt_kin.argtypes = [sz, dp, vp, dp, sz, dp, cd, cd, sz, dp, dp]
     for s in SYMBOLS:
         getattr(L, s)  # AttributeError if the library does not export what the header declares
     _lib = L

@@ -835,3 +835,268 @@ class VC:
         finally:
             L.lib().gemma_hip_vc_release()
         return self
+
+
+# ----------------------------------------------------------------------------- genomic prediction (-bslmm 2, -predict 1 / 2)
+def _g6(v):
+    """A double as the reference's default stream precision prints it (`outfile << d`: %g with six significant digits)."""
+    return "%g" % v
+
+
+def _blocks(geno, batch):
+    geno = np.ascontiguousarray(geno)
+    for s0 in range(0, geno.shape[0], batch):
+        yield geno[s0:s0 + batch]
+
+
+def ridge_set_r(r, scale=1.0):
+    """gemma_hip_ridge_set_r: the vector of the genotype product as it is (ridge_batch then returns scale * X_c' r)."""
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    L.check(L.lib().gemma_hip_ridge_set_r(r.size, _ptr(r), scale), "ridge_set_r")
+
+
+def ridge_set_indicator(indicator_idv):
+    ind = np.ascontiguousarray(indicator_idv, dtype=np.int32)
+    L.check(L.lib().gemma_hip_ridge_set_indicator(_ptr(ind), ind.size), "ridge_set_indicator")
+
+
+def ridge_batch(geno, geno_kind, out=None):
+    """One block of SNP-major rows -> alpha (numpy in / out, or torch device tensors in / out on torch's current stream)."""
+    l = geno.shape[0]
+    if _is_torch(geno):
+        import torch
+        if out is None:
+            out = torch.empty(l, dtype=torch.float64, device=geno.device)
+        L.check(L.lib().gemma_hip_ridge_batch_d(geno_kind, C.c_void_p(geno.data_ptr()), l, _tld(geno), C.c_void_p(out.data_ptr()),
+                                                _stream()), "ridge_batch")
+        return out
+    geno = np.ascontiguousarray(geno)
+    if out is None:
+        out = np.zeros(l)
+    L.check(L.lib().gemma_hip_ridge_batch(geno_kind, _ptr(geno), l, geno.strides[0] // geno.itemsize if l else 0, _ptr(out)),
+            "ridge_batch")
+    return out
+
+
+def ridge_finish():
+    L.check(L.lib().gemma_hip_ridge_finish(), "ridge_finish")
+
+
+class BSLMM:
+    """Mirror of class BSLMM (src/bslmm.h) for its deterministic mode, `-bslmm 2` (a_mode 12): RidgeR, WriteParam, WriteBV, and the
+    fields of the summary the reference logs for the fit (src/gemma.cpp:2938-2946, :2885; PARAM::pheno_mean)."""
+
+    def __init__(self):
+        self.a_mode = 12
+        self.alpha = np.zeros(0)
+        self.bv = np.zeros(0)
+        self.pheno_mean = 0.0
+        self.l_remle_null = self.pve_null = self.pve_se_null = float("nan")
+
+    def FitNull(self, eval_, UtW, Uty, trace_G, pheno_mean=0.0, l_min=1e-5, l_max=1e5, n_region=10):
+        """CalcLambda 'R' + CalcPve of the call site (src/gemma.cpp:2939-2944) on the library's null fit; pheno_mean is what
+        CenterVector(y) returned (:2885).  Returns lambda."""
+        nf = CalcLambdaNull(eval_, UtW, Uty, l_min, l_max, n_region, trace_G)
+        self.l_remle_null, self.pve_null, self.pve_se_null = nf["l_remle_null"], nf["pve"], nf["pve_se"]
+        self.pheno_mean = float(pheno_mean)
+        return self.l_remle_null
+
+    def RidgeR(self, U, eval_, Uty, lambda_, geno, geno_kind, indicator_idv=None, ns_test=None, batch=LMM_BATCH_SIZE):
+        """BSLMM::RidgeR (src/bslmm.cpp:1194-1221) without UtX: geno holds the SNP-major rows of the analysed SNPs (fp64 with NaN,
+        or .bed bytes), over the analysed individuals or -- with indicator_idv -- over all of them.  ns_test: the SNP count the
+        effects are scaled by (default: the rows of geno).  Returns (alpha, bv)."""
+        n = U.shape[0]
+        ns_test = geno.shape[0] if ns_test is None else ns_test
+        U_c = _np64(np.ascontiguousarray(U), "U")
+        ev_c = np.ascontiguousarray(eval_, dtype=np.float64)
+        Uty_c = np.ascontiguousarray(Uty, dtype=np.float64)
+        bv = np.zeros(n)
+        L.check(L.lib().gemma_hip_ridge_setup(n, _ptr(U_c), _ptr(ev_c), _ptr(Uty_c), float(lambda_), int(ns_test), _ptr(bv)),
+                "BSLMM.RidgeR")
+        try:
+            if indicator_idv is not None:
+                ridge_set_indicator(indicator_idv)
+            outs = [ridge_batch(blk, geno_kind) for blk in _blocks(geno, batch)]
+        finally:
+            ridge_finish()
+        self.alpha = np.concatenate(outs) if outs else np.zeros(0)
+        self.bv = bv
+        return self.alpha, self.bv
+
+    def WriteParam(self, path, snp_info, alpha=None):
+        """BSLMM::WriteParam(alpha), src/bslmm.cpp:193-235: snp_info = dicts with chr, rs, ps, n_miss of the analysed SNPs."""
+        alpha = self.alpha if alpha is None else alpha
+        with open(path, "w") as f:
+            f.write("chr\trs\tps\tn_miss\talpha\tbeta\tgamma\n")
+            for si, a in zip(snp_info, alpha):
+                # `scientific << setprecision(6)` stays set on the stream: the two zeros print in it too
+                f.write("%s\t%s\t%s\t%d\t%.6e\t%.6e\t%.6e\n" % (si["chr"], si["rs"], si["ps"], si["n_miss"], a, 0.0, 0.0))
+
+    def WriteBV(self, path, indicator_idv, bv=None):
+        """BSLMM::WriteBV, src/bslmm.cpp:116-140"""
+        bv = self.bv if bv is None else bv
+        t = 0
+        with open(path, "w") as f:
+            for k in indicator_idv:
+                if k == 0:
+                    f.write("NA\n")
+                else:
+                    f.write("%.6e\n" % bv[t])
+                    t += 1
+
+    def WriteLog(self, path):
+        """The lines of PARAM's log a later -predict run reads back (-emu; ReadFile_log, src/gemma_io.cpp:239-277) and the null
+        fit's summary beside them, in the reference's wording and default precision (src/gemma.cpp:3300-3400)."""
+        with open(path, "w") as f:
+            f.write("##\n## Summary Statistics:\n")
+            f.write("## pve estimate in the null model = %s\n" % _g6(self.pve_null))
+            f.write("## se(pve) in the null model = %s\n" % _g6(self.pve_se_null))
+            f.write("## estimated mean = %s\n" % _g6(self.pheno_mean))
+
+
+def ReadFile_log(path):
+    """ReadFile_log, src/gemma_io.cpp:239-277: the `estimated mean` of a -bslmm log (0 when the file has none)."""
+    for line in open(path):
+        t = line.replace(",", " ").split()
+        if len(t) >= 5 and t[1] == "estimated" and t[2] == "mean" and t[3] == "=":
+            return float(t[4])
+    return 0.0
+
+
+def ReadFile_est(path, est_column=None, have_ebv=False):
+    """ReadFile_est, src/gemma_io.cpp:2224-2289, with the defaults of PARAM::CheckParam (src/param.cpp:671-684): columns
+    rs, alpha, beta, gamma = 2 5 6 7, and 2 0 6 7 when an -ebv file is given -- column 0 is never met, so alpha stays 0 and a
+    ridge `.param.txt` (beta = gamma = 0) then yields effects that are all zero.  effect = alpha + beta * gamma.
+    Returns an ordered dict rs -> effect; a repeated SNP is an error, as in the reference."""
+    if est_column is None:
+        est_column = (2, 0, 6, 7) if have_ebv else (2, 5, 6, 7)
+    n = max(est_column)
+    out = {}
+    with open(path) as f:
+        f.readline()
+        for line in f:
+            t = line.split()
+            if not t:
+                continue
+            if len(t) < n:
+                raise ValueError("%s: a row has %d columns, %d needed" % (path, len(t), n))
+            alpha, beta, gamma = 0.0, 0.0, 1.0
+            rs = t[est_column[0] - 1]
+            if est_column[1] >= 1:
+                alpha = float(t[est_column[1] - 1])
+            if est_column[2] >= 1:
+                beta = float(t[est_column[2] - 1])
+            if est_column[3] >= 1:
+                gamma = float(t[est_column[3] - 1])
+            if rs in out:
+                raise ValueError("the same SNP occurs more than once in estimated parameter file: %s" % rs)
+            out[rs] = alpha + beta * gamma
+    return out
+
+
+class PRDT:
+    """Mirror of class PRDT (src/prdt.h) for -predict 1 / 2 (a_mode 41 / 42), the block of src/gemma.cpp:1660-1729:
+
+        p = PRDT(indicator_idv)            # 1 = phenotyped (training), 0 = to be predicted
+        p.AddBV(G, u_hat)                  # optional: -ebv with -k
+        p.AnalyzePlink(bed_rows, rs, mapRS2est)    # or AnalyzeBimbam(X, rs, mapRS2est)
+        y = p.Finish(pheno_mean, a_mode)   # + mean, Phi() for a_mode 42
+        p.WriteFiles(path, y)
+    """
+
+    def __init__(self, indicator_idv):
+        self.indicator_idv = np.ascontiguousarray(indicator_idv, dtype=np.int32)
+        self.ns_test = 0
+        self.ignored = []
+        L.check(L.lib().gemma_hip_prdt_begin(_ptr(self.indicator_idv), self.indicator_idv.size), "PRDT")
+
+    def AddBV(self, G, u_hat):
+        """PRDT::AddBV, src/prdt.cpp:133-205: G over all individuals (not changed), u_hat over the training individuals."""
+        u = np.ascontiguousarray(u_hat, dtype=np.float64)
+        ni = self.indicator_idv.size
+        if _is_torch(G):
+            rc = L.lib().gemma_hip_prdt_add_bv_d(C.c_void_p(G.data_ptr()), ni, _tld(G), _ptr(u), u.size, _stream())
+        else:
+            G_c = _np64(np.ascontiguousarray(G), "G")
+            if G_c.shape != (ni, ni):
+                raise ValueError("G must be %d x %d" % (ni, ni))
+            rc = L.lib().gemma_hip_prdt_add_bv(_ptr(G_c), ni, _ptr(u), u.size)
+        L.check(rc, "PRDT.AddBV")
+
+    def _analyze(self, geno, geno_kind, rs, mapRS2est, batch):
+        rs = list(rs)
+        sel = np.array([i for i, r in enumerate(rs) if r in mapRS2est], dtype=np.int64)
+        rows = np.ascontiguousarray(geno[sel])
+        eff = np.array([mapRS2est[rs[i]] for i in sel], dtype=np.float64)
+        self.ns_test = 0
+        self.ignored = []
+        for s0 in range(0, rows.shape[0], batch):
+            blk = rows[s0:s0 + batch]
+            w = np.ascontiguousarray(eff[s0:s0 + batch])
+            used = np.zeros(blk.shape[0], dtype=np.int32)
+            L.check(L.lib().gemma_hip_prdt_add(geno_kind, _ptr(blk), blk.shape[0], blk.strides[0] // blk.itemsize, _ptr(w),
+                                               _ptr(used)), "PRDT.Analyze")
+            self.ns_test += int(used.sum())
+            self.ignored += [rs[sel[s0 + i]] for i in np.flatnonzero(used == 0)]
+
+    def AnalyzePlink(self, bed_rows, rs, mapRS2est, batch=LMM_BATCH_SIZE):
+        """PRDT::AnalyzePlink, src/prdt.cpp:310-444: bed_rows = the .bed payload (one row per SNP of the .bim, over all
+        individuals), rs = their names; SNPs outside mapRS2est are passed over.  self.ignored: the SNPs missing in every
+        individual to be predicted; self.ns_test: the SNPs used."""
+        self._analyze(np.asarray(bed_rows, dtype=np.uint8), L.GENO_PLINK_2BIT, rs, mapRS2est, batch)
+
+    def AnalyzeBimbam(self, X_snpmajor_nan, rs, mapRS2est, batch=LMM_BATCH_SIZE):
+        """PRDT::AnalyzeBimbam, src/prdt.cpp:207-308: X over all individuals, NaN = NA."""
+        self._analyze(np.asarray(X_snpmajor_nan, dtype=np.float64), L.GENO_F64_SNP_MAJOR, rs, mapRS2est, batch)
+
+    def Finish(self, pheno_mean=0.0, a_mode=41):
+        """src/gemma.cpp:1711-1722: + pheno_mean; a_mode 42 (-predict 2): Phi(y).  Ends the device state."""
+        y = np.zeros(int((self.indicator_idv == 0).sum()))
+        L.check(L.lib().gemma_hip_prdt_end(float(pheno_mean), 1 if a_mode == 42 else 0, _ptr(y)), "PRDT.Finish")
+        return y
+
+    @staticmethod
+    def MvnormPrdt(G_full, indicator_pheno, W_full, y_full, l_min=1e-5, l_max=1e5, n_region=10):
+        """-predict from a kinship alone (a_mode 43) for one phenotype: the block of src/gemma.cpp:1732-1820 / :1873-1882 around
+        PRDT::MvnormPrdt (src/prdt.cpp:448-553).  G_full: the kinship of the individuals with covariates as it was read (not
+        centred); indicator_pheno: 1 = observed; W_full with the intercept; y_full: entries of the unobserved ones are not read.
+        Returns (Y_full with the missing entries predicted, dict(vg, ve, l_remle))."""
+        ind = np.ascontiguousarray(indicator_pheno, dtype=np.int32)
+        ni = ind.size
+        G_c = _np64(np.ascontiguousarray(G_full), "G_full")
+        W_c = np.ascontiguousarray(np.asarray(W_full, dtype=np.float64).reshape(ni, -1))
+        y_c = np.ascontiguousarray(y_full, dtype=np.float64)
+        if G_c.shape != (ni, ni) or y_c.shape != (ni,):
+            raise ValueError("G_full must be %d x %d and y_full of length %d" % (ni, ni, ni))
+        y_miss, fit = np.zeros(max(int((ind == 0).sum()), 1)), np.zeros(3)
+        L.check(L.lib().gemma_hip_prdt_kin(ni, _ptr(G_c), _ptr(ind), _ptr(W_c), W_c.shape[1], _ptr(y_c), l_min, l_max, n_region,
+                                           _ptr(y_miss), _ptr(fit)), "PRDT.MvnormPrdt")
+        Y = y_c.copy()
+        Y[ind == 0] = y_miss[:int((ind == 0).sum())]
+        return Y, dict(vg=fit[0], ve=fit[1], l_remle=fit[2])
+
+    @staticmethod
+    def WriteFilesFull(path, Y_full, indicator_cvt=None):
+        """PRDT::WriteFiles(gsl_matrix *), src/prdt.cpp:104-131: one row per individual, NA without covariates, a tab after
+        every value."""
+        Y = np.asarray(Y_full, dtype=np.float64).reshape(len(Y_full), -1)
+        ind = np.ones(Y.shape[0], dtype=np.int32) if indicator_cvt is None else np.asarray(indicator_cvt)
+        t = 0
+        with open(path, "w") as f:
+            for k in ind:
+                if k == 0:
+                    f.write("NA\n")
+                else:
+                    f.write("".join(_g6(v) + "\t" for v in Y[t]) + "\n")
+                    t += 1
+
+    def WriteFiles(self, path, y_prdt):
+        """PRDT::WriteFiles(gsl_vector *), src/prdt.cpp:76-102"""
+        t = 0
+        with open(path, "w") as f:
+            for k in self.indicator_idv:
+                if k == 1:
+                    f.write("NA\n")
+                else:
+                    f.write(_g6(y_prdt[t]) + "\n")
+                    t += 1

@@ -15,6 +15,7 @@
 #include "dgemm_mfma.hip.h"
 #include "eigh_tu.h"
 #include "vc_tu.h"
+#include "prdt_tu.h"
 #include "ingest.hip.h"
 #include "lm_assoc.hip.h"
 #include "lmm_assoc.hip.h"
@@ -433,6 +434,7 @@ extern "C" void gemma_hip_shutdown(void) {
   gemm_aux_destroy();
   eigh_tu_shutdown();
   vc_tu_shutdown();
+  prdt_tu_shutdown();
   g_ctx.inited = false;
 }
 
@@ -534,3 +536,4 @@ extern "C" int gemma_hip_dgemm(char ta, char tb, size_t M, size_t N, size_t K, d
 #include "abi_gxe_lm.inc.h"
 #include "abi_kept_comm.inc.h"
 #include "abi_vc.inc.h"
+#include "abi_prdt.inc.h"

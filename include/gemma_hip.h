@@ -456,6 +456,67 @@ int gemma_hip_vc_reml(int noconstrain, double *sigma2, double *se_sigma2, double
 int gemma_hip_vc_timing(double *t5);
 int gemma_hip_vc_release(void);
 
+/* ---- genomic prediction: -bslmm 2 (ridge regression / BLUP) and -predict 1 / 2 -------------------------------------------- */
+/* BSLMM::RidgeR (src/bslmm.cpp:1194-1221), called where src/gemma.cpp:2959-2960 calls it -- without the n x p matrix UtX the
+ * reference allocates for it (src/gemma.cpp:2878, :2951).  With b = Uty / (lambda eval + 1):
+ *   bv    = U (lambda eval o b)                          returned by ridge_setup (bv_out[n], may be NULL)
+ *   alpha = (lambda / ns_test) UtX' b = (lambda / ns_test) X_c' r,   r = U b  (n numbers, formed by ridge_setup and kept on the device)
+ * so the effects of a block of SNPs are one matrix-vector product on its packed rows (ridge_batch), in the centring of
+ * ReadFile_bed / ReadFile_geno with a UtX argument (src/gemma_io.cpp:1956-2084, :1742-1845): mean over the analysed non-missing
+ * calls, a missing call contributes 0.  ns_test = the number of analysed SNPs of the whole fit (UtX->size2).
+ * Host form: U (n x n), eval, Uty, bv_out on the host.  _d: all four on the device (U with leading dimension ldu), on `stream`,
+ * which is synchronised.  _kept: U and eval of the device-resident chain (eigh_kept_K / eigh_keep), Uty and bv_out on the host. */
+int gemma_hip_ridge_setup(size_t n, const double *U, const double *eval, const double *Uty, double lambda, size_t ns_test,
+                          double *bv_out);
+int gemma_hip_ridge_setup_d(size_t n, const double *U_d, size_t ldu, const double *eval_d, const double *Uty_d, double lambda,
+                            size_t ns_test, double *bv_out_d, void *stream);
+int gemma_hip_ridge_setup_kept(const double *Uty, double lambda, size_t ns_test, double *bv_out);
+/* The product alone: r[n] (host) is taken as it is and ridge_batch returns scale * X_c' r -- for callers that iterate on the
+ * genotype product (and for its tests), in place of ridge_setup. */
+int gemma_hip_ridge_set_r(size_t n, const double *r, double scale);
+/* Rows of the blocks cover ni_total individuals of which the n with indicator_idv != 0 are analysed (cPar.indicator_idv); without
+ * this call rows cover exactly the n analysed ones.  EINVAL when the indicator does not select n individuals. */
+int gemma_hip_ridge_set_indicator(const int *indicator_idv, size_t ni_total);
+/* alpha_out[l] for l SNP-major rows: GEMMA_GENO_PLINK_2BIT (ld bytes per row, >= ceil(ni_total / 4)) or
+ * GEMMA_GENO_F64_SNP_MAJOR (ld doubles per row, NaN = missing).  A SNP without a non-missing analysed call gets 0 (every entry
+ * of the reference's column is 0).  fp64 accumulation in an order fixed by the shapes alone: repeated calls agree bit for bit.
+ * _d: geno and alpha_out on the device, asynchronous on `stream`.  Any l: a block of more rows than one launch takes is cut. */
+int gemma_hip_ridge_batch(int geno_kind, const void *geno, size_t l, size_t ld, double *alpha_out);
+int gemma_hip_ridge_batch_d(int geno_kind, const void *geno_d, size_t l, size_t ld, double *alpha_out_d, void *stream);
+int gemma_hip_ridge_finish(void);
+
+/* The -predict block of src/gemma.cpp:1660-1729 on the device.  prdt_begin: indicator_idv over ni_total individuals, 1 = training
+ * (phenotyped), 0 = to be predicted; y_prdt (one entry per 0, in order) starts at zero.
+ * prdt_add = PRDT::AnalyzePlink / AnalyzeBimbam (src/prdt.cpp:310-444, :207-308; call site src/gemma.cpp:1705-1709) for l rows
+ * over all ni_total individuals with their effect sizes effect[l] (the SNPs of mapRS2est only): x_train_mean over the non-missing
+ * training calls, x_mean over the non-missing test calls, a missing test call counts x_mean - x_train_mean, every other
+ * g - x_train_mean.  used_out[l] (may be NULL): 0 for a SNP missing in every test individual (skipped, the reference's "will be
+ * ignored"), else 1.  A used SNP without a non-missing training call has x_train_mean = 0 / 0 and turns every prediction into
+ * NaN, as in the reference.  The sum over SNPs is cut into partitions by l alone and combined in index order.
+ * prdt_add_bv = PRDT::AddBV (src/prdt.cpp:133-205; call site src/gemma.cpp:1698): G (ni_total x ni_total, not changed) is centred
+ * with the weighted CenterMatrix(G, w) (src/mathfunc.cpp:181-201, w = the indicator), y_prdt += G_fo G_oo^+ u_hat with the
+ * eigenvalues of G_oo below 1e-10 zeroed; u_hat[n_bv] on the host, n_bv = the number of training individuals.
+ * prdt_end: y_prdt += pheno_mean, probit != 0 (-predict 2): y_prdt = Phi(y_prdt) (src/gemma.cpp:1715-1722); copies the result to
+ * the host and ends the state.  prdt_add_d is asynchronous on its stream; all adds of one prediction go to ONE stream (they
+ * accumulate into the same y_prdt), and prdt_end synchronises the stream of the last add before it reads the sums.
+ * Host forms of ridge_batch / prdt_add read only the leading ceil(ni_total / 4) bytes (or ni_total doubles) of each row of ld. */
+int gemma_hip_prdt_begin(const int *indicator_idv, size_t ni_total);
+int gemma_hip_prdt_add(int geno_kind, const void *geno, size_t l, size_t ld, const double *effect, int *used_out);
+int gemma_hip_prdt_add_d(int geno_kind, const void *geno_d, size_t l, size_t ld, const double *effect_d, int *used_out_d, void *stream);
+int gemma_hip_prdt_add_bv(const double *G, size_t ni_total, const double *u_hat, size_t n_bv);
+int gemma_hip_prdt_add_bv_d(const double *G_d, size_t ni_total, size_t ldg, const double *u_hat, size_t n_bv, void *stream);
+int gemma_hip_prdt_end(double pheno_mean, int probit, double *y_prdt);
+/* -predict from a kinship alone (a_mode 43) for ONE phenotype: src/gemma.cpp:1732-1820 and :1873-1882 with PRDT::MvnormPrdt
+ * (src/prdt.cpp:448-553).  ni individuals (those with covariates, indicator_cvt); G_full (ni x ni, as ReadFile_kin hands it over,
+ * not centred, not changed); indicator_pheno[ni]: 1 = phenotype observed; W_full (ni x n_cvt, with the intercept); y_full[ni]
+ * (entries of the unobserved individuals are not read).  The kinship of the observed individuals is centred and decomposed,
+ * lambda is the REML estimate (CalcLambda 'R'), vg / ve / beta come from CalcLmmVgVeBeta, H = ve I + vg CenterMatrix(G_full) and
+ *   y_miss = W_miss beta + H_mo H_oo^-1 (y_obs - W_obs beta)        y_miss[number of zeros of indicator_pheno], in order.
+ * H_oo is inverted as a symmetric positive-definite matrix (GEMMA_HIP_ENOTPD where ve = 0 makes it singular; the reference's LU
+ * would carry on).  fit3 (may be NULL) = {vg, ve, lambda}.  More than one phenotype (the Kronecker H_full) is not provided. */
+int gemma_hip_prdt_kin(size_t ni, const double *G_full, const int *indicator_pheno, const double *W_full, size_t n_cvt,
+                       const double *y_full, double l_min, double l_max, size_t n_region, double *y_miss, double *fit3);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1087,5 +1087,134 @@ private:
   }
 };
 
+// ----------------------------------------------------------------------------- genomic prediction (-bslmm 2, -predict 1 / 2)
+// class BSLMM (src/bslmm.h) for its deterministic mode, a_mode 12: RidgeR without the n x p matrix UtX (the effects of a block
+// of SNPs are one matrix-vector product on its packed rows, gemma_hip_ridge_batch), WriteParam and WriteBV in the reference's
+// formats.  Call site: src/gemma.cpp:2959-2960.
+class BSLMM {
+public:
+  std::vector<int> indicator_idv, indicator_snp; // CopyFromParam
+  std::vector<SNPINFO> snpInfo;
+  std::vector<double> alpha, bv; // what RidgeR leaves for the writers
+
+  // BSLMM::RidgeR, src/bslmm.cpp:1194-1221.  geno: the SNP-major rows of the analysed SNPs (GEMMA_GENO_PLINK_2BIT: ld bytes per
+  // row over all indicator_idv.size() individuals; GEMMA_GENO_F64_SNP_MAJOR: ld doubles, NaN = missing), l rows in blocks of
+  // LMM_BATCH_SIZE; ns_test = UtX->size2 of the reference, the SNP count of the whole fit.
+  void RidgeR(const Matrix *U, const Vector *Uty, const Vector *eval, const double lambda, int geno_kind, const void *geno, size_t l,
+              size_t ld, size_t ns_test) {
+    const size_t n = Uty->size;
+    if (U->tda != n) throw std::invalid_argument("BSLMM::RidgeR: U must be dense");
+    bv.assign(n, 0.0);
+    alpha.assign(l, 0.0);
+    enforce_hip(gemma_hip_ridge_setup(n, U->data, eval->data, Uty->data, lambda, ns_test, bv.data()), "BSLMM::RidgeR");
+    try {
+      if (!indicator_idv.empty())
+        enforce_hip(gemma_hip_ridge_set_indicator(indicator_idv.data(), indicator_idv.size()), "BSLMM::RidgeR");
+      const size_t esz = geno_kind == GEMMA_GENO_PLINK_2BIT ? 1 : sizeof(double);
+      for (size_t s0 = 0; s0 < l; s0 += LMM_BATCH_SIZE) {
+        const size_t m = std::min(LMM_BATCH_SIZE, l - s0);
+        enforce_hip(gemma_hip_ridge_batch(geno_kind, static_cast<const char *>(geno) + s0 * ld * esz, m, ld, alpha.data() + s0),
+                    "BSLMM::RidgeR");
+      }
+    } catch (...) {
+      gemma_hip_ridge_finish();
+      throw;
+    }
+    enforce_hip(gemma_hip_ridge_finish(), "BSLMM::RidgeR");
+  }
+
+  // BSLMM::WriteParam(alpha), src/bslmm.cpp:193-235 (`scientific << setprecision(6)` stays set: the zeros print in it too)
+  void WriteParam(const std::string &file_str) const {
+    std::ofstream outfile(file_str.c_str(), std::ofstream::out);
+    if (!outfile) throw std::runtime_error("error writing file: " + file_str);
+    outfile << "chr\trs\tps\tn_miss\talpha\tbeta\tgamma" << std::endl;
+    size_t t = 0;
+    for (size_t i = 0; i < snpInfo.size(); ++i) {
+      if (!indicator_snp.empty() && indicator_snp[i] == 0) continue;
+      outfile << snpInfo[i].chr << "\t" << snpInfo[i].rs_number << "\t" << snpInfo[i].base_position << "\t" << snpInfo[i].n_miss << "\t";
+      outfile << std::scientific << std::setprecision(6) << alpha[t] << "\t";
+      outfile << 0.0 << "\t" << 0.0 << std::endl;
+      t++;
+    }
+  }
+
+  // BSLMM::WriteBV, src/bslmm.cpp:116-140
+  void WriteBV(const std::string &file_str) const {
+    std::ofstream outfile(file_str.c_str(), std::ofstream::out);
+    if (!outfile) throw std::runtime_error("error writing file: " + file_str);
+    size_t t = 0;
+    for (size_t i = 0; i < indicator_idv.size(); ++i) {
+      if (indicator_idv[i] == 0) outfile << "NA" << std::endl;
+      else outfile << std::scientific << std::setprecision(6) << bv[t++] << std::endl;
+    }
+  }
+};
+
+// class PRDT (src/prdt.h) for a_mode 41 / 42, the block of src/gemma.cpp:1660-1729: construct with cPar.indicator_idv
+// (1 = phenotyped), AddBV (:1698) if -ebv and -k were given, Analyze (:1705-1709) per block, Finish (:1711-1722), WriteFiles.
+class PRDT {
+public:
+  std::vector<int> indicator_idv;
+  size_t ns_test = 0;
+  std::vector<size_t> ignored; // rows (counted over all Analyze calls) missing in every individual to be predicted
+
+  explicit PRDT(const std::vector<int> &indicator) : indicator_idv(indicator) {
+    enforce_hip(gemma_hip_prdt_begin(indicator_idv.data(), indicator_idv.size()), "PRDT");
+  }
+  // PRDT::AddBV, src/prdt.cpp:133-205: G over all individuals (left as it is), u_hat over the phenotyped ones
+  void AddBV(const Matrix *G, const Vector *u_hat) {
+    if (G->tda != G->size2) throw std::invalid_argument("PRDT::AddBV: G must be dense");
+    enforce_hip(gemma_hip_prdt_add_bv(G->data, G->size1, u_hat->data, u_hat->size), "PRDT::AddBV");
+  }
+  // PRDT::AnalyzePlink / AnalyzeBimbam, src/prdt.cpp:310-444 / :207-308, on l rows (the SNPs of mapRS2est) with their effects
+  void Analyze(int geno_kind, const void *geno, size_t l, size_t ld, const double *effect) {
+    std::vector<int> used(l);
+    enforce_hip(gemma_hip_prdt_add(geno_kind, geno, l, ld, effect, used.data()), "PRDT::Analyze");
+    for (size_t i = 0; i < l; ++i) {
+      if (used[i]) ns_test++;
+      else ignored.push_back(rows_seen + i);
+    }
+    rows_seen += l;
+  }
+  // + pheno_mean; a_mode 42: gsl_cdf_gaussian_P(y, 1).  Ends the device state.
+  std::vector<double> Finish(double pheno_mean, int a_mode) {
+    size_t nf = 0;
+    for (int k : indicator_idv) nf += (k == 0);
+    std::vector<double> y(nf ? nf : 1);
+    enforce_hip(gemma_hip_prdt_end(pheno_mean, a_mode == 42 ? 1 : 0, y.data()), "PRDT::Finish");
+    y.resize(nf);
+    return y;
+  }
+  // a_mode 43 for one phenotype, src/gemma.cpp:1732-1820 / :1873-1882 around PRDT::MvnormPrdt (src/prdt.cpp:448-553): G_full as
+  // ReadFile_kin read it for the individuals with covariates, indicator_pheno 1 = observed; the missing entries of y_full are
+  // filled in.  Needs no PRDT object.  Returns {vg, ve, lambda}.
+  static std::vector<double> MvnormPrdt(const Matrix *G_full, const std::vector<int> &indicator_pheno, const Matrix *W_full,
+                                        std::vector<double> &y_full, double l_min = 1e-5, double l_max = 1e5, size_t n_region = 10) {
+    const size_t ni = indicator_pheno.size();
+    if (G_full->tda != ni || W_full->tda != W_full->size2 || y_full.size() != ni) throw std::invalid_argument("PRDT::MvnormPrdt: shapes");
+    std::vector<double> y_miss(ni + 1), fit(3);
+    enforce_hip(gemma_hip_prdt_kin(ni, G_full->data, indicator_pheno.data(), W_full->data, W_full->size2, y_full.data(), l_min, l_max,
+                                   n_region, y_miss.data(), fit.data()), "PRDT::MvnormPrdt");
+    size_t t = 0;
+    for (size_t i = 0; i < ni; ++i)
+      if (indicator_pheno[i] == 0) y_full[i] = y_miss[t++];
+    return fit;
+  }
+  // PRDT::WriteFiles(gsl_vector *), src/prdt.cpp:76-102 (default stream precision)
+  void WriteFiles(const std::string &file_str, const std::vector<double> &y_prdt) const { WriteFiles(file_str, indicator_idv, y_prdt); }
+  static void WriteFiles(const std::string &file_str, const std::vector<int> &indicator, const std::vector<double> &y_prdt) {
+    std::ofstream outfile(file_str.c_str(), std::ofstream::out);
+    if (!outfile) throw std::runtime_error("error writing file: " + file_str);
+    size_t ci_test = 0;
+    for (size_t i = 0; i < indicator.size(); i++) {
+      if (indicator[i] == 1) outfile << "NA" << std::endl;
+      else outfile << y_prdt[ci_test++] << std::endl;
+    }
+  }
+
+private:
+  size_t rows_seen = 0;
+};
+
 } // namespace gemma_amd
 #endif
