@@ -402,6 +402,23 @@ extern "C" int gemma_hip_dbg_last_block_missing(int *any) {
   return GEMMA_HIP_OK;
 }
 
+extern "C" int gemma_hip_dbg_last_i8_post(long *short_rows, long *long_rows, int *epilogue) {
+  NEED_INIT();
+  if (!short_rows || !long_rows || !epilogue) return fail(GEMMA_HIP_EINVAL, "dbg_last_i8_post: null");
+  *short_rows = *long_rows = -1;
+  *epilogue = g_ctx.i8_last_epi;
+  if (g_ctx.i8_rowsur_n <= 0 || !g_ctx.i8_rowsur.p) return GEMMA_HIP_OK;
+  std::vector<int> cnt((size_t)g_ctx.i8_rowsur_n);
+  HIPCHK(hipDeviceSynchronize());
+  HIPCHK(hipMemcpy(cnt.data(), g_ctx.i8_rowsur.p, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
+  *short_rows = *long_rows = 0;
+  for (int c : cnt) {
+    if (c > SUR_MAX) *long_rows += 1;
+    else if (c > 0) *short_rows += 1;
+  }
+  return GEMMA_HIP_OK;
+}
+
 extern "C" int gemma_hip_reload_env(void) {
   const int digits0 = i8_digits_for(g_ctx.cfg.n), scale0 = g_ctx.knobs.i8_scale_max;
   g_ctx.knobs.load();

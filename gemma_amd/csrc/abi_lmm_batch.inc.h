@@ -216,7 +216,7 @@ static int lmm_batch_plink_chunked(const void *geno, size_t l, size_t ld, gemma_
   int c = 0;
   for (size_t row0 = 0; row0 < l; row0 += per, ++c) {
     const size_t rows = std::min(per, l - row0), rows_pad = std::min(per, d.lpad - row0);
-    if ((rc = i8_gemm_rows(d, row0, rows_pad, s))) break;
+    if ((rc = i8_gemm_rows(d, row0, rows_pad, s, UtX, ldx, rows))) break;
     if (hipEventRecord(g_ctx.ov_ready[c], s) != hipSuccess || hipStreamWaitEvent(side, g_ctx.ov_ready[c], 0) != hipSuccess) {
       rc = fail(GEMMA_HIP_ERUNTIME, "lmm_batch: %s", hipGetErrorString(hipGetLastError())); // and join below, as on every path
       break;
@@ -292,7 +292,9 @@ extern "C" int gemma_hip_lmm_batch_pipe_d(int kind, const void *geno, size_t l, 
   if (x.post_valid[slot]) HIPCHK(hipStreamWaitEvent(x.P, x.post_done[slot], 0));
   g_ctx.last_utx_path = 1;
   I8Dims d;
-  if ((rc = i8_begin(l, &d, x.P))) return xp_abort(rc);
+  // the separate combine stays here: ONE g_ctx.UtX serves both blocks in flight, and this block's product must not write it while
+  // the block before is read from it on Q
+  if ((rc = i8_begin(l, &d, x.P, false))) return xp_abort(rc);
   {
     ProfScope ps(GEMMA_STAGE_INGEST, x.P);
     IngestI8Args a;

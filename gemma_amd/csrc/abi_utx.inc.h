@@ -9,13 +9,17 @@ struct I8Dims {
   int mdrop; // 1: the 7g6m form -- plane 0 (digit 0 alone) carries the genotype product only
   int complete; // 1: sparse2_meta_kernel flags the block's missing calls (the int after the row counters) and a block without one
                 // takes the genotype product alone (Sparse2Args::anymiss): same planes, same U^T x, bit for bit
+  int epi; // 1: plane 0 is launched last, in the epilogue form of the 16-row records kernel, and writes U^T x itself: i8_gemm_rows
+           // must be given the destination, i8_post_rows runs no digit combine, i8_C holds planes 1 .. nplanes - 1 only
 };
 static const int *i8_anymiss(const I8Dims &d) { return d.complete ? g_ctx.i8_rowsur.as<int>() + d.lpad : nullptr; }
 // GEMMA_HIP_I8_SPARSE: 0 = the mask product on dense MFMAs (i8gemm_packed_kernel_t), 1 = on the 2:4 sparse MFMA with byte-wise
 // genotypes and separate mask words (i8gemm_sparse.hip.h), 2 (default) = sparse MFMA, left factor as 16-byte records of 2-bit
 // genotypes + mask words, 256 x 128 tiles (i8gemm_sparse2.hip.h)
 static int i8_sparse_mode() { return g_ctx.knobs.i8_sparse; }
-static int i8_begin(size_t l, I8Dims *d, hipStream_t s) {
+// allow_epi = false: the caller needs the planes and a separate combine (the two-block pipe: its product must not write the ONE
+// g_ctx.UtX while the block before it is still read from there)
+static int i8_begin(size_t l, I8Dims *d, hipStream_t s, bool allow_epi = true) {
   int rc = i8_prepare_u(s);
   if (rc) return rc;
   d->n = g_ctx.cfg.n; d->ldk = g_ctx.i8_ldk; d->npad = g_ctx.i8_npad;
@@ -27,7 +31,9 @@ static int i8_begin(size_t l, I8Dims *d, hipStream_t s) {
   // the 7g6m form needs plane 0 to be digit 0 alone (odd count, fused planes) and the 16-row records kernel
   d->mdrop = (g_ctx.knobs.i8_mdrop && d->fuse && d->digits == 7 && i8_sparse_mode() == 2 && g_ctx.knobs.i8_rows == 16) ? 1 : 0;
   d->complete = (g_ctx.knobs.i8_complete && i8_sparse_mode() == 2 && g_ctx.knobs.i8_rows == 16) ? 1 : 0;
-  const size_t c_elems = (size_t)d->nplanes * d->mrows * d->npad;
+  // GEMMA_HIP_I8_EPILOGUE=0: every plane to memory and i8_combine_kernel behind the product (rounds 1-6)
+  d->epi = (allow_epi && g_ctx.knobs.i8_epilogue && i8_sparse_mode() == 2 && g_ctx.knobs.i8_rows == 16 && d->nplanes >= 2) ? 1 : 0;
+  const size_t c_elems = (size_t)(d->nplanes - d->epi) * d->mrows * d->npad;
   if (g_ctx.i8_A.reserve(d->lpad * d->ldk) || g_ctx.i8_C.reserve(c_elems * 4) || g_ctx.i8_mean.reserve(l * 8))
     return fail(GEMMA_HIP_ENOMEM, "lmm_batch: int8 product buffers (%zu bytes)", d->lpad * d->ldk + c_elems * 4);
   if (d->lpad != l) HIPCHK(hipMemsetAsync(g_ctx.i8_A.p, 0, d->lpad * d->ldk, s)); // padding rows
@@ -53,6 +59,7 @@ static int i8_meta_build(const I8Dims &d, hipStream_t s) {
                        (long)d.lpad, (long)d.ldk, g_ctx.i8_meta.as<uint4>(), g_ctx.i8_rowsur.as<int>());
   HIPCHK(hipGetLastError());
   g_ctx.i8_flag_at = (mode == 2 && d.complete) ? (long)d.lpad : -1;
+  g_ctx.i8_rowsur_n = (long)d.lpad;
   return GEMMA_HIP_OK;
 }
 
@@ -86,11 +93,16 @@ static int raster_for(int tiles_m, int tiles_n, int rb, hipStream_t s, const int
 
 // rows_pad: padded rows of this piece (a multiple of the tile height; row0 too).  Pieces other than the whole block are taken
 // by the records kernel only (mode 2).
-static int i8_gemm_rows(const I8Dims &d, size_t row0, size_t rows_pad, hipStream_t s) {
+// UtX, ldx, rows (d.epi only): where the rows [row0, row0 + rows) of U^T x go -- the whole destination, as i8_post_rows takes it.
+static int i8_gemm_rows(const I8Dims &d, size_t row0, size_t rows_pad, hipStream_t s, double *UtX = nullptr, size_t ldx = 0,
+                        size_t rows = 0) {
   // GEMMA_HIP_I8_SPARSE=0: the mask product on dense MFMAs (i8gemm_packed_kernel_t); default: on the 2:4 sparse MFMA
   // (i8gemm_sparse2.hip.h) -- rows that lose calls to the 2-of-4 limit are completed in fp64 after the digits are combined
   const int mode = i8_sparse_mode();
   const bool sparse = mode != 0;
+  if (d.epi && (mode != 2 || g_ctx.knobs.i8_rows != 16 || !UtX || rows == 0))
+    return fail(GEMMA_HIP_ESTATE, "lmm_batch: the epilogue form of the int8 product without its destination");
+  g_ctx.i8_last_epi = d.epi;
   ProfScope ps(GEMMA_STAGE_UTX_GEMM, s);
   static bool attr_set = false;
   if (!attr_set) {
@@ -120,12 +132,17 @@ static int i8_gemm_rows(const I8Dims &d, size_t row0, size_t rows_pad, hipStream
                                  hipFuncAttributeMaxDynamicSharedMemorySize, S2_R16_LDS));
       HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(i8gemm_sparse2_r16_g_kernel),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, S2_R16_LDS));
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(i8gemm_sparse2_r16_ep_kernel),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, S2_R16_LDS));
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(i8gemm_sparse2_r16_ep_g_kernel),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, S2_R16_LDS));
       attr3 = true;
     }
     Sparse2Args g2;
     // records: [tile_m][ktile][row % 256][chunk]; planes: G rows at row, M rows at lpad + row
     g2.AM = g_ctx.i8_meta.as<uint4>() + (row0 / S2_BM) * (size_t)g.nk * S2_BM * 4;
-    g2.Bt = g.Bt; g2.C = g.C + row0 * (size_t)g.ldc; g2.ldk = g.ldk; g2.ldc = g.ldc; g2.strideB = g.strideB; g2.strideC = g.strideC;
+    // d.epi: plane 0 is never stored, plane q >= 1 lives at slot q - 1 of i8_C (the kernels address plane q at C + q * strideC)
+    g2.Bt = g.Bt; g2.C = g.C + row0 * (size_t)g.ldc - (d.epi ? g.strideC : 0); g2.ldk = g.ldk; g2.ldc = g.ldc; g2.strideB = g.strideB; g2.strideC = g.strideC;
     g2.m_row0 = g.m_row0;
     g2.tiles_m = (int)(rows_pad / S2_BM); g2.tiles_n = (int)(d.npad / S2_BN);
     g2.nk = g.nk; g2.gm = g.gm; g2.fuse = g.fuse; g2.digits = g.digits;
@@ -149,6 +166,33 @@ static int i8_gemm_rows(const I8Dims &d, size_t row0, size_t rows_pad, hipStream
     if (g_ctx.knobs.i8_rows == 32) {
       hipLaunchKernelGGL(i8gemm_sparse2_kernel, dim3((unsigned)(g2.tiles_m * g2.tiles_n), (unsigned)d.nplanes), dim3(512),
                          S2_NST * S2_STAGE, s, g2);
+    } else if (d.epi) {
+      // planes nplanes - 1 .. 1 as ever, THEN plane 0 in the epilogue form: stream order is the dependency.  7g6m: plane 0 is the
+      // genotype product alone; complete-block form: both launches are the pair of which one returns at once
+      const unsigned wgs = (unsigned)(g2.tiles_m * g2.tiles_n);
+      g2.anymiss = i8_anymiss(d);
+      g2.plane0 = 1;
+      g2.run_if = g2.anymiss ? 1 : 0;
+      hipLaunchKernelGGL(i8gemm_sparse2_r16_kernel, dim3(wgs, (unsigned)d.nplanes - 1u), dim3(512), S2_R16_LDS, s, g2);
+      if (g2.anymiss) {
+        g2.run_if = 2;
+        hipLaunchKernelGGL(i8gemm_sparse2_r16_g_kernel, dim3(wgs, (unsigned)d.nplanes - 1u), dim3(512), S2_R16_LDS, s, g2);
+      }
+      g2.plane0 = 0;
+      g2.UtX = UtX + row0 * ldx; g2.ldx = (long)ldx; g2.l = (long)rows; g2.n = (long)d.n;
+      g2.mean = g_ctx.i8_mean.as<double>() + row0; g2.qinv = g_ctx.i8_qinv.as<double>();
+      g2.m_scale = 1.0; g2.nplanes = d.nplanes;
+      if (d.mdrop) {
+        g2.run_if = 0;
+        hipLaunchKernelGGL(i8gemm_sparse2_r16_ep_g_kernel, dim3(wgs, 1u), dim3(512), S2_R16_LDS, s, g2);
+      } else {
+        g2.run_if = g2.anymiss ? 1 : 0;
+        hipLaunchKernelGGL(i8gemm_sparse2_r16_ep_kernel, dim3(wgs, 1u), dim3(512), S2_R16_LDS, s, g2);
+        if (g2.anymiss) {
+          g2.run_if = 2;
+          hipLaunchKernelGGL(i8gemm_sparse2_r16_ep_g_kernel, dim3(wgs, 1u), dim3(512), S2_R16_LDS, s, g2);
+        }
+      }
     } else {
       // 7g6m: planes 1..3 (digit pairs {2,1} {4,3} {6,5}) with both products, then plane 0 (digit 0) with the genotype product alone
       const unsigned wgs = (unsigned)(g2.tiles_m * g2.tiles_n), first = d.mdrop ? 1u : 0u;
@@ -203,12 +247,19 @@ static int i8_post_rows(size_t l, const I8Dims &d, size_t row0, size_t rows, dou
                        g_ctx.i8_rowsur.as<int>() + row0, (long)rows, sur_cnt, sur_list);
     HIPCHK(hipGetLastError());
   }
-  hipLaunchKernelGGL(i8_combine_kernel, dim3((unsigned)((d.n + 1023) / 1024), (unsigned)std::min<size_t>(rows, 65535)),
-                     dim3(256), 0, s,
-                     g_ctx.i8_C.as<int>() + row0 * d.npad, (long)d.npad, (long)(d.mrows * d.npad), (long)d.lpad,
-                     g_ctx.i8_mean.as<double>() + row0, g_ctx.i8_qinv.as<double>(), (long)rows, (long)d.n, UtX + row0 * ldx, (long)ldx,
-                     1.0, d.fuse, d.digits, sur_cnt, sur_list, g_ctx.U, (long)d.n, d.mdrop, i8_anymiss(d));
-  HIPCHK(hipGetLastError());
+  if (!d.epi) {
+    hipLaunchKernelGGL(i8_combine_kernel, dim3((unsigned)((d.n + 1023) / 1024), (unsigned)std::min<size_t>(rows, 65535)),
+                       dim3(256), 0, s,
+                       g_ctx.i8_C.as<int>() + row0 * d.npad, (long)d.npad, (long)(d.mrows * d.npad), (long)d.lpad,
+                       g_ctx.i8_mean.as<double>() + row0, g_ctx.i8_qinv.as<double>(), (long)rows, (long)d.n, UtX + row0 * ldx, (long)ldx,
+                       1.0, d.fuse, d.digits, sur_cnt, sur_list, g_ctx.U, (long)d.n, d.mdrop, i8_anymiss(d));
+    HIPCHK(hipGetLastError());
+  } else if (sparse) {
+    // the product's epilogue wrote U^T x: only the short lists are left of the combine
+    hipLaunchKernelGGL(i8_surplus_short_kernel, dim3((unsigned)rows), dim3(256), 0, s, sur_cnt, sur_list,
+                       g_ctx.i8_mean.as<double>() + row0, g_ctx.U, (long)d.n, (long)d.n, (long)rows, UtX + row0 * ldx, (long)ldx);
+    HIPCHK(hipGetLastError());
+  }
   if (sparse) {
     hipLaunchKernelGGL(i8_surplus_fix_kernel, dim3((unsigned)rows), dim3(256), 0, s, Arow, (long)d.ldk,
                        g_ctx.i8_rowsur.as<int>() + row0, g_ctx.i8_mean.as<double>() + row0, g_ctx.U, (long)d.n, (long)d.n,
@@ -221,7 +272,7 @@ static int i8_post_rows(size_t l, const I8Dims &d, size_t row0, size_t rows, dou
 // UtX (l x ldx) from the packed left factor in g_ctx.i8_A and the per-SNP means in g_ctx.i8_mean
 static int i8_product(size_t l, const I8Dims &d, double *UtX, size_t ldx, hipStream_t s) {
   int rc = i8_meta_build(d, s);
-  if (!rc) rc = i8_gemm_rows(d, 0, d.lpad, s);
+  if (!rc) rc = i8_gemm_rows(d, 0, d.lpad, s, UtX, ldx, l);
   if (!rc) rc = i8_post_rows(l, d, 0, l, UtX, ldx, s);
   return rc;
 }

@@ -176,6 +176,27 @@ __global__ __launch_bounds__(256) void i8_surplus_list_kernel(const int8_t *__re
   if (lane == 0) sur_cnt[s] = have;
 }
 
+// The short lists applied to a U^T x that is already combined (the records kernel's epilogue form wrote it: no digit combine runs
+// that could add them in passing): rows with 1 .. SUR_MAX dropped calls get UtX[s][k] += mean_s * sum_e U[i_e][k], the sum in list
+// order from 0.0 and one final update -- the operations of i8_combine_kernel on the value it would have held, so the same doubles.
+// One workgroup per row; rows without a list return at once.
+__global__ __launch_bounds__(256) void i8_surplus_short_kernel(const int *__restrict__ sur_cnt, const int *__restrict__ sur_list,
+                                                               const double *__restrict__ mean, const double *__restrict__ U,
+                                                               long ldu, long n, long l, double *__restrict__ UtX, long ldx) {
+  const long s = blockIdx.x;
+  if (s >= l) return;
+  const int cnt = sur_cnt[s];
+  if (cnt <= 0) return;
+  const double mu = mean[s];
+  for (long k = threadIdx.x; k < n; k += 256) {
+    double acc = 0.0;
+    for (int e = 0; e < cnt; ++e) acc += U[(long)sur_list[s * SUR_MAX + e] * ldu + k];
+    double v = UtX[s * ldx + k];
+    v += mu * acc;
+    UtX[s * ldx + k] = v;
+  }
+}
+
 __device__ __forceinline__ i32x4 sp_expand(unsigned bits) {
   i32x4 v;
 #pragma unroll

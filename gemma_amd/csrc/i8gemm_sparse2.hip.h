@@ -54,6 +54,14 @@ struct Sparse2Args {
   // asynchronous pipeline needs no read-back, and neither K loop changes.
   const int *anymiss = nullptr;
   int run_if = 0;
+  // The epilogue instances of the 16-row kernel (i8gemm_sparse2_r16.hip.h, COMBINE) only: the launch is plane 0, planes
+  // nplanes - 1 .. 1 are complete in C, and U^T x = qinv_j * sum_planes (G + mean_s * m_scale * M) goes to UtX (l x ldx, the
+  // first n columns) instead of plane 0 to C.  Every other kernel ignores these.
+  double *UtX = nullptr;
+  long ldx = 0, l = 0, n = 0;
+  const double *mean = nullptr, *qinv = nullptr;
+  double m_scale = 1.0;
+  int nplanes = 0;
 };
 // Tried in round 4 and dropped: one digit fewer for the MASK product (the mask product sums only the row's missing calls, so
 // five digits keep its worst-case error at the level of the six-digit genotype product: -1/18 of the matrix instructions).  The

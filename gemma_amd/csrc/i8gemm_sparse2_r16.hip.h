@@ -51,7 +51,12 @@ constexpr int S2_R16_LDS = S2_R16_NST * S2_STAGE; // dynamic LDS of a launch
 // WITH_S = false: the genotype product alone (round 6, the "7g6m" form: the lowest of seven digits is multiplied with the genotypes
 // only -- its mask term is below the rounding of the other six): no sparse instruction, no mask accumulators, no M rows
 // written.  The same loop otherwise; one source so that the two cannot drift apart.
-template <bool WITH_S>
+//
+// COMBINE = true: the launch of plane 0 (the lowest digit or digit pair), queued on the stream behind the launch of planes
+// nplanes - 1 .. 1.  Its workgroups keep plane 0 in their accumulators, read the other planes of their tile back, run the digit
+// combine (i8gemm.hip.h: i8_combine_kernel -- the same operations in the same order, so the same doubles) and store U^T x
+// themselves: plane 0 never goes to memory and the separate pass over the planes is not run.  The K loop is the same source.
+template <bool WITH_S, bool COMBINE = false>
 __device__ __forceinline__ void s2_r16_body(const Sparse2Args &g) {
   extern __shared__ __attribute__((aligned(1024))) int8_t i8lds[];
   constexpr bool NO_S = !WITH_S || S2_R16_ABL_NO_S;
@@ -301,19 +306,86 @@ __device__ __forceinline__ void s2_r16_body(const Sparse2Args &g) {
   }
 
   asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
-  int *Cg = g.C + (long)plane * g.strideC;
+  if constexpr (COMBINE) {
+    // Entry (i, sb, r) of this lane: row tm * 256 + wave * 32 + 16 i + 4 q + r, column tn * 128 + 16 sb + r16.  A batch is the 8
+    // entries (i, sb = 2 h, 2 h + 1, r); per batch and plane 8 G + 8 M dwords are requested one step ahead of the Horner step that
+    // uses them, so 16 - 32 loads per wavefront are in flight (beside the 128 accumulators there is no room for more: 16 entries a
+    // batch spill).  Every load is issued behind the last K-tile: the counted waits of the loop never see one.
+    const int np = g.nplanes;
+    const bool load_m = !(g.anymiss && __builtin_amdgcn_readfirstlane(*g.anymiss) == 0); // complete block: no M row was written
+    const double w_hi = g.fuse ? 65536.0 : 256.0;          // planes above plane 0 sit two digits apart when fused
+    const double w0 = (g.fuse && !odd) ? 65536.0 : 256.0;  // an odd digit count leaves plane 0 one digit wide
+    // addresses: a uniform base per (plane, row, sub-block) in scalar registers + ONE 32-bit lane offset per array, so that the
+    // epilogue's addresses take no vector registers beside the accumulators (4 q rows + r16 columns: far below 2^32 bytes)
+    const long row_w = (long)tm * S2_BM + wave * 32, col_w = (long)tn * S2_BN;
+    const long row_l = row_w + 4 * q, col_l = col_w + r16; // of this lane: + 16 i + r, + 16 sb
+    const unsigned lo_c = (unsigned)((4 * q * g.ldc + r16) * 4), lo_x = (unsigned)((4 * q * g.ldx + r16) * 8);
+#define EP_AT(T, BASE, LO) (*(T *)((const char *)(BASE) + (LO)))
+#define EP_LOAD(DG, DM, I, H, P)                                                                                  \
+  do {                                                                                                            \
+    const int *cp_ = g.C + (long)(P) * g.strideC + (row_w + 16 * (I)) * g.ldc + col_w + 32 * (H);                 \
+    _Pragma("unroll") for (int k_ = 0; k_ < 2; ++k_) _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_) {           \
+      DG[4 * k_ + r_] = EP_AT(const int, cp_ + r_ * g.ldc + 16 * k_, lo_c);                                       \
+      DM[4 * k_ + r_] = load_m ? EP_AT(const int, cp_ + (g.m_row0 + r_) * g.ldc + 16 * k_, lo_c) : 0;             \
+    }                                                                                                             \
+  } while (0)
+    int cg[8], cm[8];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+    for (int e = 0; e < 8; ++e) cg[e] = cm[e] = 0;
+    if (np > 1) EP_LOAD(cg, cm, 0, 0, np - 1);
 #pragma unroll
-    for (int sb = 0; sb < 8; ++sb) {
-      const long col = (long)tn * S2_BN + 16 * sb + r16;
+    for (int b = 0; b < 8; ++b) {
+      const int i = b >> 2, h = b & 3;
+      double tg[8], tk[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) tg[e] = tk[e] = 0.0;
+      for (int p = np - 1; p >= 1; --p) {
+        int ng[8], nm[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ng[e] = nm[e] = 0;
+        if (p > 1) EP_LOAD(ng, nm, i, h, p - 1);
+        else if (b < 7) EP_LOAD(ng, nm, (b + 1) >> 2, (b + 1) & 3, np - 1);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          tg[e] = tg[e] * w_hi + (double)cg[e];
+          tk[e] = tk[e] * w_hi + (double)cm[e];
+          cg[e] = ng[e];
+          cm[e] = nm[e];
+        }
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const long row = (long)tm * S2_BM + wave * 32 + 16 * i + 4 * q + r;
-        Cg[row * g.ldc + col] = accg[i][sb][r];
-        if (WITH_S) Cg[(g.m_row0 + row) * g.ldc + col] = accm[i][sb][r];
+        const bool row_in = row_l + 16 * i + r < g.l;
+        const double ms = row_in ? EP_AT(const double, g.mean + row_w + 16 * i + r, (unsigned)(32 * q)) * g.m_scale : 0.0;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+          const int e = 4 * k + r, sb = 2 * h + k;
+          const int m0 = WITH_S ? accm[i][sb][r] : 0;
+          tg[e] = tg[e] * w0 + (double)accg[i][sb][r];
+          tk[e] = tk[e] * w0 + (double)m0;
+          if (row_in && col_l + 16 * sb < g.n)
+            EP_AT(double, g.UtX + (row_w + 16 * i + r) * g.ldx + col_w + 16 * sb, lo_x) =
+                fma(ms, tk[e], tg[e]) * EP_AT(const double, g.qinv + col_w + 16 * sb, (unsigned)(8 * r16));
+        }
       }
     }
+#undef EP_AT
+#undef EP_LOAD
+  } else {
+    int *Cg = g.C + (long)plane * g.strideC;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int sb = 0; sb < 8; ++sb) {
+        const long col = (long)tn * S2_BN + 16 * sb + r16;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const long row = (long)tm * S2_BM + wave * 32 + 16 * i + 4 * q + r;
+          Cg[row * g.ldc + col] = accg[i][sb][r];
+          if (WITH_S) Cg[(g.m_row0 + row) * g.ldc + col] = accm[i][sb][r];
+        }
+      }
+  }
 #undef GS_INIT_SRC
 #undef GS_DMA_A
 #undef GS_DMA_B
@@ -331,5 +403,8 @@ __device__ __forceinline__ void s2_r16_body(const Sparse2Args &g) {
 __global__ __launch_bounds__(512, 2) void i8gemm_sparse2_r16_kernel(Sparse2Args g) { s2_r16_body<true>(g); }
 // the genotype product alone (plane 0 of the 7g6m form)
 __global__ __launch_bounds__(512, 2) void i8gemm_sparse2_r16_g_kernel(Sparse2Args g) { s2_r16_body<false>(g); }
+// plane 0 with the digit combine as its epilogue (Sparse2Args::UtX): both products / the genotype product alone
+__global__ __launch_bounds__(512, 2) void i8gemm_sparse2_r16_ep_kernel(Sparse2Args g) { s2_r16_body<true, true>(g); }
+__global__ __launch_bounds__(512, 2) void i8gemm_sparse2_r16_ep_g_kernel(Sparse2Args g) { s2_r16_body<false, true>(g); }
 
 } // namespace gemma_hip

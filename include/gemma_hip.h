@@ -413,6 +413,13 @@ int gemma_hip_dbg_last_utx_kernel(gemma_utx_kernel_info *info);
  * mask product of zeros adds +0.0); GEMMA_HIP_I8_COMPLETE=0 sends every block through both products.  *any: that flag for the last
  * records product of a plain batch (1 / 0; -1: form off or no such product yet).  Synchronises the device. */
 int gemma_hip_dbg_last_block_missing(int *any);
+/* rows of the last sparse int8 product's block whose mask operand dropped calls (groups of four with 3 - 4 missing calls keep two):
+ * *short_rows = rows with 1 .. 16 of them (completed from a short per-row list), *long_rows = rows with more (fp64 fix-up pass);
+ * -1 / -1 when no such product ran.  *epilogue = 1: the last int8 product wrote U^T x from the epilogue of its plane-0 launch
+ * (i8gemm_sparse2_r16_ep_kernel / _ep_g_kernel: the default on the 16-row records kernel) and no digit combine ran; 0: every plane
+ * went to memory and i8_combine_kernel read them back (GEMMA_HIP_I8_EPILOGUE=0, the other kernels, the two-block pipe); -1: none
+ * yet.  Synchronises the device. */
+int gemma_hip_dbg_last_i8_post(long *short_rows, long *long_rows, int *epilogue);
 /* re-read the GEMMA_HIP_* switches of the batch path.  The library reads them once per setup (gemma_hip_init, lmm_setup*, lm_setup,
  * mvlmm_null / mvlmm_set, kin_begin), never per launch; a caller that changes one between two batches of ONE setup calls this. */
 int gemma_hip_reload_env(void);
