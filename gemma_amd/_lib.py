@@ -30,6 +30,8 @@ SYMBOLS = [
     "gemma_hip_ridge_set_indicator", "gemma_hip_ridge_batch", "gemma_hip_ridge_batch_d", "gemma_hip_ridge_finish",
     "gemma_hip_prdt_begin", "gemma_hip_prdt_add", "gemma_hip_prdt_add_d", "gemma_hip_prdt_add_bv", "gemma_hip_prdt_add_bv_d",
     "gemma_hip_prdt_end", "gemma_hip_prdt_kin",
+    "gemma_hip_mqs_begin", "gemma_hip_mqs_add", "gemma_hip_mqs_add_d", "gemma_hip_mqs_end", "gemma_hip_mqs_get",
+    "gemma_hip_mqs_S", "gemma_hip_mqs_S_d", "gemma_hip_mqs_release",
 ]
 COMM_ID_BYTES = 128
 
@@ -209,6 +211,14 @@ def lib():
     L.gemma_hip_prdt_add_bv_d.argtypes = [dp, sz, sz, dp, sz, vp]
     L.gemma_hip_prdt_end.argtypes = [cd, ci, dp]
     L.gemma_hip_prdt_kin.argtypes = [sz, dp, vp, dp, sz, dp, cd, cd, sz, dp, dp]
+    L.gemma_hip_mqs_begin.argtypes = [sz, vp, sz, dp, sz, ci]
+    L.gemma_hip_mqs_add.argtypes = [ci, vp, sz, sz, vp, dp]
+    L.gemma_hip_mqs_add_d.argtypes = [ci, vp, sz, sz, vp, dp, vp]
+    L.gemma_hip_mqs_end.argtypes = [dp, dp]
+    L.gemma_hip_mqs_get.argtypes = [ci, sz, dp]
+    L.gemma_hip_mqs_S.argtypes = [sz, sz, dp, dp, sz, sz, dp]
+    L.gemma_hip_mqs_S_d.argtypes = [sz, sz, dp, dp, sz, sz, dp, vp]
+    L.gemma_hip_mqs_release.argtypes = []
     for s in SYMBOLS:
         getattr(L, s)  # AttributeError if the library does not export what the header declares
     _lib = L

@@ -1100,3 +1100,388 @@ class PRDT:
                 else:
                     f.write(_g6(y_prdt[t]) + "\n")
                     t += 1
+
+
+# ----------------------------------------------------------------------------- MQS summary statistics (-gs, -vc 1 -beta)
+class MQS:
+    """PARAM::CalcS (src/param.cpp:1717-1812) on the device, called where src/gemma.cpp:1977 (-gs) and :2166 (-vc 1 -beta) call it:
+
+        m = MQS(indicator_idv, W, n_vc)        # W: ni_test x n_cvt with the intercept
+        m.AnalyzePlink(bed_rows, cat, weight)  # rows of the SNPs with indicator_snp != 0; cat < 0: skipped; weight None: 1
+        S, Svar, ns = m.Finish()               # prefix.S.txt = S on top of Svar, ns = the per-category SNP counts of size.txt
+        K0 = m.Get(0, 0)                       # the centred + scaled kinship of category 0
+
+    slot=1 fills A beside the K of a finished slot=0 pass (the second CalcS of src/gemma.cpp:2198)."""
+
+    def __init__(self, indicator_idv, W, n_vc):
+        self.indicator_idv = np.ascontiguousarray(indicator_idv, dtype=np.int32)
+        self.n = int((self.indicator_idv != 0).sum())
+        self.W = np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(self.n, -1))
+        self.n_vc = int(n_vc)
+
+    def _analyze(self, geno, geno_kind, cat, weight, slot, batch):
+        lib = L.lib()
+        L.check(lib.gemma_hip_mqs_begin(self.indicator_idv.size, _ptr(self.indicator_idv), self.n_vc, _ptr(self.W), self.W.shape[1],
+                                        int(slot)), "MQS.begin")
+        l = geno.shape[0]
+        if _is_torch(geno):
+            import torch
+            cat_t = torch.as_tensor(np.asarray(cat, dtype=np.int32)).to(geno.device) if not _is_torch(cat) else cat
+            w_t = None
+            if weight is not None:
+                w_t = torch.as_tensor(np.asarray(weight, dtype=np.float64)).to(geno.device) if not _is_torch(weight) else weight
+            for s0 in range(0, l, batch):
+                blk, cb = geno[s0:s0 + batch], cat_t[s0:s0 + batch]
+                wp = C.c_void_p(w_t[s0:s0 + batch].data_ptr()) if w_t is not None else None
+                L.check(lib.gemma_hip_mqs_add_d(geno_kind, C.c_void_p(blk.data_ptr()), blk.shape[0], _tld(geno), C.c_void_p(cb.data_ptr()),
+                                                wp, _stream()), "MQS.add")
+            return
+        cat = np.ascontiguousarray(cat, dtype=np.int32)
+        weight = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64)
+        if cat.shape != (l,) or (weight is not None and weight.shape != (l,)):
+            raise ValueError("cat and weight take one entry per SNP row")
+        geno = np.ascontiguousarray(geno)
+        for s0 in range(0, l, batch):
+            blk, cb = geno[s0:s0 + batch], cat[s0:s0 + batch]
+            wb = None if weight is None else weight[s0:s0 + batch]
+            L.check(lib.gemma_hip_mqs_add(geno_kind, _ptr(blk), blk.shape[0], blk.strides[0] // blk.itemsize, _ptr(cb),
+                                          None if wb is None else _ptr(wb)), "MQS.add")
+
+    def AnalyzePlink(self, bed_rows, cat, weight=None, slot=0, batch=K_BATCH_SIZE):
+        """PlinkKin with weights and categories, src/gemma_io.cpp:2947-3170: bed_rows = .bed rows over all ni_total individuals."""
+        if not _is_torch(bed_rows):
+            bed_rows = np.asarray(bed_rows, dtype=np.uint8)
+        self._analyze(bed_rows, L.GENO_PLINK_2BIT, cat, weight, slot, batch)
+
+    def AnalyzeBimbam(self, G, cat, weight=None, slot=0, batch=K_BATCH_SIZE):
+        """BimbamKinUncentered, src/gemma_io.cpp:2753-2945: G SNP-major over all individuals, NaN = NA."""
+        if not _is_torch(G):
+            G = np.asarray(G, dtype=np.float64)
+        self._analyze(G, L.GENO_F64_SNP_MAJOR, cat, weight, slot, batch)
+
+    def Finish(self):
+        S = np.zeros((2 * self.n_vc, self.n_vc))
+        ns = np.zeros(self.n_vc)
+        L.check(L.lib().gemma_hip_mqs_end(_ptr(S), _ptr(ns)), "MQS.Finish")
+        return S[:self.n_vc].copy(), S[self.n_vc:].copy(), ns
+
+    def Get(self, slot, i):
+        out = np.zeros((self.n, self.n))
+        L.check(L.lib().gemma_hip_mqs_get(int(slot), int(i), _ptr(out)), "MQS.Get")
+        return out
+
+    @staticmethod
+    def S(A, K, n_cvt):
+        """gemma_hip_mqs_S: (S, Svar) from centred + scaled matrices A, K of shape (n_vc, n, n); `A is K` halves the work."""
+        K_c = _np64(np.ascontiguousarray(K), "K")
+        A_c = K_c if A is K else _np64(np.ascontiguousarray(A), "A")
+        n_vc, n = K_c.shape[0], K_c.shape[1]
+        if K_c.shape != (n_vc, n, n) or A_c.shape != K_c.shape:
+            raise ValueError("A and K must be n_vc x n x n")
+        S = np.zeros((2 * n_vc, n_vc))
+        L.check(L.lib().gemma_hip_mqs_S(n, n_vc, _ptr(A_c), _ptr(K_c), n, int(n_cvt), _ptr(S)), "MQS.S")
+        return S[:n_vc].copy(), S[n_vc:].copy()
+
+    @staticmethod
+    def Release():
+        L.check(L.lib().gemma_hip_mqs_release(), "MQS.Release")
+
+
+_HEADER_SETS = dict(  # ReadHeader_io, src/gemma_io.cpp:2367-2427 (the a1 / a0 sets as the reference builds them: one name short each)
+    rs=("rs", "RS", "snp", "SNP", "snps", "SNPS", "snpid", "SNPID", "rsid", "RSID", "MarkerName"),
+    chr=("chr", "CHR"), pos=("ps", "PS", "pos", "POS", "base_position", "BASE_POSITION", "bp", "BP"), cm=("cm", "CM"),
+    a1=("a1", "A1", "allele1", "ALLELE1", "Allele1"),
+    a0=("a0", "A0", "allele0", "ALLELE0", "Allele0", "a2", "A2", "allele2", "ALLELE2", "Allele2"),
+    z=("z", "Z", "z_score", "Z_SCORE", "zscore", "ZSCORE"), beta=("beta", "BETA", "b", "B"),
+    sebeta=("se_beta", "SE_BETA", "se", "SE"), chisq=("chisq", "CHISQ", "chisquare", "CHISQUARE"),
+    p=("p", "P", "pvalue", "PVALUE", "p-value", "P-VALUE"), n=("n", "N", "ntotal", "NTOTAL", "n_total", "N_TOTAL"),
+    nmis=("nmis", "NMIS", "n_mis", "N_MIS", "n_miss", "N_MISS"), nobs=("nobs", "NOBS", "n_obs", "N_OBS"),
+    ncase=("ncase", "NCASE", "n_case", "N_CASE"), ncontrol=("ncontrol", "NCONTROL", "n_control", "N_CONTROL"),
+    ws=("window_size", "WINDOW_SIZE", "ws", "WS"),
+    af=("af", "AF", "maf", "MAF", "f", "F", "allele_freq", "ALLELE_FREQ", "allele_frequency", "ALLELE_FREQUENCY",
+        "Freq.Allele1.HapMapCEU", "FreqAllele1HapMapCEU", "Freq1.Hapmap"),
+    cor=("cor", "COR", "r", "R"))
+_HEADER_ORDER = ("rs", "chr", "pos", "cm", "a1", "a0", "z", "beta", "sebeta", "chisq", "p", "n", "nmis", "nobs", "ncase", "ncontrol",
+                 "ws", "af", "cor")
+
+
+def _tokens(line):
+    return [t for t in line.replace(",", " ").replace("\t", " ").split(" ") if t]
+
+
+def _open_text(path):
+    import gzip
+    with open(path, "rb") as f:
+        gz = f.read(2) == b"\x1f\x8b"
+    return gzip.open(path, "rt") if gz else open(path, "r")
+
+
+def ReadHeader_io(line):
+    """src/gemma_io.cpp:2367-2629: column numbers (1-based, 0 = absent) by header name; every other column is a category."""
+    h = {k + "_col": 0 for k in _HEADER_ORDER}
+    h["cat_cols"] = []
+    coln = 0
+    for tok in _tokens(line):
+        for k in _HEADER_ORDER:
+            if tok in _HEADER_SETS[k]:
+                if h[k + "_col"] == 0:
+                    h[k + "_col"] = coln + 1
+                break
+        else:
+            h["cat_cols"].append(coln + 1)
+        coln += 1
+    h["coln"] = coln
+    return h
+
+
+def _atoi(tok):
+    import re
+    m = re.match(r"\s*[+-]?\d+", tok)
+    return int(m.group(0)) if m else 0
+
+
+def _atof(tok):
+    import re
+    m = re.match(r"\s*[+-]?(\d+\.?\d*([eE][+-]?\d+)?|\.\d+([eE][+-]?\d+)?|nan|inf(inity)?)", tok, re.I)
+    return float(m.group(0)) if m else 0.0
+
+
+def ReadFile_cat(file_cat):
+    """src/gemma_io.cpp:2634-2718 -> (mapRS2cat, n_vc): the first category column holding 1 names the SNP's category; a SNP with
+    0 in every column is in no category."""
+    mapRS2cat = {}
+    with _open_text(file_cat) as f:
+        lines = f.read().splitlines()
+    h = ReadHeader_io(lines[0])
+    named = ("rs", "chr", "pos", "cm", "a1", "a0")
+    n_vc = h["coln"] - sum(1 for k in named if h[k + "_col"] != 0)
+    rs = chr_ = pos = ""
+    for line in lines[1:]:
+        toks = _tokens(line)
+        if not toks:
+            continue
+        i_cat = 0
+        for i in range(h["coln"]):
+            tok = toks[i]
+            if h["rs_col"] == i + 1:
+                rs = tok
+            elif h["chr_col"] == i + 1:
+                chr_ = tok
+            elif h["pos_col"] == i + 1:
+                pos = tok
+            elif i + 1 in (h["cm_col"], h["a1_col"], h["a0_col"]):
+                pass
+            elif _atoi(tok) in (0, 1):
+                if i_cat == 0 and h["rs_col"] == 0:
+                    rs = chr_ + ":" + pos
+                if _atoi(tok) == 1 and rs not in mapRS2cat:
+                    mapRS2cat[rs] = i_cat
+                i_cat += 1
+    return mapRS2cat, n_vc
+
+
+def _norm_ppf(p):
+    """Inverse of the standard normal distribution function (Acklam's rational approximation, one Halley step on erfc)."""
+    import math
+    a = (-3.969683028665376e+01, 2.209460984245205e+02, -2.759285104469687e+02, 1.383577518672690e+02, -3.066479806614716e+01,
+         2.506628277459239e+00)
+    b = (-5.447609879822406e+01, 1.615858368580409e+02, -1.556989798598866e+02, 6.680131188771972e+01, -1.328068155288572e+01)
+    c = (-7.784894002430293e-03, -3.223964580411365e-01, -2.400758277161838e+00, -2.549732539343734e+00, 4.374664141464968e+00,
+         2.938163982698783e+00)
+    d = (7.784695709041462e-03, 3.224671290700398e-01, 2.445134137142996e+00, 3.754408661907416e+00)
+    if p <= 0.0:
+        return -math.inf
+    if p >= 1.0:
+        return math.inf
+    if p < 0.02425:
+        q = math.sqrt(-2 * math.log(p))
+        x = (((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) / ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1)
+    elif p > 1 - 0.02425:
+        q = math.sqrt(-2 * math.log(1 - p))
+        x = -(((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) / ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1)
+    else:
+        q = p - 0.5
+        r = q * q
+        x = (((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * q / \
+            (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1)
+    e = 0.5 * math.erfc(-x / math.sqrt(2)) - p
+    u = e * math.sqrt(2 * math.pi) * math.exp(x * x / 2)
+    return x - u / (1 + x * u / 2)
+
+
+def ReadFile_beta(file_beta, mapRS2cat, mapRS2wA):
+    """The z-score overload of ReadFile_beta, src/gemma_io.cpp:3363-3551 -> dict(vec_cat, vec_ni, vec_weight, vec_z2, ni_total,
+    ns_total, ns_test).  z from z, else beta / se, else chisq, else the p-value (gsl_cdf_chisq_Qinv(p, 1))."""
+    vec_cat, vec_ni, vec_weight, vec_z2 = [], [], [], []
+    ni_total = ns_total = ns_test = 0
+    with _open_text(file_beta) as f:
+        lines = f.read().splitlines()
+    h = ReadHeader_io(lines[0])
+    rs = chr_ = pos = ""
+    for line in lines[1:]:
+        if not line.strip(" \t\r"):
+            continue
+        toks = _tokens(line)
+        z = beta = se = chisq = pv = 0.0
+        n_total = n_mis = n_obs = n_case = n_control = 0
+        for i in range(h["coln"]):
+            tok, k = toks[i], i + 1
+            if h["rs_col"] == k:
+                rs = tok
+            if h["chr_col"] == k:
+                chr_ = tok
+            if h["pos_col"] == k:
+                pos = tok
+            if h["z_col"] == k:
+                z = _atof(tok)
+            if h["beta_col"] == k:
+                beta = _atof(tok)
+            if h["sebeta_col"] == k:
+                se = _atof(tok)
+            if h["chisq_col"] == k:
+                chisq = _atof(tok)
+            if h["p_col"] == k:
+                pv = _atof(tok)
+            if h["n_col"] == k:
+                n_total = _atoi(tok)
+            if h["nmis_col"] == k:
+                n_mis = _atoi(tok)
+            if h["nobs_col"] == k:
+                n_obs = _atoi(tok)
+            if h["ncase_col"] == k:
+                n_case = _atoi(tok)
+            if h["ncontrol_col"] == k:
+                n_control = _atoi(tok)
+        if h["rs_col"] == 0:
+            rs = chr_ + ":" + pos
+        if h["n_col"] == 0:
+            n_total = n_mis + n_obs if (h["nmis_col"] != 0 and h["nobs_col"] != 0) else n_case + n_control
+        if h["z_col"] != 0:
+            z2 = z * z
+        elif h["beta_col"] != 0 and h["sebeta_col"] != 0:
+            z = beta / se if se != 0 else (float("nan") if beta == 0 else float("inf"))
+            z2 = z * z
+        elif h["chisq_col"] != 0:
+            z2 = chisq
+        elif h["p_col"] != 0:
+            z2 = _norm_ppf(pv / 2) ** 2
+        else:
+            z2 = 0.0
+        if (not mapRS2wA or rs in mapRS2wA) and (not mapRS2cat or rs in mapRS2cat) and z2 != 0:
+            vec_cat.append(mapRS2cat[rs] if mapRS2cat else 0)
+            vec_ni.append(n_total)
+            vec_weight.append(mapRS2wA[rs] if mapRS2wA else 1.0)
+            vec_z2.append(z2)
+            ni_total = max(ni_total, n_total)
+            ns_test += 1
+        ns_total += 1
+    return dict(vec_cat=np.array(vec_cat, dtype=np.int64), vec_ni=np.array(vec_ni, dtype=np.int64),
+                vec_weight=np.array(vec_weight, dtype=np.float64), vec_z2=np.array(vec_z2, dtype=np.float64),
+                ni_total=ni_total, ns_total=ns_total, ns_test=ns_test)
+
+
+def ObtainWeight(rs_analysed, setSnps_beta, mapRS2cat):
+    """PARAM::ObtainWeight without -wsnp / -wcat, src/param.cpp:2214-2296: weight 1 for every analysed SNP that is in the beta file
+    (when one is given) and in a category (when categories are given)."""
+    return {rs: 1.0 for rs in rs_analysed if (not setSnps_beta or rs in setSnps_beta) and (not mapRS2cat or rs in mapRS2cat)}
+
+
+def Calcq(n_block, vec_cat, vec_ni, vec_weight, vec_z2, n_vc):
+    """src/gemma_io.cpp:3716-3870 -> (Vq, q, s): q per category and its block-jackknife variance over n_block SNP blocks, with the
+    reference's `!= 0` tests and its halving of the off-diagonals."""
+    n_vc, n_block = int(n_vc), int(n_block)
+    Vq, q, s = np.zeros((n_vc, n_vc)), np.zeros(n_vc), np.zeros(n_vc)
+    vec_q, vec_s, n_snps = [0.0] * n_vc, [0.0] * n_vc, [0.0] * n_vc
+    cats = [int(c) for c in vec_cat]
+    nis = [int(v) for v in vec_ni]
+    ws = [float(v) for v in vec_weight]
+    z2s = [float(v) for v in vec_z2]
+    for cat, n_total, w, z2 in zip(cats, nis, ws, z2s):
+        vec_q[cat] += (z2 - 1.0) * w / float(n_total)
+        vec_s[cat] += w
+        n_snps[cat] += 1
+    for i in range(n_vc):
+        if vec_s[i] != 0:
+            q[i] = vec_q[i] / vec_s[i]
+        s[i] = vec_s[i]
+    for l in range(n_vc):
+        n_snp = int(np.floor(n_snps[l] / n_block))
+        t = b = 0
+        if n_snp == 0:
+            continue
+        mat_q = [[0.0] * n_vc for _ in range(n_block)]
+        mat_s = [[0.0] * n_vc for _ in range(n_block)]
+        for cat, n_total, w, z2 in zip(cats, nis, ws, z2s):
+            mat_q[b][cat] += (z2 - 1.0) * w
+            mat_s[b][cat] += w
+            if cat == l:
+                if b < n_block - 1:
+                    if t < n_snp - 1:
+                        t += 1
+                    else:
+                        b += 1
+                        t = 0
+                else:
+                    t += 1
+        for i in range(n_vc):
+            m = n = 0.0
+            for k in range(n_block):
+                if mat_s[k][i] != 0 and vec_s[i] != mat_s[k][i]:
+                    d = (vec_q[i] - mat_q[k][i]) / (vec_s[i] - mat_s[k][i])
+                    mat_q[k][i] = d
+                    m += d
+                    n += 1
+            if n != 0:
+                m /= n
+            for k in range(n_block):
+                if mat_q[k][i] != 0:
+                    mat_q[k][i] -= m
+        for i in range(n_vc):
+            d = n = 0.0
+            for k in range(n_block):
+                if mat_q[k][l] != 0 and mat_q[k][i] != 0:
+                    d += mat_q[k][l] * mat_q[k][i]
+                    n += 1
+            if n != 0:
+                d /= n
+                d *= n - 1
+            d += Vq[i, l]
+            Vq[i, l] = d
+            if i != l:
+                Vq[l, i] = d
+    for i in range(n_vc):
+        for j in range(i + 1, n_vc):
+            d = Vq[i, j]
+            Vq[i, j] = d / 2
+            Vq[j, i] = d / 2
+    return Vq, q, s
+
+
+def CalcVCss(Vq, S_mat, Svar_mat, q_vec, s_vec, df):
+    """src/vc.cpp:1309-1500 -> dict(pve, se_pve, pve_total, se_pve_total, sigma2, se_sigma2, enrich, se_enrich): the n_vc x n_vc
+    algebra of the estimates; s_vec = the per-category SNP counts CalcS returned, df = ni_study."""
+    S_mat, Svar_mat, Vq = np.asarray(S_mat, dtype=np.float64), np.asarray(Svar_mat, dtype=np.float64), np.asarray(Vq, dtype=np.float64)
+    q_vec, s_vec = np.asarray(q_vec, dtype=np.float64), np.asarray(s_vec, dtype=np.float64)
+    n_vc = S_mat.shape[0]
+    Si = np.linalg.inv(S_mat)
+    pve = Si @ q_vec
+    sigma2 = pve / s_vec
+    qvar = Vq / (df * df)
+    Var = np.zeros((n_vc, n_vc))
+    for i in range(n_vc):
+        for j in range(i, n_vc):
+            Var[i, j] = Var[j, i] = Svar_mat[i, j] * pve[i] * pve[j] + qvar[i, j]
+    Var = (Si @ Var) @ Si
+    se_pve = np.sqrt(np.diag(Var))
+    se_sigma2 = se_pve / s_vec
+    pve_total, se_pve_total = float(pve.sum()), float(np.sqrt(Var.sum()))
+    s_pve, s_snp = pve.sum(), s_vec.sum()
+    enrich = sigma2 * (s_snp / s_pve)
+    T = np.zeros((n_vc, n_vc))
+    for i in range(n_vc):
+        d, d1 = pve[i] / s_pve, s_vec[i]
+        for j in range(n_vc):
+            T[i, j] = ((1 - d) if i == j else (-1 * d)) / d1 * s_snp / s_pve
+    se_enrich = np.sqrt(np.diag((T @ Var) @ T.T))
+    return dict(pve=pve, se_pve=se_pve, pve_total=pve_total, se_pve_total=se_pve_total, sigma2=sigma2, se_sigma2=se_sigma2,
+                enrich=enrich, se_enrich=se_enrich)

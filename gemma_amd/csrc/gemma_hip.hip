@@ -16,6 +16,7 @@
 #include "eigh_tu.h"
 #include "vc_tu.h"
 #include "prdt_tu.h"
+#include "mqs_tu.h"
 #include "ingest.hip.h"
 #include "lm_assoc.hip.h"
 #include "lmm_assoc.hip.h"
@@ -440,6 +441,7 @@ extern "C" void gemma_hip_shutdown(void) {
   eigh_tu_shutdown();
   vc_tu_shutdown();
   prdt_tu_shutdown();
+  mqs_tu_shutdown();
   g_ctx.inited = false;
 }
 
@@ -542,3 +544,4 @@ extern "C" int gemma_hip_dgemm(char ta, char tb, size_t M, size_t N, size_t K, d
 #include "abi_kept_comm.inc.h"
 #include "abi_vc.inc.h"
 #include "abi_prdt.inc.h"
+#include "abi_mqs.inc.h"

@@ -524,6 +524,40 @@ int gemma_hip_prdt_end(double pheno_mean, int probit, double *y_prdt);
 int gemma_hip_prdt_kin(size_t ni, const double *G_full, const int *indicator_pheno, const double *W_full, size_t n_cvt,
                        const double *y_full, double l_min, double l_max, size_t n_region, double *y_miss, double *fit3);
 
+/* ---- MQS summary-statistic variance components: -gs and -vc 1 -beta (Zhou 2017) ---------------------------------------------- */
+/* PARAM::CalcS (src/param.cpp:1717-1812), called where src/gemma.cpp:1977 (-gs) and :2166 / :2198 (-vc 1 / 2 with -beta) call it.
+ * A session computes the weighted, covariate-residualised, category-partitioned kinships of PlinkKin / BimbamKinUncentered with
+ * weights (src/gemma_io.cpp:2947-3170, :2753-2945) over the ANALYSED individuals, then CenterMatrix + ScaleMatrix per category
+ * (src/mathfunc.cpp:147-177, :271-286), compAKtoS (src/param.cpp:1325-1378) and JackknifeAKtoS (:1596-1713).
+ * mqs_begin: indicator_idv over ni_total individuals (NULL: all analysed; n = the number of non-zero entries), n_vc in 1..8
+ * categories, W (n x n_cvt on the host, n_cvt in 1..64, with the intercept; (W^T W)^-1 is formed on the host, EINVAL when
+ * singular).  slot 0 starts over, fills K and makes A = K (CalcS with an empty mapRS2wA); slot 1 needs the finished K of a slot 0
+ * session with the same ni_total, n and n_vc, keeps it and fills A (the second CalcS of src/gemma.cpp:2198).
+ * mqs_add: l SNP-major rows (GEMMA_GENO_PLINK_2BIT, ld bytes per row; GEMMA_GENO_F64_SNP_MAJOR, ld doubles per row, NaN = missing)
+ * of the SNPs with indicator_snp != 0, cat[l] = mapRS2cat of each SNP (0 when n_vc == 1; < 0: the SNP is in no category or has no
+ * weight and is skipped; >= n_vc: EINVAL, nothing of the block is accumulated), weight[l] = mapRS2weight (NULL: 1).  Per SNP: mean
+ * over the called genotypes, impute, centre, x <- x - W (W^T W)^-1 W^T x, var = x^T x / n of that residual; var == 0 (and a SNP
+ * without any called genotype, which poisons the reference's matrix with NaN) drops the SNP, otherwise x sqrt(w / var) joins the
+ * panel of its category and K_c += X_c X_c^T on the fp64 matrix units.  _d: geno, cat and weight on the device, on `stream`, which
+ * is synchronised once per block (the per-category counts come back to the host).
+ * mqs_end: K_c /= ns_c (a category without SNPs stays the zero matrix: its rows and columns of S and Svar are 0, where the
+ * reference divides 0 by 0), centre, scale; ns[n_vc] (may be NULL) = ns_c; S (2 n_vc x n_vc, row-major, may be NULL) = S on top of
+ * Svar, as prefix.S.txt.  A slot 1 session centres and scales A only.
+ * mqs_get: the centred + scaled matrix i_vc of slot 0 (K) or 1 (A; K when A = K), n x n, to the host.
+ * mqs_S / mqs_S_d: S and Svar alone from given centred + scaled matrices: matrix i of A (K) is n x n at A + i n ld with leading
+ * dimension ld; A == K is allowed and halves the work.  The jackknife is evaluated in its exact O(n^2 n_vc^2) form (DESIGN.md
+ * section 13), Svar as the variance around the mean of the n leave-one-out values; with n_cvt == 1 S is the bias-corrected
+ * n d - (n - 1) mean, as in the reference.  All sums run in a fixed order: repeated calls agree bit for bit.
+ * mqs_release returns all device memory of the state. */
+int gemma_hip_mqs_begin(size_t ni_total, const int *indicator_idv, size_t n_vc, const double *W, size_t n_cvt, int slot);
+int gemma_hip_mqs_add(int geno_kind, const void *geno, size_t l, size_t ld, const int *cat, const double *weight);
+int gemma_hip_mqs_add_d(int geno_kind, const void *geno_d, size_t l, size_t ld, const int *cat_d, const double *weight_d, void *stream);
+int gemma_hip_mqs_end(double *S, double *ns);
+int gemma_hip_mqs_get(int slot, size_t i_vc, double *out);
+int gemma_hip_mqs_S(size_t n, size_t n_vc, const double *A, const double *K, size_t ld, size_t n_cvt, double *S);
+int gemma_hip_mqs_S_d(size_t n, size_t n_vc, const double *A_d, const double *K_d, size_t ld, size_t n_cvt, double *S, void *stream);
+int gemma_hip_mqs_release(void);
+
 #ifdef __cplusplus
 }
 #endif

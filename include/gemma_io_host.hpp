@@ -13,6 +13,10 @@
 //                                           src/lmm.cpp:1660-1706)
 //   -eigen / -d -u artefacts              : WriteEigen (src/gemma.cpp:1779-1800 -> PARAM::WriteMatrix / WriteVector),
 //                                           ReadFile_eigenU / ReadFile_eigenD (src/gemma_io.cpp:1323-1416)
+//   MQS summary statistics (-gs, -vc 1 -beta) : ReadHeader_io, ReadFile_cat, ReadFile_snps_header, ReadFile_beta, Calcq
+//                                           (src/gemma_io.cpp:2367-2718, :3363-3551, :3716-3870), ObtainWeight / UpdateSNP
+//                                           (src/param.cpp:2214-2296, :2420-2453), CalcVCss (src/vc.cpp:1309-1500), CalcS
+//                                           (src/param.cpp:1717-1812: the .bed rows go to gemma_hip_mqs_*), WriteMQS
 //
 // Nothing here computes on the host what the reference computes per SNP: counting, imputation and the filters run
 // in gemma_hip_snp_qc; the host side only tokenises text and moves bytes.  Text -> double conversion must give the
@@ -1265,6 +1269,512 @@ struct RunLog {
     return true;
   }
 };
+
+// ---------------------------------------------------------------------------------------------------------------
+// MQS summary statistics: -gs (a_mode 25) and -vc 1 -beta (a_mode 61), src/gemma.cpp:1948-1999, :2102-2230
+// ---------------------------------------------------------------------------------------------------------------
+// class HEADER, src/gemma_io.h: 1-based column numbers, 0 = absent
+struct HEADER {
+  size_t rs_col, chr_col, pos_col, cm_col, a1_col, a0_col, z_col, beta_col, sebeta_col, chisq_col, p_col, n_col, nmis_col, nobs_col,
+      ncase_col, ncontrol_col, af_col, var_col, ws_col, cor_col, coln;
+  std::set<size_t> catc_col, catd_col;
+};
+
+// ReadHeader_io, src/gemma_io.cpp:2367-2629: every spelling of every column name; any other name is a category column
+// (continuous when it ends in _c / _C).  The a1 / a0 sets are built one name short there (INC_ALLELE / DEC_ALLELE never match).
+inline bool ReadHeader_io(const std::string &line, HEADER &header) {
+  struct Names {
+    size_t HEADER::*col;
+    const char *what;
+    std::vector<std::string> names;
+  };
+  static const std::vector<Names> table = {
+      {&HEADER::rs_col, "rs", {"rs", "RS", "snp", "SNP", "snps", "SNPS", "snpid", "SNPID", "rsid", "RSID", "MarkerName"}},
+      {&HEADER::chr_col, "chr", {"chr", "CHR"}},
+      {&HEADER::pos_col, "pos", {"ps", "PS", "pos", "POS", "base_position", "BASE_POSITION", "bp", "BP"}},
+      {&HEADER::cm_col, "cm", {"cm", "CM"}},
+      {&HEADER::a1_col, "allele1", {"a1", "A1", "allele1", "ALLELE1", "Allele1"}},
+      {&HEADER::a0_col, "allele0", {"a0", "A0", "allele0", "ALLELE0", "Allele0", "a2", "A2", "allele2", "ALLELE2", "Allele2"}},
+      {&HEADER::z_col, "z", {"z", "Z", "z_score", "Z_SCORE", "zscore", "ZSCORE"}},
+      {&HEADER::beta_col, "beta", {"beta", "BETA", "b", "B"}},
+      {&HEADER::sebeta_col, "se_beta", {"se_beta", "SE_BETA", "se", "SE"}},
+      {&HEADER::chisq_col, "z", {"chisq", "CHISQ", "chisquare", "CHISQUARE"}},
+      {&HEADER::p_col, "p", {"p", "P", "pvalue", "PVALUE", "p-value", "P-VALUE"}},
+      {&HEADER::n_col, "n_total", {"n", "N", "ntotal", "NTOTAL", "n_total", "N_TOTAL"}},
+      {&HEADER::nmis_col, "n_mis", {"nmis", "NMIS", "n_mis", "N_MIS", "n_miss", "N_MISS"}},
+      {&HEADER::nobs_col, "n_obs", {"nobs", "NOBS", "n_obs", "N_OBS"}},
+      {&HEADER::ncase_col, "n_case", {"ncase", "NCASE", "n_case", "N_CASE"}},
+      {&HEADER::ncontrol_col, "n_control", {"ncontrol", "NCONTROL", "n_control", "N_CONTROL"}},
+      {&HEADER::ws_col, "window_size", {"window_size", "WINDOW_SIZE", "ws", "WS"}},
+      {&HEADER::af_col, "af", {"af", "AF", "maf", "MAF", "f", "F", "allele_freq", "ALLELE_FREQ", "allele_frequency", "ALLELE_FREQUENCY",
+                               "Freq.Allele1.HapMapCEU", "FreqAllele1HapMapCEU", "Freq1.Hapmap"}},
+      {&HEADER::cor_col, "cor", {"cor", "COR", "r", "R"}}};
+  header = HEADER();
+  size_t n_error = 0;
+  const char *p = line.data(), *end = p + line.size(), *b, *e;
+  while (detail::next_token(p, end, b, e)) {
+    const std::string type(b, e);
+    bool named = false;
+    for (size_t k = 0; k < table.size() && !named; ++k)
+      if (std::find(table[k].names.begin(), table[k].names.end(), type) != table[k].names.end()) {
+        named = true;
+        if (header.*(table[k].col) == 0) header.*(table[k].col) = header.coln + 1;
+        else {
+          std::cout << "error! more than two " << table[k].what << " columns in the file." << std::endl;
+          n_error++;
+        }
+      }
+    if (!named) {
+      const std::string cat = type.size() >= 2 ? type.substr(type.size() - 2, 2) : std::string();
+      if (cat == "_c" || cat == "_C") header.catc_col.insert(header.coln + 1);
+      else header.catd_col.insert(header.coln + 1);
+    }
+    header.coln++;
+  }
+  if (header.cor_col != 0 && header.cor_col != header.coln) {
+    std::cout << "error! the cor column should be the last column." << std::endl;
+    n_error++;
+  }
+  if (header.rs_col == 0) {
+    if (header.chr_col != 0 && header.pos_col != 0) std::cout << "missing an rs column. rs id will be replaced by chr:pos" << std::endl;
+    else {
+      std::cout << "error! missing an rs column." << std::endl;
+      n_error++;
+    }
+  }
+  return n_error == 0;
+}
+
+// ReadFile_cat, src/gemma_io.cpp:2634-2718 (`-cat`): the first category column that holds 1 names the SNP's category; a SNP with
+// 0 everywhere is in no category and leaves the analysis
+inline bool ReadFile_cat(const std::string &file_cat, std::map<std::string, size_t> &mapRS2cat, size_t &n_vc) {
+  mapRS2cat.clear();
+  TextFile infile(file_cat);
+  if (!infile.ok()) {
+    std::cout << "error! fail to open category file: " << file_cat << std::endl;
+    return false;
+  }
+  std::string line, rs, chr, pos;
+  HEADER header;
+  infile.getline(line);
+  ReadHeader_io(line, header);
+  n_vc = header.coln;
+  const size_t named[6] = {header.rs_col, header.chr_col, header.pos_col, header.cm_col, header.a1_col, header.a0_col};
+  for (size_t k = 0; k < 6; ++k)
+    if (named[k] != 0) n_vc--;
+  while (infile.getline(line)) {
+    const char *p = line.data(), *end = p + line.size(), *b, *e;
+    size_t i_cat = 0;
+    for (size_t i = 0; i < header.coln; i++) {
+      if (!detail::next_token(p, end, b, e)) throw std::runtime_error("Parsing input file '" + file_cat + "' failed");
+      const std::string tok(b, e);
+      if (header.rs_col == i + 1) rs = tok;
+      else if (header.chr_col == i + 1) chr = tok;
+      else if (header.pos_col == i + 1) pos = tok;
+      else if (header.cm_col == i + 1 || header.a1_col == i + 1 || header.a0_col == i + 1) {
+      } else if (atoi(tok.c_str()) == 1 || atoi(tok.c_str()) == 0) {
+        if (i_cat == 0 && header.rs_col == 0) rs = chr + ":" + pos;
+        if (atoi(tok.c_str()) == 1 && mapRS2cat.count(rs) == 0) mapRS2cat[rs] = i_cat;
+        i_cat++;
+      }
+    }
+  }
+  return true;
+}
+
+// ReadFile_snps_header, src/gemma_io.cpp:181-250: the SNP ids of a file with a header line (rs column, else chr:pos)
+inline bool ReadFile_snps_header(const std::string &file_snps, std::set<std::string> &setSnps) {
+  setSnps.clear();
+  TextFile infile(file_snps);
+  if (!infile.ok()) {
+    std::cout << "error! fail to open snps file: " << file_snps << std::endl;
+    return false;
+  }
+  std::string line, rs, chr, pos;
+  HEADER header;
+  infile.getline(line);
+  ReadHeader_io(line, header);
+  if (header.rs_col == 0 && (header.chr_col == 0 || header.pos_col == 0)) std::cout << "missing rs id in the hearder" << std::endl;
+  while (infile.getline(line)) {
+    const char *p = line.data(), *end = p + line.size(), *b, *e;
+    bool any = false;
+    for (size_t i = 0; i < header.coln && detail::next_token(p, end, b, e); i++) {
+      any = true;
+      if (header.rs_col == i + 1) rs.assign(b, e);
+      if (header.chr_col == i + 1) chr.assign(b, e);
+      if (header.pos_col == i + 1) pos.assign(b, e);
+    }
+    if (!any) continue;
+    if (header.rs_col == 0) rs = chr + ":" + pos;
+    setSnps.insert(rs);
+  }
+  return true;
+}
+
+// gsl_cdf_chisq_Qinv(p, 1) = (Phi^-1(p / 2))^2: Acklam's rational approximation of Phi^-1 and one Halley step on erfc
+inline double chisq1_Qinv(double pvalue) {
+  const double p = pvalue / 2;
+  if (p <= 0.0) return std::numeric_limits<double>::infinity();
+  if (p >= 1.0) return std::numeric_limits<double>::infinity();
+  static const double a[6] = {-3.969683028665376e+01, 2.209460984245205e+02, -2.759285104469687e+02, 1.383577518672690e+02,
+                              -3.066479806614716e+01, 2.506628277459239e+00};
+  static const double b[5] = {-5.447609879822406e+01, 1.615858368580409e+02, -1.556989798598866e+02, 6.680131188771972e+01,
+                              -1.328068155288572e+01};
+  static const double c[6] = {-7.784894002430293e-03, -3.223964580411365e-01, -2.400758277161838e+00, -2.549732539343734e+00,
+                              4.374664141464968e+00, 2.938163982698783e+00};
+  static const double d[4] = {7.784695709041462e-03, 3.224671290700398e-01, 2.445134137142996e+00, 3.754408661907416e+00};
+  double x;
+  if (p < 0.02425) {
+    const double q = std::sqrt(-2 * std::log(p));
+    x = (((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) / ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1);
+  } else if (p > 1 - 0.02425) {
+    const double q = std::sqrt(-2 * std::log(1 - p));
+    x = -(((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) / ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1);
+  } else {
+    const double q = p - 0.5, r = q * q;
+    x = (((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * q /
+        (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1);
+  }
+  const double er = 0.5 * std::erfc(-x / std::sqrt(2.0)) - p;
+  const double u = er * std::sqrt(2 * 3.14159265358979323846) * std::exp(x * x / 2);
+  x = x - u / (1 + x * u / 2);
+  return x * x;
+}
+
+// ReadFile_beta, the z-score overload, src/gemma_io.cpp:3363-3551: z^2 from z, else beta / se, else chisq, else the p-value
+inline void ReadFile_beta(const std::string &file_beta, const std::map<std::string, size_t> &mapRS2cat,
+                          const std::map<std::string, double> &mapRS2wA, std::vector<size_t> &vec_cat, std::vector<size_t> &vec_ni,
+                          std::vector<double> &vec_weight, std::vector<double> &vec_z2, size_t &ni_total, size_t &ns_total,
+                          size_t &ns_test) {
+  vec_cat.clear();
+  vec_ni.clear();
+  vec_weight.clear();
+  vec_z2.clear();
+  ni_total = ns_total = ns_test = 0;
+  TextFile infile(file_beta);
+  if (!infile.ok()) {
+    std::cout << "error! fail to open beta file: " << file_beta << std::endl;
+    return;
+  }
+  std::string line, rs, chr, pos;
+  HEADER header;
+  infile.getline(line);
+  ReadHeader_io(line, header);
+  if (header.n_col == 0) {
+    if ((header.nobs_col == 0 && header.nmis_col == 0) && (header.ncase_col == 0 && header.ncontrol_col == 0))
+      std::cout << "error! missing sample size in the beta file." << std::endl;
+    else std::cout << "total sample size will be replaced by obs/mis sample size." << std::endl;
+  }
+  if (header.z_col == 0 && (header.beta_col == 0 || header.sebeta_col == 0) && header.chisq_col == 0 && header.p_col == 0)
+    std::cout << "error! missing z scores in the beta file." << std::endl;
+  while (infile.getline(line)) {
+    if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+    const char *p = line.data(), *end = p + line.size(), *b, *e;
+    double z = 0, beta = 0, se_beta = 0, chisq = 0, pvalue = 0, zsquare = 0;
+    size_t n_total = 0, n_mis = 0, n_obs = 0, n_case = 0, n_control = 0;
+    for (size_t i = 0; i < header.coln; i++) {
+      if (!detail::next_token(p, end, b, e)) throw std::runtime_error("Parsing input file '" + file_beta + "' failed");
+      const std::string tok(b, e);
+      if (header.rs_col == i + 1) rs = tok;
+      if (header.chr_col == i + 1) chr = tok;
+      if (header.pos_col == i + 1) pos = tok;
+      if (header.z_col == i + 1) z = atof(tok.c_str());
+      if (header.beta_col == i + 1) beta = atof(tok.c_str());
+      if (header.sebeta_col == i + 1) se_beta = atof(tok.c_str());
+      if (header.chisq_col == i + 1) chisq = atof(tok.c_str());
+      if (header.p_col == i + 1) pvalue = atof(tok.c_str());
+      if (header.n_col == i + 1) n_total = (size_t)atoi(tok.c_str());
+      if (header.nmis_col == i + 1) n_mis = (size_t)atoi(tok.c_str());
+      if (header.nobs_col == i + 1) n_obs = (size_t)atoi(tok.c_str());
+      if (header.ncase_col == i + 1) n_case = (size_t)atoi(tok.c_str());
+      if (header.ncontrol_col == i + 1) n_control = (size_t)atoi(tok.c_str());
+    }
+    if (header.rs_col == 0) rs = chr + ":" + pos;
+    if (header.n_col == 0) n_total = (header.nmis_col != 0 && header.nobs_col != 0) ? n_mis + n_obs : n_case + n_control;
+    if (header.z_col != 0) zsquare = z * z;
+    else if (header.beta_col != 0 && header.sebeta_col != 0) {
+      z = beta / se_beta;
+      zsquare = z * z;
+    } else if (header.chisq_col != 0) zsquare = chisq;
+    else if (header.p_col != 0) zsquare = chisq1_Qinv(pvalue);
+    else zsquare = 0;
+    if ((mapRS2wA.size() == 0 || mapRS2wA.count(rs) != 0) && (mapRS2cat.size() == 0 || mapRS2cat.count(rs) != 0) && zsquare != 0) {
+      vec_cat.push_back(mapRS2cat.size() != 0 ? mapRS2cat.at(rs) : 0);
+      vec_ni.push_back(n_total);
+      vec_weight.push_back(mapRS2wA.size() == 0 ? 1 : mapRS2wA.at(rs));
+      vec_z2.push_back(zsquare);
+      ni_total = std::max(ni_total, n_total);
+      ns_test++;
+    }
+    ns_total++;
+  }
+}
+
+// PARAM::ObtainWeight without -wsnp / -wcat, src/param.cpp:2214-2296: weight 1 for every analysed SNP that the beta file (when one
+// is given) and the category file (when one is given) both know
+inline void ObtainWeight(const std::vector<SNPINFO> &snpInfo, const std::vector<int> &indicator_snp,
+                         const std::set<std::string> &setSnps_beta, const std::map<std::string, size_t> &mapRS2cat,
+                         std::map<std::string, double> &mapRS2wK) {
+  mapRS2wK.clear();
+  for (size_t i = 0; i < snpInfo.size(); i++) {
+    if (indicator_snp[i] == 0) continue;
+    const std::string &rs = snpInfo[i].rs_number;
+    if ((setSnps_beta.size() == 0 || setSnps_beta.count(rs) != 0) && (mapRS2cat.size() == 0 || mapRS2cat.count(rs) != 0)) mapRS2wK[rs] = 1;
+  }
+}
+
+// PARAM::UpdateSNP, src/param.cpp:2420-2453
+inline void UpdateSNP(const std::vector<SNPINFO> &snpInfo, std::vector<int> &indicator_snp, const std::map<std::string, double> &mapRS2wA) {
+  for (size_t i = 0; i < snpInfo.size(); i++)
+    if (indicator_snp[i] != 0 && mapRS2wA.count(snpInfo[i].rs_number) == 0) indicator_snp[i] = 0;
+}
+
+// Calcq, src/gemma_io.cpp:3716-3870: q per category and the block jackknife of its variance over n_block blocks of SNPs, with
+// the reference's branch structure (the `!= 0` tests that stand for "this block holds SNPs of the category", the halving of the
+// off-diagonal elements that were added twice)
+inline void Calcq(const size_t n_block, const std::vector<size_t> &vec_cat, const std::vector<size_t> &vec_ni,
+                  const std::vector<double> &vec_weight, const std::vector<double> &vec_z2, Matrix *Vq, Vector *q, Vector *s) {
+  const size_t nq = q->size;
+  for (size_t i = 0; i < Vq->size1; i++)
+    for (size_t j = 0; j < Vq->size2; j++) Vq->data[i * Vq->tda + j] = 0;
+  for (size_t i = 0; i < nq; i++) q->data[i * q->stride] = 0;
+  for (size_t i = 0; i < s->size; i++) s->data[i * s->stride] = 0;
+  std::vector<double> vec_q(nq, 0.0), vec_s(nq, 0.0), n_snps(nq, 0.0);
+  std::vector<std::vector<double>> mat_q(n_block, vec_q), mat_s(n_block, vec_s);
+  for (size_t i = 0; i < vec_cat.size(); i++) {
+    const size_t cat = vec_cat[i];
+    vec_q[cat] += (vec_z2[i] - 1.0) * vec_weight[i] / (double)vec_ni[i];
+    vec_s[cat] += vec_weight[i];
+    n_snps[cat]++;
+  }
+  for (size_t i = 0; i < nq; i++) {
+    if (vec_s[i] != 0) q->data[i * q->stride] = vec_q[i] / vec_s[i];
+    s->data[i * s->stride] = vec_s[i];
+  }
+  size_t t = 0, b = 0, n_snp = 0;
+  double d, m, n;
+  for (size_t l = 0; l < nq; l++) {
+    n_snp = (size_t)std::floor(n_snps[l] / n_block);
+    t = 0;
+    b = 0;
+    if (n_snp == 0) continue;
+    for (size_t i = 0; i < n_block; i++)
+      for (size_t j = 0; j < nq; j++) {
+        mat_q[i][j] = 0;
+        mat_s[i][j] = 0;
+      }
+    for (size_t i = 0; i < vec_cat.size(); i++) {
+      const size_t cat = vec_cat[i];
+      mat_q[b][cat] += (vec_z2[i] - 1.0) * vec_weight[i];
+      mat_s[b][cat] += vec_weight[i];
+      if (cat == l) {
+        if (b < n_block - 1) {
+          if (t < n_snp - 1) t++;
+          else {
+            b++;
+            t = 0;
+          }
+        } else t++;
+      }
+    }
+    for (size_t i = 0; i < nq; i++) {
+      m = 0;
+      n = 0;
+      for (size_t k = 0; k < n_block; k++)
+        if (mat_s[k][i] != 0 && vec_s[i] != mat_s[k][i]) {
+          d = (vec_q[i] - mat_q[k][i]) / (vec_s[i] - mat_s[k][i]);
+          mat_q[k][i] = d;
+          m += d;
+          n++;
+        }
+      if (n != 0) m /= n;
+      for (size_t k = 0; k < n_block; k++)
+        if (mat_q[k][i] != 0) mat_q[k][i] -= m;
+    }
+    for (size_t i = 0; i < nq; i++) {
+      d = 0;
+      n = 0;
+      for (size_t k = 0; k < n_block; k++)
+        if (mat_q[k][l] != 0 && mat_q[k][i] != 0) {
+          d += mat_q[k][l] * mat_q[k][i];
+          n++;
+        }
+      if (n != 0) {
+        d /= n;
+        d *= n - 1;
+      }
+      d += Vq->data[i * Vq->tda + l];
+      Vq->data[i * Vq->tda + l] = d;
+      if (i != l) Vq->data[l * Vq->tda + i] = d;
+    }
+  }
+  for (size_t i = 0; i < nq; i++)
+    for (size_t j = i + 1; j < nq; j++) {
+      d = Vq->data[i * Vq->tda + j];
+      Vq->data[i * Vq->tda + j] = d / 2;
+      Vq->data[j * Vq->tda + i] = d / 2;
+    }
+}
+
+namespace detail {
+// inverse of an m x m matrix by elimination with partial pivoting (LUDecomp + LUInvert on n_vc <= 8); false if singular
+inline bool small_inverse(std::vector<double> &A, size_t m) {
+  std::vector<double> I(m * m, 0.0);
+  for (size_t i = 0; i < m; ++i) I[i * m + i] = 1.0;
+  for (size_t k = 0; k < m; ++k) {
+    size_t p = k;
+    for (size_t i = k + 1; i < m; ++i)
+      if (std::fabs(A[i * m + k]) > std::fabs(A[p * m + k])) p = i;
+    if (A[p * m + k] == 0.0) return false;
+    for (size_t j = 0; j < m && p != k; ++j) {
+      std::swap(A[k * m + j], A[p * m + j]);
+      std::swap(I[k * m + j], I[p * m + j]);
+    }
+    const double d = 1.0 / A[k * m + k];
+    for (size_t j = 0; j < m; ++j) {
+      A[k * m + j] *= d;
+      I[k * m + j] *= d;
+    }
+    for (size_t i = 0; i < m; ++i) {
+      const double f = A[i * m + k];
+      if (i == k || f == 0.0) continue;
+      for (size_t j = 0; j < m; ++j) {
+        A[i * m + j] -= f * A[k * m + j];
+        I[i * m + j] -= f * I[k * m + j];
+      }
+    }
+  }
+  A = I;
+  return true;
+}
+inline std::vector<double> matmul(const std::vector<double> &A, const std::vector<double> &B, size_t m, bool transB = false) {
+  std::vector<double> Cm(m * m, 0.0);
+  for (size_t i = 0; i < m; ++i)
+    for (size_t j = 0; j < m; ++j)
+      for (size_t k = 0; k < m; ++k) Cm[i * m + j] += A[i * m + k] * (transB ? B[j * m + k] : B[k * m + j]);
+  return Cm;
+}
+} // namespace detail
+
+// CalcVCss, src/vc.cpp:1309-1500: pve = S^-1 q, its variance from Svar and Vq / df^2, the per-SNP sigma2 and the enrichment
+inline void CalcVCss(const Matrix *Vq, const Matrix *S_mat, const Matrix *Svar_mat, const Vector *q_vec, const Vector *s_vec,
+                     const double df, std::vector<double> &v_pve, std::vector<double> &v_se_pve, double &pve_total,
+                     double &se_pve_total, std::vector<double> &v_sigma2, std::vector<double> &v_se_sigma2,
+                     std::vector<double> &v_enrich, std::vector<double> &v_se_enrich) {
+  const size_t n_vc = S_mat->size1;
+  std::vector<double> Si(n_vc * n_vc), Var(n_vc * n_vc, 0.0), pve(n_vc, 0.0), sigma2persnp(n_vc), se_pve(n_vc), se_sigma2persnp(n_vc);
+  for (size_t i = 0; i < n_vc; i++)
+    for (size_t j = 0; j < n_vc; j++) Si[i * n_vc + j] = S_mat->data[i * S_mat->tda + j];
+  if (!detail::small_inverse(Si, n_vc)) throw std::runtime_error("CalcVCss: S is singular");
+  auto qv = [&](size_t i) { return q_vec->data[i * q_vec->stride]; };
+  auto sv = [&](size_t i) { return s_vec->data[i * s_vec->stride]; };
+  for (size_t i = 0; i < n_vc; i++) {
+    for (size_t j = 0; j < n_vc; j++) pve[i] += Si[i * n_vc + j] * qv(j);
+    sigma2persnp[i] = pve[i] / sv(i);
+  }
+  for (size_t i = 0; i < n_vc; i++)
+    for (size_t j = i; j < n_vc; j++) {
+      double d = Svar_mat->data[i * Svar_mat->tda + j];
+      d *= pve[i] * pve[j];
+      d += Vq->data[i * Vq->tda + j] * (1.0 / (df * df));
+      Var[i * n_vc + j] = Var[j * n_vc + i] = d;
+    }
+  Var = detail::matmul(detail::matmul(Si, Var, n_vc), Si, n_vc);
+  for (size_t i = 0; i < n_vc; i++) {
+    const double d = std::sqrt(Var[i * n_vc + i]);
+    se_pve[i] = d;
+    se_sigma2persnp[i] = d / sv(i);
+  }
+  pve_total = 0;
+  se_pve_total = 0;
+  for (size_t i = 0; i < n_vc; i++) {
+    pve_total += pve[i];
+    for (size_t j = 0; j < n_vc; j++) se_pve_total += Var[i * n_vc + j];
+  }
+  se_pve_total = std::sqrt(se_pve_total);
+  double s_pve = 0, s_snp = 0;
+  for (size_t i = 0; i < n_vc; i++) {
+    s_pve += pve[i];
+    s_snp += sv(i);
+  }
+  std::vector<double> T(n_vc * n_vc);
+  for (size_t i = 0; i < n_vc; i++) {
+    const double d = pve[i] / s_pve, d1 = sv(i);
+    for (size_t j = 0; j < n_vc; j++) T[i * n_vc + j] = (i == j ? (1 - d) : -1 * d) / d1 * s_snp / s_pve;
+  }
+  const std::vector<double> VarEnrich = detail::matmul(detail::matmul(T, Var, n_vc), T, n_vc, true);
+  v_pve.clear();
+  v_se_pve.clear();
+  v_sigma2.clear();
+  v_se_sigma2.clear();
+  v_enrich.clear();
+  v_se_enrich.clear();
+  for (size_t i = 0; i < n_vc; i++) {
+    v_pve.push_back(pve[i]);
+    v_se_pve.push_back(se_pve[i]);
+    v_sigma2.push_back(sigma2persnp[i]);
+    v_se_sigma2.push_back(se_sigma2persnp[i]);
+    v_enrich.push_back(sigma2persnp[i] * (s_snp / s_pve));
+    v_se_enrich.push_back(std::sqrt(VarEnrich[i * n_vc + i]));
+  }
+}
+
+// PARAM::CalcS on a PLINK set, src/param.cpp:1717-1812 with PlinkKin(..., mapRS2weight, mapRS2cat, ...), src/gemma_io.cpp:2947-3170:
+// the .bed rows of the SNPs with indicator_snp != 0 go to the device in blocks with their category (-1: no category or no
+// weight) and weight; S (2 n_vc x n_vc: S on top of Svar) and ns (n_vc) come back.  slot 0: K, and A = K (empty mapRS2wA);
+// slot 1: A beside the K of the previous call (src/gemma.cpp:2198).
+inline bool CalcS(const std::string &file_bed, const std::vector<int> &indicator_idv, const std::vector<int> &indicator_snp,
+                  const std::map<std::string, double> &mapRS2weight, const std::map<std::string, size_t> &mapRS2cat,
+                  const std::vector<SNPINFO> &snpInfo, const Matrix *W, const size_t n_vc, Matrix *S, Vector *ns, const int slot = 0) {
+  std::ifstream infile(file_bed.c_str(), std::ios::binary);
+  if (!infile) {
+    std::cout << "error reading bed file:" << file_bed << std::endl;
+    return false;
+  }
+  if (W->tda != W->size2 || S->tda != S->size2 || S->size1 != 2 * n_vc || S->size2 != n_vc || ns->size < n_vc || ns->stride != 1)
+    throw HipError(GEMMA_HIP_EINVAL, "CalcS: contiguous W, S (2 n_vc x n_vc) and ns (n_vc)");
+  const size_t ni_total = indicator_idv.size(), n_bit = (ni_total + 3) / 4;
+  std::vector<int> cat;
+  std::vector<double> weight;
+  for (size_t t = 0; t < indicator_snp.size(); ++t) {
+    if (indicator_snp[t] == 0) continue;
+    const std::string &rs = snpInfo[t].rs_number;
+    int c = 0;
+    double w = 1.0;
+    if (mapRS2weight.size() != 0) {
+      if (mapRS2weight.count(rs) == 0) c = -1;
+      else w = mapRS2weight.at(rs);
+    }
+    if (c == 0 && !(n_vc == 1 || mapRS2cat.size() == 0)) c = mapRS2cat.count(rs) != 0 ? (int)mapRS2cat.at(rs) : -1;
+    cat.push_back(c);
+    weight.push_back(w);
+  }
+  enforce_hip(gemma_hip_mqs_begin(ni_total, indicator_idv.data(), n_vc, W->data, W->size2, slot), "CalcS");
+  const size_t B = io_block_rows(K_BATCH_SIZE);
+  std::vector<unsigned char> block(B * n_bit);
+  size_t t_next = 0, done = 0;
+  for (;;) {
+    const size_t l = read_bed_rows(infile, indicator_snp, t_next, n_bit, block.data(), B);
+    if (l == (size_t)-1) {
+      std::cout << "error reading bed file:" << file_bed << " (truncated)" << std::endl;
+      return false;
+    }
+    if (l == 0) break;
+    enforce_hip(gemma_hip_mqs_add(GEMMA_GENO_PLINK_2BIT, block.data(), l, n_bit, cat.data() + done, weight.data() + done), "CalcS");
+    done += l;
+  }
+  enforce_hip(gemma_hip_mqs_end(S->data, ns->data), "CalcS");
+  return true;
+}
+
+// The four files of src/gemma.cpp:2217-2220 (-gs: S and size only), precision(10): prefix.S.txt, .Vq.txt, .q.txt, .size.txt;
+// size = ns per category followed by ni_test.  Vq / q may be NULL.
+inline bool WriteMQS(const std::string &prefix, const Matrix *S, const Matrix *Vq, const Vector *q, const Vector *size) {
+  bool ok = WriteMatrix(S, prefix + ".S.txt") && WriteVector(size, prefix + ".size.txt");
+  if (Vq) ok = ok && WriteMatrix(Vq, prefix + ".Vq.txt");
+  if (q) ok = ok && WriteVector(q, prefix + ".q.txt");
+  return ok;
+}
 
 } // namespace gemma_amd
 #endif
