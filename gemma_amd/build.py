@@ -10,15 +10,15 @@ LIB = os.path.join(HERE, "libgemma_hip.so")
 UNITS = {
     "gemma_hip.hip": ["dgemm_mfma.hip.h", "lmm_grid.hip.h", "i8gemm.hip.h", "i8gemm_sparse.hip.h", "i8gemm_sparse2.hip.h", "i8gemm_sparse2_r16.hip.h", "i8gemm_dense16.hip.h", "lmm_assoc.hip.h",
                       "lmm_search.hip.h", "comm.hip.h", "comm_shm.hpp", "kin_i8.hip.h", "ingest.hip.h", "qc.hip.h", "lm_assoc.hip.h", "mvlmm.hip.h",
-                      "mvlmm_kernels.hip.h", "eigh_tu.h",
+                      "mvlmm_kernels.hip.h", "eigh_tu.h", "tu_common.h",
                       # the stages of the C ABI: textual parts of gemma_hip.hip (one translation unit around g_ctx)
                       "abi_kinship.inc.h", "abi_eigen_qc.inc.h", "abi_lmm_stage.inc.h", "abi_utx.inc.h", "abi_lmm_batch.inc.h",
                       "abi_mvlmm.inc.h", "abi_gxe_lm.inc.h", "abi_kept_comm.inc.h", "abi_vc.inc.h", "vc_tu.h", "abi_prdt.inc.h", "prdt_tu.h",
                       "abi_mqs.inc.h", "mqs_tu.h"],
-    "eigh_tu.hip": ["dgemm_mfma.hip.h", "eigh.hip.h", "eigh2.hip.h", "eigh_tu.h"],  # the eigensolver: its own object file
-    "vc_tu.hip": ["dgemm_mfma.hip.h", "spd_inv.hip.h", "vc.hip.h", "vc_tu.h", "../../include/gemma_vc_hybrid.hpp"],  # -vc 1 / -vc 2
-    "prdt_tu.hip": ["dgemm_mfma.hip.h", "geno_mv.hip.h", "eigh_tu.h", "prdt_tu.h"],  # -bslmm 2 / -predict: genotype matrix-vector passes
-    "mqs_tu.hip": ["dgemm_mfma.hip.h", "mqs.hip.h", "mqs_tu.h"],  # -gs / -vc 1 -beta: MQS kinships, S and its jackknife
+    "eigh_tu.hip": ["dgemm_mfma.hip.h", "eigh.hip.h", "eigh2.hip.h", "eigh_tu.h", "tu_common.h"],  # the eigensolver: its own object file
+    "vc_tu.hip": ["dgemm_mfma.hip.h", "spd_inv.hip.h", "vc.hip.h", "vc_tu.h", "tu_common.h", "host_linalg.h", "../../include/gemma_vc_hybrid.hpp"],  # -vc 1 / -vc 2
+    "prdt_tu.hip": ["dgemm_mfma.hip.h", "geno_mv.hip.h", "dev_common.hip.h", "eigh_tu.h", "prdt_tu.h", "tu_common.h"],  # -bslmm 2 / -predict: genotype matrix-vector passes
+    "mqs_tu.hip": ["dgemm_mfma.hip.h", "mqs.hip.h", "dev_common.hip.h", "mqs_tu.h", "tu_common.h", "host_linalg.h"],  # -gs / -vc 1 -beta: MQS kinships, S and its jackknife
     "mvlmm_kernels.hip": ["mvlmm.hip.h", "mvlmm_kernels.hip.h"],
     "mvlmm_kernels_wide.hip": ["mvlmm.hip.h", "mvlmm_kernels.hip.h"],
     "mvlmm_kernels_rt.hip": ["mvlmm.hip.h", "mvlmm_kernels.hip.h"],  # the run-time (d, c) instance

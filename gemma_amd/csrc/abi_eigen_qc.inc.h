@@ -107,7 +107,7 @@ extern "C" int gemma_hip_eigh_reserve(size_t n) {
   }
   std::string msg;
   const int rc = eigh_reserve_x((long)n, msg);
-  if (rc) return fail(rc, "%s", msg.c_str());
+  if (rc) return ret(rc, msg);
   return GEMMA_HIP_OK;
 }
 

@@ -9,7 +9,7 @@ extern "C" int gemma_hip_mqs_begin(size_t ni_total, const int *indicator_idv, si
   if (slot != 0 && slot != 1) return fail(GEMMA_HIP_EINVAL, "mqs_begin: slot = %d (0: K, 1: A)", slot);
   std::string msg;
   const int rc = mqs_begin_x((long)ni_total, indicator_idv, (int)n_vc, W, (int)n_cvt, slot, msg);
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 static int mqs_add_common(int geno_kind, const void *geno, size_t l, size_t ld, const int *cat, const double *weight, bool device,
@@ -21,7 +21,7 @@ static int mqs_add_common(int geno_kind, const void *geno, size_t l, size_t ld, 
   if (rc) return rc;
   std::string msg;
   rc = mqs_add_x(geno_kind, geno, (long)l, (long)ld, cat, weight, device, S(stream), msg);
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 extern "C" int gemma_hip_mqs_add(int geno_kind, const void *geno, size_t l, size_t ld, const int *cat, const double *weight) {
@@ -40,7 +40,7 @@ extern "C" int gemma_hip_mqs_end(double *S, double *ns) {
   if (!mqs_active_x()) return fail(GEMMA_HIP_EINVAL, "mqs_end before mqs_begin");
   std::string msg;
   const int rc = mqs_end_x(S, ns, msg);
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 extern "C" int gemma_hip_mqs_get(int slot, size_t i_vc, double *out) {
@@ -48,7 +48,7 @@ extern "C" int gemma_hip_mqs_get(int slot, size_t i_vc, double *out) {
   if (!out || i_vc >= 8) return fail(GEMMA_HIP_EINVAL, "mqs_get: matrix %zu", i_vc);
   std::string msg;
   const int rc = mqs_get_x(slot, (int)i_vc, out, msg);
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 static int mqs_S_check(size_t n, size_t n_vc, const double *A, const double *K, size_t ld, size_t n_cvt, const double *S) {
@@ -64,7 +64,7 @@ extern "C" int gemma_hip_mqs_S_d(size_t n, size_t n_vc, const double *A_d, const
   if (rc) return rc;
   std::string msg;
   rc = mqs_S_x((long)n, (int)n_vc, A_d, K_d, (long)ld, (int)n_cvt, S_out, S(stream), msg);
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 extern "C" int gemma_hip_mqs_S(size_t n, size_t n_vc, const double *A, const double *K, size_t ld, size_t n_cvt, double *S) {
@@ -85,7 +85,7 @@ extern "C" int gemma_hip_mqs_S(size_t n, size_t n_vc, const double *A, const dou
   if (e == hipSuccess) rc = mqs_S_x((long)n, (int)n_vc, Ad, Kd, (long)ldd, (int)n_cvt, S, nullptr, msg);
   d.release();
   if (e != hipSuccess) return fail(GEMMA_HIP_ERUNTIME, "mqs_S: %s", hipGetErrorString(e));
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 extern "C" int gemma_hip_mqs_release(void) {

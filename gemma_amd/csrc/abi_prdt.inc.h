@@ -9,7 +9,7 @@ static int ridge_setup_common(size_t n, const double *U, size_t ldu, const doubl
   if (!(lambda >= 0.0)) return fail(GEMMA_HIP_EINVAL, "ridge_setup: lambda = %g", lambda);
   std::string msg;
   const int rc = ridge_setup_x((long)n, U, (long)ldu, eval, ue_device, Uty, uty_device, lambda, (long)ns_test, bv_out, S(stream), msg);
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 extern "C" int gemma_hip_ridge_setup(size_t n, const double *U, const double *eval, const double *Uty, double lambda, size_t ns_test,
@@ -37,7 +37,7 @@ extern "C" int gemma_hip_ridge_set_r(size_t n, const double *r, double scale) {
   if (n == 0 || !r) return fail(GEMMA_HIP_EINVAL, "ridge_set_r: n = %zu", n);
   std::string msg;
   const int rc = ridge_set_r_x((long)n, r, scale, msg);
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 extern "C" int gemma_hip_ridge_set_indicator(const int *indicator_idv, size_t ni_total) {
@@ -48,7 +48,7 @@ extern "C" int gemma_hip_ridge_set_indicator(const int *indicator_idv, size_t ni
     return fail(GEMMA_HIP_EINVAL, "ridge_set_indicator: %zu analysed individuals, ni_total = %zu", ridge_n_x(), ni_total);
   std::string msg;
   const int rc = ridge_set_indicator_x(indicator_idv, (long)ni_total, msg);
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 static int mv_check_block(const char *who, int geno_kind, const void *geno, size_t l, size_t ld, size_t ni_total) {
@@ -68,7 +68,7 @@ static int ridge_batch_common(int geno_kind, const void *geno, size_t l, size_t 
   if (rc) return rc;
   std::string msg;
   rc = ridge_batch_x(geno_kind, geno, (long)l, (long)ld, device, alpha_out, S(stream), msg);
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 extern "C" int gemma_hip_ridge_batch(int geno_kind, const void *geno, size_t l, size_t ld, double *alpha_out) {
@@ -92,7 +92,7 @@ extern "C" int gemma_hip_prdt_begin(const int *indicator_idv, size_t ni_total) {
   if (!indicator_idv || ni_total == 0) return fail(GEMMA_HIP_EINVAL, "prdt_begin: ni_total = %zu", ni_total);
   std::string msg;
   const int rc = prdt_begin_x(indicator_idv, (long)ni_total, msg);
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 static int prdt_add_common(int geno_kind, const void *geno, size_t l, size_t ld, bool device, const double *effect, int *used_out,
@@ -104,7 +104,7 @@ static int prdt_add_common(int geno_kind, const void *geno, size_t l, size_t ld,
   if (rc) return rc;
   std::string msg;
   rc = prdt_add_x(geno_kind, geno, (long)l, (long)ld, device, effect, used_out, S(stream), msg);
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 extern "C" int gemma_hip_prdt_add(int geno_kind, const void *geno, size_t l, size_t ld, const double *effect, int *used_out) {
@@ -128,7 +128,7 @@ static int prdt_add_bv_common(const double *G, size_t ni_total, size_t ldg, bool
   if (n_bv > 65535 || ni_total - n_bv > 65535) return fail(GEMMA_HIP_EINVAL, "prdt_add_bv: more than 65535 individuals in a group");
   std::string msg;
   const int rc = prdt_add_bv_x(G, (long)ni_total, (long)ldg, device, u_hat, S(stream), msg);
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 extern "C" int gemma_hip_prdt_add_bv(const double *G, size_t ni_total, const double *u_hat, size_t n_bv) {
@@ -147,7 +147,7 @@ extern "C" int gemma_hip_prdt_end(double pheno_mean, int probit, double *y_prdt)
   if (!y_prdt && prdt_ni_total_x() > prdt_n_train_x()) return fail(GEMMA_HIP_EINVAL, "prdt_end: y_prdt is NULL");
   std::string msg;
   const int rc = prdt_end_x(pheno_mean, probit, y_prdt, msg);
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 // Mode 43 for one phenotype (src/gemma.cpp:1732-1820, :1873-1882 with PRDT::MvnormPrdt, src/prdt.cpp:448-553): every dense step

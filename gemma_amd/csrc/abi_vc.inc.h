@@ -6,7 +6,7 @@ extern "C" int gemma_hip_spd_inverse_d(double *A_d, size_t n, size_t lda, double
   if (n == 0 || lda < n || !A_d) return fail(GEMMA_HIP_EINVAL, "spd_inverse: n = %zu, lda = %zu", n, lda);
   std::string msg;
   const int rc = spd_inverse_x(A_d, (long)n, (long)lda, logdet, bad_pivot, S(stream), msg);
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 extern "C" int gemma_hip_spd_inverse(double *A, size_t n, size_t lda, double *logdet, long *bad_pivot) {
@@ -24,7 +24,7 @@ extern "C" int gemma_hip_spd_inverse(double *A, size_t n, size_t lda, double *lo
   }
   d.release();
   if (e != hipSuccess) return fail(GEMMA_HIP_ERUNTIME, "spd_inverse: %s", hipGetErrorString(e));
-  return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK;
+  return ret(rc, msg);
 }
 
 static bool g_vc_ready = false;
@@ -42,7 +42,7 @@ static int vc_setup_common(size_t n, size_t n_vc, const double *const *K, size_t
   const int rc = vc_setup_x((long)n, (int)n_vc, K, (long)ldk, device, W, (int)n_cvt, y, msg);
   if (rc) {
     vc_release_x();
-    return fail(rc, "%s", msg.c_str());
+    return ret(rc, msg);
   }
   g_vc_ready = true;
   g_vc_nvc = n_vc;
@@ -79,7 +79,7 @@ extern "C" int gemma_hip_vc_he(double *sigma2, double *se_sigma2, double *pve, d
   VcResult r{};
   std::string msg;
   const int rc = vc_he_x(r, msg);
-  if (rc) return fail(rc, "%s", msg.c_str());
+  if (rc) return ret(rc, msg);
   vc_copy_out(r, sigma2, se_sigma2, pve, se_pve, pve_total, se_pve_total);
   return GEMMA_HIP_OK;
 }
@@ -94,7 +94,7 @@ extern "C" int gemma_hip_vc_reml(int noconstrain, double *sigma2, double *se_sig
   std::vector<double> it;
   std::string msg;
   const int rc = vc_reml_x(noconstrain != 0, r, &it, msg);
-  if (rc) return fail(rc, "%s", msg.c_str());
+  if (rc) return ret(rc, msg);
   vc_copy_out(r, sigma2, se_sigma2, pve, se_pve, pve_total, se_pve_total);
   if (iterations) *iterations = r.iterations;
   if (status) *status = r.status;

@@ -8,27 +8,11 @@
 #include <vector>
 
 #include "../../include/gemma_hip.h"
+#include "tu_common.h"
 #include "eigh.hip.h"
 #include "eigh_tu.h"
 
 namespace gemma_hip {
-
-namespace {
-struct TuBuf { // device scratch of a diagnostic call
-  void *p = nullptr;
-  bool reserve(size_t bytes) {
-    if (hipMalloc(&p, std::max<size_t>(bytes, 8)) != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      return false;
-    }
-    return true;
-  }
-  ~TuBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-} // namespace
 
 int eigh_device_x(double *G, long n, double *U, double *eval, hipStream_t s, std::string &msg, const EighShard *sh) {
   gemm_aux_init();
@@ -81,9 +65,9 @@ size_t eigh_pool_idle_bytes_x() { return eig_pool().idle_bytes(); }
 int dbg_tridiag_x(const double *G, size_t n, double *d, double *e, double *tau, double *VT, std::string &msg) {
   gemm_aux_init();
   EigWs ws;
-  TuBuf dG;
+  ScopedBuf dG; // device copy of G
   const size_t nn = n * n;
-  if (!dG.reserve(nn * 8)) return GEMMA_HIP_ENOMEM;
+  if (dG.reserve(std::max<size_t>(nn * 8, 8))) return GEMMA_HIP_ENOMEM;
   bool ok = ws.get(ws.VT, nn) && ws.get(ws.WT, (size_t)EIG_NB * n) && ws.get(ws.xcol, n + 2) && ws.get(ws.p, n) &&
             ws.get(ws.ab, 2 * EIG_NB) && ws.get(ws.ssbuf, n / TD_ROWS + 2) && ws.get(ws.dotbuf, n / TD_ROWS + 2) &&
             ws.get(ws.wtmp, n) && ws.get(ws.d, n) && ws.get(ws.e, n) && ws.get(ws.tau, n);
@@ -118,9 +102,9 @@ int dbg_eigh2_x(const double *G, size_t n, double *band, double *d, double *e, s
   }
   EigWs ws;
   Eig2Ws w2;
-  TuBuf dG;
+  ScopedBuf dG; // device copy of G
   const size_t nn = n * n;
-  if (!dG.reserve(nn * 8)) return GEMMA_HIP_ENOMEM;
+  if (dG.reserve(nn * 8)) return GEMMA_HIP_ENOMEM;
   bool ok = ws.get(ws.VT, nn) && ws.get(ws.WT, (size_t)EIG_NB * n) && ws.get(ws.d, n) && ws.get(ws.e, n) &&
             ws.get(ws.tau, n) && ws.get(ws.S, (size_t)EIG_NB * EIG_NB) && ws.get(ws.T, (size_t)EIG_NB * EIG_NB) &&
             ws.get(ws.Tall, ((n + EIG_NB - 1) / EIG_NB) * EIG_NB * EIG_NB) && eig2_alloc((long)n, ws, w2);

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/gemma_hip.h"
+#include "tu_common.h"
 #include "dgemm_mfma.hip.h"
 #include "eigh_tu.h"
 #include "vc_tu.h"
@@ -34,29 +35,6 @@
 using namespace gemma_hip;
 
 namespace {
-
-struct DevBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  int reserve(size_t bytes) {
-    if (bytes <= cap) return GEMMA_HIP_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return GEMMA_HIP_ENOMEM;
-    }
-    cap = bytes;
-    return GEMMA_HIP_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T> T *as() { return reinterpret_cast<T *>(p); }
-};
 
 struct StageProf {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;
@@ -279,6 +257,9 @@ int fail(int code, const char *fmt, ...) {
   if (g_ctx.verbose) fprintf(stderr, "gemma_hip: %s\n", buf);
   return code;
 }
+
+// the tail of an entry point around a feature unit: the unit's code, its message into last_error
+int ret(int rc, const std::string &msg) { return rc ? fail(rc, "%s", msg.c_str()) : GEMMA_HIP_OK; }
 
 #define HIPCHK(expr)                                                                        \
   do {                                                                                      \

@@ -22,18 +22,14 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "dev_common.hip.h"
+
 namespace gemma_hip {
 
 constexpr int MV_ROWS = 64;       // X_c^T r, 2-bit: SNP rows per workgroup
 constexpr int MV_CHUNK = 256;     // X_c^T r, 2-bit: words per workgroup (4096 individuals)
 constexpr int MV_PARTS_MAX = 32;  // X~ w: SNP partitions
 constexpr int MV_PART_MIN = 64;   // X~ w: at least this many rows per partition
-
-__device__ __forceinline__ double mv_wsum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // word w of a 2-bit row of `bytes` bytes; bits past the row's end read as 0 (the group masks never select them)
 template <bool ALIGNED>
@@ -101,7 +97,7 @@ __global__ __launch_bounds__(256) void mv_stats_f64_kernel(const double *X, long
     if (k == 1) { sa += x; ca += 1.0; }
     else { sb += x; cb += 1.0; }
   }
-  sa = mv_wsum(sa); ca = mv_wsum(ca); sb = mv_wsum(sb); cb = mv_wsum(cb);
+  sa = wave_sum(sa); ca = wave_sum(ca); sb = wave_sum(sb); cb = wave_sum(cb);
   if (lane == 0) stats[s] = make_double4(sa, ca, sb, cb);
 }
 
@@ -144,7 +140,7 @@ __global__ __launch_bounds__(256) void mv_xtr_plink_kernel(const unsigned char *
     double acc = 0.0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) acc = fma(tr[(v >> (2 * k)) & 3u], rr[k], acc);
-    acc = mv_wsum(acc);
+    acc = wave_sum(acc);
     if (lane == 0) red[t][wave] = acc;
   }
   __syncthreads();
@@ -173,15 +169,15 @@ __global__ __launch_bounds__(256) void mv_xtr_f64_kernel(const double *X, long l
     const double x = row[i];
     if (g.grp[i] == 1 && !isnan(x)) { tot += x; cnt += 1.0; }
   }
-  tot = mv_wsum(tot);
-  cnt = mv_wsum(cnt);
+  tot = wave_sum(tot);
+  cnt = wave_sum(cnt);
   const double mean = tot / cnt;
   double acc = 0.0;
   for (long i = lane; i < g.ni_total; i += 64) {
     const double x = row[i];
     if (g.grp[i] == 1 && !isnan(x)) acc = fma(x - mean, r_full[i], acc);
   }
-  acc = mv_wsum(acc);
+  acc = wave_sum(acc);
   if (lane == 0) alpha[s] = scale * acc;
 }
 

@@ -16,6 +16,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "dev_common.hip.h"
+
 namespace gemma_hip {
 
 constexpr int MQS_THREADS = 256;
@@ -23,15 +25,9 @@ constexpr int MQS_SCAN_THREADS = 1024;
 constexpr int MQS_CMAX = 64;  // covariates, as everywhere in the library
 constexpr int MQS_VCMAX = 8;  // categories
 
-__device__ __forceinline__ double mqs_wsum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // sum over the 256 threads of a workgroup, the same value in every thread; red: 4 doubles of LDS
 __device__ __forceinline__ double mqs_bsum(double v, double *red) {
-  v = mqs_wsum(v);
+  v = wave_sum(v);
   __syncthreads(); // red may still be read from the previous sum
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -105,7 +101,7 @@ __global__ __launch_bounds__(MQS_THREADS) void mqs_ingest_kernel(MqsIngest g) {
         if (a0 + a < c) acc[a] += g.Wt[(long)(a0 + a) * g.ldx + i] * xi;
     }
 #pragma unroll
-    for (int a = 0; a < 8; ++a) acc[a] = mqs_wsum(acc[a]);
+    for (int a = 0; a < 8; ++a) acc[a] = wave_sum(acc[a]);
     __syncthreads();
     if (lane == 0) {
 #pragma unroll
@@ -214,7 +210,7 @@ __global__ __launch_bounds__(MQS_THREADS) void mqs_rowstat_kernel(const double *
   const double *row = M + r * ld;
   double s = 0.0;
   for (long j = lane; j < n; j += 64) s += row[j];
-  s = mqs_wsum(s);
+  s = wave_sum(s);
   if (lane == 0) {
     rs[r] = s;
     dg[r] = row[r];
@@ -226,7 +222,7 @@ __global__ __launch_bounds__(1024) void mqs_total_kernel(const double *v, long n
   __shared__ double part[16];
   double s = 0.0;
   for (long i = threadIdx.x; i < n; i += 1024) s += v[i];
-  s = mqs_wsum(s);
+  s = wave_sum(s);
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -295,9 +291,9 @@ __global__ __launch_bounds__(MQS_THREADS) void mqs_pair_kernel(const double *A, 
       v += k[j] * sA[j];
     }
   }
-  h = mqs_wsum(h);
-  u = mqs_wsum(u);
-  v = mqs_wsum(v);
+  h = wave_sum(h);
+  u = wave_sum(u);
+  v = wave_sum(v);
   if (lane == 0) {
     huv[t] = h;
     huv[n + t] = u;

@@ -13,6 +13,8 @@
 #include <vector>
 
 #include "../../include/gemma_hip.h"
+#include "tu_common.h"
+#include "host_linalg.h"
 #include "dgemm_mfma.hip.h"
 #include "mqs.hip.h"
 #include "mqs_tu.h"
@@ -25,85 +27,21 @@ struct MqsState {
   bool active = false, haveK = false, haveA = false;
   long n = 0, ni_total = 0, ld = 0, cap = 0;
   int nvc = 0, c = 0, slot = 0;
-  double *K = nullptr, *A = nullptr; // n_vc matrices of n x ld each; A == nullptr: A is K
-  int *idx = nullptr;
-  double *Wt = nullptr, *Wi = nullptr;
-  double *X = nullptr, *P = nullptr, *var = nullptr, *w_d = nullptr;
-  int *pos = nullptr, *cnt = nullptr, *cat_d = nullptr; // cnt: n_vc counts, then the bad-category flag
-  void *stage = nullptr;
-  size_t stage_cap = 0;
+  DevBuf K, A;                // n_vc matrices of n x ld doubles each; !haveA: A is K
+  DevBuf idx;                 // ints
+  DevBuf Wt, Wi;              // doubles
+  DevBuf X, P, var, w_d;      // doubles
+  DevBuf pos, cnt, cat_d;     // ints; cnt: n_vc counts, then the bad-category flag
+  DevBuf stage;               // host blocks land here
   long ns[MQS_VCMAX] = {};
   hipStream_t last = nullptr;
 } g_mqs;
 
-int herr(hipError_t e, const char *what, std::string &msg) {
-  msg = std::string(what) + ": " + hipGetErrorString(e);
-  return GEMMA_HIP_ERUNTIME;
-}
-#define MQCHK(expr)                                    \
-  do {                                                 \
-    hipError_t e_ = (expr);                            \
-    if (e_ != hipSuccess) return herr(e_, #expr, msg); \
-  } while (0)
-
-template <class T> int dalloc(T **p, size_t count, std::string &msg) {
-  if (hipMalloc((void **)p, std::max<size_t>(count, 2) * sizeof(T)) != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    msg = "mqs: cannot allocate " + std::to_string(count * sizeof(T)) + " bytes of device memory";
-    return GEMMA_HIP_ENOMEM;
-  }
-  return GEMMA_HIP_OK;
-}
-template <class T> void dfree(T *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
+// the buffers of one block, sized for g_mqs.cap SNPs
 void free_block_buffers() {
-  dfree(g_mqs.X);
-  dfree(g_mqs.P);
-  dfree(g_mqs.var);
-  dfree(g_mqs.w_d);
-  dfree(g_mqs.pos);
-  dfree(g_mqs.cat_d);
-  if (g_mqs.stage) (void)hipFree(g_mqs.stage);
-  g_mqs.stage = nullptr;
-  g_mqs.stage_cap = 0;
+  g_mqs.X.release(); g_mqs.P.release(); g_mqs.var.release(); g_mqs.w_d.release(); g_mqs.pos.release(); g_mqs.cat_d.release();
+  g_mqs.stage.release();
   g_mqs.cap = 0;
-}
-
-// Gauss-Jordan inverse with partial pivoting of the c x c matrix W^T W (LUDecomp + LUInvert, src/gemma_io.cpp:2977-2980)
-bool small_inverse(std::vector<double> &A, int m) {
-  std::vector<double> I((size_t)m * m, 0.0);
-  for (int i = 0; i < m; ++i) I[i * m + i] = 1.0;
-  for (int k = 0; k < m; ++k) {
-    int p = k;
-    for (int i = k + 1; i < m; ++i)
-      if (std::fabs(A[i * m + k]) > std::fabs(A[p * m + k])) p = i;
-    if (!(std::fabs(A[p * m + k]) > 0.0)) return false;
-    if (p != k)
-      for (int j = 0; j < m; ++j) {
-        std::swap(A[k * m + j], A[p * m + j]);
-        std::swap(I[k * m + j], I[p * m + j]);
-      }
-    const double d = 1.0 / A[k * m + k];
-    for (int j = 0; j < m; ++j) {
-      A[k * m + j] *= d;
-      I[k * m + j] *= d;
-    }
-    for (int i = 0; i < m; ++i) {
-      if (i == k) continue;
-      const double f = A[i * m + k];
-      if (f == 0.0) continue;
-      for (int j = 0; j < m; ++j) {
-        A[i * m + j] -= f * A[k * m + j];
-        I[i * m + j] -= f * I[k * m + j];
-      }
-    }
-  }
-  A = I;
-  return true;
 }
 
 // compAKtoS + JackknifeAKtoS for one ordered pair from the O(n) quantities of the passes.  All sums in
@@ -153,12 +91,7 @@ void finish_pair(long n, int c, const double *sA, const double *dA, const double
 
 void mqs_release_x() {
   free_block_buffers();
-  dfree(g_mqs.K);
-  dfree(g_mqs.A);
-  dfree(g_mqs.idx);
-  dfree(g_mqs.Wt);
-  dfree(g_mqs.Wi);
-  dfree(g_mqs.cnt);
+  g_mqs.K.release(); g_mqs.A.release(); g_mqs.idx.release(); g_mqs.Wt.release(); g_mqs.Wi.release(); g_mqs.cnt.release();
   g_mqs.active = g_mqs.haveK = g_mqs.haveA = false;
   g_mqs.n = g_mqs.ni_total = g_mqs.ld = 0;
   g_mqs.nvc = g_mqs.c = 0;
@@ -197,16 +130,13 @@ int mqs_begin_x(long ni_total, const int *indicator, int n_vc, const double *W, 
   for (long i = 0; i < n; ++i)
     for (int a = 0; a < c; ++a)
       for (int e = 0; e < c; ++e) WtW[a * c + e] += W[i * c + a] * W[i * c + e];
-  if (!small_inverse(WtW, c)) {
+  if (small_inverse(WtW, c) != SMALL_INVERSE_OK) { // a NaN pivot is refused too
     msg = "mqs_begin: W^T W is singular";
     return GEMMA_HIP_EINVAL;
   }
   if (slot == 0) mqs_release_x();
   else {
-    dfree(g_mqs.A);
-    dfree(g_mqs.idx);
-    dfree(g_mqs.Wt);
-    dfree(g_mqs.Wi);
+    g_mqs.A.release(); g_mqs.idx.release(); g_mqs.Wt.release(); g_mqs.Wi.release();
     g_mqs.haveA = false;
   }
   gemm_aux_init();
@@ -220,21 +150,22 @@ int mqs_begin_x(long ni_total, const int *indicator, int n_vc, const double *W, 
   g_mqs.last = nullptr;
   for (long &v : g_mqs.ns) v = 0;
   int rc;
-  double **M = slot == 0 ? &g_mqs.K : &g_mqs.A;
+  DevBuf &M = slot == 0 ? g_mqs.K : g_mqs.A;
   const size_t total = (size_t)n_vc * n * ld;
-  if ((rc = dalloc(M, total, msg)) || (rc = dalloc(&g_mqs.idx, (size_t)n, msg)) || (rc = dalloc(&g_mqs.Wt, (size_t)c * ld, msg)) ||
-      (rc = dalloc(&g_mqs.Wi, (size_t)c * c, msg)) || (!g_mqs.cnt && (rc = dalloc(&g_mqs.cnt, (size_t)MQS_VCMAX + 1, msg)))) {
+  if ((rc = M.reserve(total * 8, "mqs", msg)) || (rc = g_mqs.idx.reserve((size_t)n * sizeof(int), "mqs", msg)) ||
+      (rc = g_mqs.Wt.reserve((size_t)c * ld * 8, "mqs", msg)) || (rc = g_mqs.Wi.reserve((size_t)c * c * 8, "mqs", msg)) ||
+      (rc = g_mqs.cnt.reserve((size_t)(MQS_VCMAX + 1) * sizeof(int), "mqs", msg))) {
     if (slot == 0) mqs_release_x();
-    else dfree(g_mqs.A);
+    else g_mqs.A.release();
     return rc;
   }
-  MQCHK(hipMemset(*M, 0, total * 8));
+  TU_CHK(hipMemset(M.p, 0, total * 8));
   std::vector<double> Wt((size_t)c * ld, 0.0);
   for (long i = 0; i < n; ++i)
     for (int a = 0; a < c; ++a) Wt[(size_t)a * ld + i] = W[i * c + a];
-  MQCHK(hipMemcpy(g_mqs.idx, idx.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-  MQCHK(hipMemcpy(g_mqs.Wt, Wt.data(), Wt.size() * 8, hipMemcpyHostToDevice));
-  MQCHK(hipMemcpy(g_mqs.Wi, WtW.data(), WtW.size() * 8, hipMemcpyHostToDevice));
+  TU_CHK(hipMemcpy(g_mqs.idx.p, idx.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  TU_CHK(hipMemcpy(g_mqs.Wt.p, Wt.data(), Wt.size() * 8, hipMemcpyHostToDevice));
+  TU_CHK(hipMemcpy(g_mqs.Wi.p, WtW.data(), WtW.size() * 8, hipMemcpyHostToDevice));
   if (slot == 0) g_mqs.haveK = false;
   g_mqs.active = true;
   return GEMMA_HIP_OK;
@@ -247,11 +178,11 @@ int mqs_add_x(int geno_kind, const void *geno, long l, long ld_src, const int *c
   const bool plink = geno_kind == GEMMA_GENO_PLINK_2BIT;
   int rc;
   if (l > g_mqs.cap) {
-    MQCHK(hipDeviceSynchronize());
+    TU_CHK(hipDeviceSynchronize());
     free_block_buffers();
-    if ((rc = dalloc(&g_mqs.X, (size_t)l * ld, msg)) || (rc = dalloc(&g_mqs.P, (size_t)l * ld, msg)) ||
-        (rc = dalloc(&g_mqs.var, (size_t)l, msg)) || (rc = dalloc(&g_mqs.w_d, (size_t)l, msg)) ||
-        (rc = dalloc(&g_mqs.pos, (size_t)l, msg)) || (rc = dalloc(&g_mqs.cat_d, (size_t)l, msg))) {
+    if ((rc = g_mqs.X.reserve((size_t)l * ld * 8, "mqs", msg)) || (rc = g_mqs.P.reserve((size_t)l * ld * 8, "mqs", msg)) ||
+        (rc = g_mqs.var.reserve((size_t)l * 8, "mqs", msg)) || (rc = g_mqs.w_d.reserve((size_t)l * 8, "mqs", msg)) ||
+        (rc = g_mqs.pos.reserve((size_t)l * sizeof(int), "mqs", msg)) || (rc = g_mqs.cat_d.reserve((size_t)l * sizeof(int), "mqs", msg))) {
       free_block_buffers();
       return rc;
     }
@@ -267,63 +198,49 @@ int mqs_add_x(int geno_kind, const void *geno, long l, long ld_src, const int *c
         return GEMMA_HIP_EINVAL;
       }
     const size_t row = plink ? (size_t)((g_mqs.ni_total + 3) / 4) : (size_t)g_mqs.ni_total * 8, pitch = (size_t)ld_src * (plink ? 1 : 8);
-    const size_t bytes = (size_t)l * row;
-    if (bytes > g_mqs.stage_cap) {
-      MQCHK(hipDeviceSynchronize());
-      if (g_mqs.stage) (void)hipFree(g_mqs.stage);
-      g_mqs.stage = nullptr;
-      g_mqs.stage_cap = 0;
-      if (hipMalloc(&g_mqs.stage, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        msg = "mqs_add: cannot allocate " + std::to_string(bytes) + " bytes of device memory";
-        return GEMMA_HIP_ENOMEM;
-      }
-      g_mqs.stage_cap = bytes;
-    }
-    MQCHK(hipMemcpy2DAsync(g_mqs.stage, row, geno, pitch, row, (size_t)l, hipMemcpyHostToDevice, s));
-    MQCHK(hipMemcpyAsync(g_mqs.cat_d, cat, (size_t)l * sizeof(int), hipMemcpyHostToDevice, s));
-    if (weight) MQCHK(hipMemcpyAsync(g_mqs.w_d, weight, (size_t)l * 8, hipMemcpyHostToDevice, s));
-    src = g_mqs.stage;
-    ld_src = plink ? (long)row : g_mqs.ni_total;
-    cat_d = g_mqs.cat_d;
-    w_d = weight ? g_mqs.w_d : nullptr;
+    if ((size_t)l * row > g_mqs.stage.cap) TU_CHK(hipDeviceSynchronize()); // an earlier add may still read the buffer that grows
+    if ((rc = stage_rows(g_mqs.stage, geno, (size_t)l, row, pitch, plink ? 1 : 8, s, "mqs_add", msg, src, ld_src))) return rc;
+    TU_CHK(hipMemcpyAsync(g_mqs.cat_d.p, cat, (size_t)l * sizeof(int), hipMemcpyHostToDevice, s));
+    if (weight) TU_CHK(hipMemcpyAsync(g_mqs.w_d.p, weight, (size_t)l * 8, hipMemcpyHostToDevice, s));
+    cat_d = g_mqs.cat_d.as<int>();
+    w_d = weight ? g_mqs.w_d.as<double>() : nullptr;
   }
+  double *const X = g_mqs.X.as<double>(), *const P = g_mqs.P.as<double>(), *const var = g_mqs.var.as<double>();
+  int *const pos = g_mqs.pos.as<int>(), *const cnt_d = g_mqs.cnt.as<int>();
   MqsIngest g;
   g.src = src;
   g.ld = ld_src;
   g.l = l;
-  g.idx = g_mqs.idx;
+  g.idx = g_mqs.idx.as<int>();
   g.n = (int)n;
   g.c = g_mqs.c;
-  g.Wt = g_mqs.Wt;
-  g.Wi = g_mqs.Wi;
-  g.X = g_mqs.X;
+  g.Wt = g_mqs.Wt.as<double>();
+  g.Wi = g_mqs.Wi.as<double>();
+  g.X = X;
   g.ldx = ld;
-  g.var = g_mqs.var;
+  g.var = var;
   if (plink) hipLaunchKernelGGL(mqs_ingest_kernel<true>, dim3((unsigned)l), dim3(MQS_THREADS), 0, s, g);
   else hipLaunchKernelGGL(mqs_ingest_kernel<false>, dim3((unsigned)l), dim3(MQS_THREADS), 0, s, g);
-  MQCHK(hipGetLastError());
-  MQCHK(hipMemsetAsync(g_mqs.cnt, 0, (MQS_VCMAX + 1) * sizeof(int), s));
-  hipLaunchKernelGGL(mqs_scan_kernel, dim3((unsigned)nvc), dim3(MQS_SCAN_THREADS), 0, s, cat_d, g_mqs.var, l, nvc, g_mqs.pos, g_mqs.cnt,
-                     g_mqs.cnt + MQS_VCMAX);
-  MQCHK(hipGetLastError());
+  TU_CHK(hipGetLastError());
+  TU_CHK(hipMemsetAsync(cnt_d, 0, (MQS_VCMAX + 1) * sizeof(int), s));
+  hipLaunchKernelGGL(mqs_scan_kernel, dim3((unsigned)nvc), dim3(MQS_SCAN_THREADS), 0, s, cat_d, var, l, nvc, pos, cnt_d, cnt_d + MQS_VCMAX);
+  TU_CHK(hipGetLastError());
   int cnt[MQS_VCMAX + 1];
-  MQCHK(hipMemcpyAsync(cnt, g_mqs.cnt, sizeof cnt, hipMemcpyDeviceToHost, s));
-  MQCHK(hipStreamSynchronize(s));
+  TU_CHK(hipMemcpyAsync(cnt, cnt_d, sizeof cnt, hipMemcpyDeviceToHost, s));
+  TU_CHK(hipStreamSynchronize(s));
   if (cnt[MQS_VCMAX]) { // nothing was accumulated from this block
     msg = "mqs_add: a category index of the block is >= n_vc = " + std::to_string(nvc);
     return GEMMA_HIP_EINVAL;
   }
-  hipLaunchKernelGGL(mqs_compact_kernel, dim3((unsigned)l), dim3(MQS_THREADS), 0, s, g_mqs.X, ld, l, cat_d, g_mqs.var, w_d, nvc,
-                     g_mqs.pos, g_mqs.cnt, g_mqs.P);
-  MQCHK(hipGetLastError());
-  double *M = g_mqs.slot == 0 ? g_mqs.K : g_mqs.A;
+  hipLaunchKernelGGL(mqs_compact_kernel, dim3((unsigned)l), dim3(MQS_THREADS), 0, s, X, ld, l, cat_d, var, w_d, nvc, pos, cnt_d, P);
+  TU_CHK(hipGetLastError());
+  double *M = (g_mqs.slot == 0 ? g_mqs.K : g_mqs.A).as<double>();
   long base = 0;
   for (int k = 0; k < nvc; ++k) {
     if (cnt[k] > 0) {
       // K_c (upper tiles) += X_c^T X_c: the panel rows of category c as [k = snp][m = individual] -> ('T', 'N')
-      const double *Pc = g_mqs.P + (size_t)base * ld;
-      MQCHK(launch_dgemm('T', 'N', n, n, (long)cnt[k], 1.0, Pc, ld, Pc, ld, 1.0, M + (size_t)k * n * ld, ld, true, false, s));
+      const double *Pc = P + (size_t)base * ld;
+      TU_CHK(launch_dgemm('T', 'N', n, n, (long)cnt[k], 1.0, Pc, ld, Pc, ld, 1.0, M + (size_t)k * n * ld, ld, true, false, s));
       g_mqs.ns[k] += cnt[k];
     }
     base += cnt[k];
@@ -338,7 +255,7 @@ const hipStream_t S0 = nullptr;
 
 int row_stats(const double *M, long n, long ld, double *rs, double *dg, hipStream_t s, std::string &msg) {
   hipLaunchKernelGGL(mqs_rowstat_kernel, dim3((unsigned)((n + 3) / 4)), dim3(MQS_THREADS), 0, s, M, n, ld, rs, dg);
-  MQCHK(hipGetLastError());
+  TU_CHK(hipGetLastError());
   return GEMMA_HIP_OK;
 }
 
@@ -348,15 +265,15 @@ int finish_matrix(double *M, long n, long ld, long ns, double *work, std::string
   double *rs = work, *dg = work + ld, *tot = work + 2 * ld;
   const unsigned nb = (unsigned)((n + 31) / 32), ny = (unsigned)std::min<long>(n, 65535), nx = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(mqs_symm_scale_kernel, dim3(nb, nb), dim3(32, 8), 0, S0, M, n, ld, ns > 0 ? (double)ns : 1.0);
-  MQCHK(hipGetLastError());
+  TU_CHK(hipGetLastError());
   if ((rc = row_stats(M, n, ld, rs, dg, S0, msg))) return rc;
   hipLaunchKernelGGL(mqs_total_kernel, dim3(1), dim3(1024), 0, S0, rs, n, tot);
   hipLaunchKernelGGL(mqs_center_kernel, dim3(nx, ny), dim3(256), 0, S0, M, n, ld, rs, tot);
-  MQCHK(hipGetLastError());
+  TU_CHK(hipGetLastError());
   if ((rc = row_stats(M, n, ld, rs, dg, S0, msg))) return rc;
   hipLaunchKernelGGL(mqs_total_kernel, dim3(1), dim3(1024), 0, S0, dg, n, tot + 1);
   hipLaunchKernelGGL(mqs_scale_kernel, dim3(nx, ny), dim3(256), 0, S0, M, n, ld, tot + 1);
-  MQCHK(hipGetLastError());
+  TU_CHK(hipGetLastError());
   return GEMMA_HIP_OK;
 }
 
@@ -366,21 +283,18 @@ int mqs_S_x(long n, int n_vc, const double *A, const double *K, long ld, int c, 
   const bool same = (A == K);
   const long lv = (n + 1) & ~1L; // stride of the per-matrix vectors: even, so that two-double loads stay aligned
   const bool vec = (ld % 2) == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(K) & 15) == 0;
-  double *work = nullptr;
-  int rc = dalloc(&work, (size_t)4 * n_vc * lv + 3 * (size_t)lv, msg);
+  ScopedBuf wb;
+  int rc = wb.reserve(((size_t)4 * n_vc * lv + 3 * (size_t)lv) * 8, "mqs", msg);
   if (rc) return rc;
-  struct Free {
-    double *&p;
-    ~Free() { dfree(p); }
-  } free_work{work};
+  double *work = wb.as<double>();
   double *sK = work, *dK = sK + (size_t)n_vc * lv, *sA = dK + (size_t)n_vc * lv, *dA = sA + (size_t)n_vc * lv, *huv = dA + (size_t)n_vc * lv;
   for (int j = 0; j < n_vc; ++j) {
     if ((rc = row_stats(K + (size_t)j * n * ld, n, ld, sK + (size_t)j * lv, dK + (size_t)j * lv, s, msg))) return rc;
     if (!same && (rc = row_stats(A + (size_t)j * n * ld, n, ld, sA + (size_t)j * lv, dA + (size_t)j * lv, s, msg))) return rc;
   }
   std::vector<double> hs((size_t)4 * n_vc * lv), hp((size_t)3 * n);
-  MQCHK(hipMemcpyAsync(hs.data(), work, hs.size() * 8, hipMemcpyDeviceToHost, s));
-  MQCHK(hipStreamSynchronize(s));
+  TU_CHK(hipMemcpyAsync(hs.data(), work, hs.size() * 8, hipMemcpyDeviceToHost, s));
+  TU_CHK(hipStreamSynchronize(s));
   const double *h_sK = hs.data(), *h_dK = h_sK + (size_t)n_vc * lv;
   const double *h_sA = same ? h_sK : h_dK + (size_t)n_vc * lv, *h_dA = same ? h_dK : h_sA + (size_t)n_vc * lv;
   const double *d_sA = same ? sK : sA;
@@ -393,9 +307,9 @@ int mqs_S_x(long n, int n_vc, const double *A, const double *K, long ld, int c, 
       else
         hipLaunchKernelGGL(mqs_pair_kernel<false>, dim3((unsigned)((n + 3) / 4)), dim3(MQS_THREADS), 0, s, Ai, Kj, n, ld,
                            d_sA + (size_t)i * lv, sK + (size_t)j * lv, huv);
-      MQCHK(hipGetLastError());
-      MQCHK(hipMemcpyAsync(hp.data(), huv, hp.size() * 8, hipMemcpyDeviceToHost, s));
-      MQCHK(hipStreamSynchronize(s));
+      TU_CHK(hipGetLastError());
+      TU_CHK(hipMemcpyAsync(hp.data(), huv, hp.size() * 8, hipMemcpyDeviceToHost, s));
+      TU_CHK(hipStreamSynchronize(s));
       double sv, vv;
       finish_pair(n, c, h_sA + (size_t)i * lv, h_dA + (size_t)i * lv, h_sK + (size_t)j * lv, h_dK + (size_t)j * lv, hp.data(),
                   hp.data() + n, hp.data() + 2 * n, &sv, &vv);
@@ -413,23 +327,24 @@ int mqs_end_x(double *S, double *ns, std::string &msg) {
   const long n = g_mqs.n, ld = g_mqs.ld;
   const int nvc = g_mqs.nvc;
   int rc;
-  if (g_mqs.last) MQCHK(hipStreamSynchronize(g_mqs.last));
+  if (g_mqs.last) TU_CHK(hipStreamSynchronize(g_mqs.last));
   g_mqs.active = false;
   free_block_buffers();
-  double *work = nullptr;
-  if ((rc = dalloc(&work, (size_t)2 * ld + 2, msg))) return rc;
-  double *M = g_mqs.slot == 0 ? g_mqs.K : g_mqs.A;
+  ScopedBuf wb;
+  if ((rc = wb.reserve(((size_t)2 * ld + 2) * 8, "mqs", msg))) return rc;
+  double *work = wb.as<double>();
+  double *M = (g_mqs.slot == 0 ? g_mqs.K : g_mqs.A).as<double>();
   for (int k = 0; k < nvc && !rc; ++k) rc = finish_matrix(M + (size_t)k * n * ld, n, ld, g_mqs.ns[k], work, msg);
   hipError_t e = hipStreamSynchronize(S0);
-  dfree(work);
+  wb.release();
   if (rc) return rc;
-  if (e != hipSuccess) return herr(e, "mqs_end", msg);
+  if (e != hipSuccess) return hip_err(e, "mqs_end", msg);
   if (g_mqs.slot == 0) g_mqs.haveK = true;
   else g_mqs.haveA = true;
   if (ns)
     for (int k = 0; k < nvc; ++k) ns[k] = (double)g_mqs.ns[k];
   if (!S) return GEMMA_HIP_OK;
-  return mqs_S_x(n, nvc, g_mqs.haveA ? g_mqs.A : g_mqs.K, g_mqs.K, ld, g_mqs.c, S, S0, msg);
+  return mqs_S_x(n, nvc, (g_mqs.haveA ? g_mqs.A : g_mqs.K).as<double>(), g_mqs.K.as<double>(), ld, g_mqs.c, S, S0, msg);
 }
 
 int mqs_get_x(int slot, int i_vc, double *out, std::string &msg) {
@@ -438,9 +353,9 @@ int mqs_get_x(int slot, int i_vc, double *out, std::string &msg) {
           std::to_string(g_mqs.nvc);
     return GEMMA_HIP_EINVAL;
   }
-  const double *M = (slot == 1 && g_mqs.haveA) ? g_mqs.A : g_mqs.K;
+  const double *M = ((slot == 1 && g_mqs.haveA) ? g_mqs.A : g_mqs.K).as<double>();
   const long n = g_mqs.n, ld = g_mqs.ld;
-  MQCHK(hipMemcpy2D(out, (size_t)n * 8, M + (size_t)i_vc * n * ld, (size_t)ld * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToHost));
+  TU_CHK(hipMemcpy2D(out, (size_t)n * 8, M + (size_t)i_vc * n * ld, (size_t)ld * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToHost));
   return GEMMA_HIP_OK;
 }
 

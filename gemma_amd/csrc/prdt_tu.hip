@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/gemma_hip.h"
+#include "tu_common.h"
 #include "dgemm_mfma.hip.h"
 #include "eigh_tu.h"
 #include "geno_mv.hip.h"
@@ -23,45 +24,11 @@ namespace gemma_hip {
 
 namespace {
 
-int herr(hipError_t e, const char *what, std::string &msg) {
-  msg = std::string(what) + ": " + hipGetErrorString(e);
-  return GEMMA_HIP_ERUNTIME;
-}
-#define PDCHK(expr)                                    \
-  do {                                                 \
-    hipError_t e_ = (expr);                            \
-    if (e_ != hipSuccess) return herr(e_, #expr, msg); \
-  } while (0)
-
-struct Buf {
-  void *p = nullptr;
-  size_t cap = 0;
-  int reserve(size_t bytes, std::string &msg) {
-    if (bytes <= cap && p) return GEMMA_HIP_OK;
-    release();
-    bytes = std::max<size_t>(bytes, 16);
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      msg = "prdt: cannot allocate " + std::to_string(bytes) + " bytes of device memory";
-      return GEMMA_HIP_ENOMEM;
-    }
-    cap = bytes;
-    return GEMMA_HIP_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T> T *as() { return reinterpret_cast<T *>(p); }
-};
-
 // the groups of individuals of a block's rows, on the device in both forms the kernels read
 struct Groups {
   long ni_total = 0, words = 0, n_a = 0, n_b = 0;
   std::vector<int> pos_a, pos_b; // positions of the A / B individuals in ni_total
-  Buf amask, bmask, grp, posb;
+  DevBuf amask, bmask, grp, posb;
   int set(const int *ind, long ni, std::string &msg) { // ind == nullptr: everybody is in A
     ni_total = ni;
     words = (ni + 15) / 16;
@@ -78,13 +45,13 @@ struct Groups {
     n_a = (long)pos_a.size();
     n_b = (long)pos_b.size();
     int rc;
-    if ((rc = amask.reserve(words * 4, msg)) || (rc = bmask.reserve(words * 4, msg)) || (rc = grp.reserve(ni, msg)) ||
-        (rc = posb.reserve(std::max<long>(n_b, 1) * 4, msg)))
+    if ((rc = amask.reserve(words * 4, "prdt", msg)) || (rc = bmask.reserve(words * 4, "prdt", msg)) || (rc = grp.reserve(ni, "prdt", msg)) ||
+        (rc = posb.reserve(std::max<long>(n_b, 1) * 4, "prdt", msg)))
       return rc;
-    PDCHK(hipMemcpy(amask.p, am.data(), words * 4, hipMemcpyHostToDevice));
-    PDCHK(hipMemcpy(bmask.p, bm.data(), words * 4, hipMemcpyHostToDevice));
-    PDCHK(hipMemcpy(grp.p, g.data(), ni, hipMemcpyHostToDevice));
-    if (n_b) PDCHK(hipMemcpy(posb.p, pos_b.data(), n_b * 4, hipMemcpyHostToDevice));
+    TU_CHK(hipMemcpy(amask.p, am.data(), words * 4, hipMemcpyHostToDevice));
+    TU_CHK(hipMemcpy(bmask.p, bm.data(), words * 4, hipMemcpyHostToDevice));
+    TU_CHK(hipMemcpy(grp.p, g.data(), ni, hipMemcpyHostToDevice));
+    if (n_b) TU_CHK(hipMemcpy(posb.p, pos_b.data(), n_b * 4, hipMemcpyHostToDevice));
     return GEMMA_HIP_OK;
   }
   MvGroups dev() {
@@ -109,14 +76,14 @@ struct RidgeState {
   double scale = 1.0;
   std::vector<double> r; // host copy: scattered again when the indicator changes
   Groups grp;
-  Buf r_full, work, stage_in, stage_out, dense;
+  DevBuf r_full, work, stage_in, stage_out, dense;
 } g_rg;
 
 struct PrdtState {
   bool active = false;
   hipStream_t last = nullptr; // the stream of the last prdt_add
   Groups grp;
-  Buf y, work, stage_in, stage_w, used, dense;
+  DevBuf y, work, stage_in, stage_w, used, dense;
 } g_pd;
 
 bool g_aux = false;
@@ -130,9 +97,9 @@ int ridge_scatter(std::string &msg) {
   const long len = mv_rfull_len(g_rg.grp.ni_total);
   std::vector<double> full(len, 0.0);
   for (long j = 0; j < g_rg.n; ++j) full[g_rg.grp.pos_a[j]] = g_rg.r[j];
-  int rc = g_rg.r_full.reserve(len * 8, msg);
+  int rc = g_rg.r_full.reserve(len * 8, "prdt", msg);
   if (rc) return rc;
-  PDCHK(hipMemcpy(g_rg.r_full.p, full.data(), len * 8, hipMemcpyHostToDevice));
+  TU_CHK(hipMemcpy(g_rg.r_full.p, full.data(), len * 8, hipMemcpyHostToDevice));
   return GEMMA_HIP_OK;
 }
 
@@ -165,7 +132,7 @@ __global__ __launch_bounds__(256) void bv_rowsum_kernel(const double *G, long ld
   if (i >= ni) return;
   double a = 0.0;
   for (long j = lane; j < n_a; j += 64) a += G[i * ldg + pos_a[j]];
-  a = mv_wsum(a);
+  a = wave_sum(a);
   if (lane == 0) gw[i] = a;
 }
 
@@ -173,7 +140,7 @@ __global__ __launch_bounds__(256) void bv_wgw_kernel(const double *gw, const int
   __shared__ double red[4];
   double a = 0.0;
   for (long j = threadIdx.x; j < n_a; j += 256) a += gw[pos_a[j]];
-  a = mv_wsum(a);
+  a = wave_sum(a);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = a;
   __syncthreads();
   if (threadIdx.x == 0) *d = ((red[0] + red[1]) + red[2]) + red[3];
@@ -237,33 +204,33 @@ int ridge_setup_x(long n, const double *U, long ldu, const double *eval, bool ue
   aux_init();
   // dense: [U copy n x ldc | eval n | Uty n | B n x 2 | C n x 2]
   const long ldc = ue_device ? 0 : ((n + 1) & ~1L);
-  int rc = g_rg.dense.reserve((size_t)(n * ldc + 6 * n) * 8, msg);
+  int rc = g_rg.dense.reserve((size_t)(n * ldc + 6 * n) * 8, "prdt", msg);
   if (rc) return rc;
   double *base = g_rg.dense.as<double>();
   double *Uc = base, *ev = base + n * ldc, *uy = ev + n, *B = uy + n, *Cm = B + 2 * n;
   const double *Ud = U, *evd = eval, *uyd = Uty;
   long ld = ldu;
   if (!ue_device) {
-    PDCHK(hipMemcpy2DAsync(Uc, ldc * 8, U, ldu * 8, n * 8, n, hipMemcpyHostToDevice, s));
-    PDCHK(hipMemcpyAsync(ev, eval, n * 8, hipMemcpyHostToDevice, s));
+    TU_CHK(hipMemcpy2DAsync(Uc, ldc * 8, U, ldu * 8, n * 8, n, hipMemcpyHostToDevice, s));
+    TU_CHK(hipMemcpyAsync(ev, eval, n * 8, hipMemcpyHostToDevice, s));
     Ud = Uc; evd = ev; ld = ldc;
   }
   if (!uty_device) {
-    PDCHK(hipMemcpyAsync(uy, Uty, n * 8, hipMemcpyHostToDevice, s));
+    TU_CHK(hipMemcpyAsync(uy, Uty, n * 8, hipMemcpyHostToDevice, s));
     uyd = uy;
   }
   ridge_rhs_kernel<<<nb(n), 256, 0, s>>>(evd, uyd, n, lambda, B);
-  PDCHK(hipGetLastError());
-  PDCHK(launch_dgemm('N', 'N', n, 2, n, 1.0, Ud, ld, B, 2, 0.0, Cm, 2, false, false, s));
+  TU_CHK(hipGetLastError());
+  TU_CHK(launch_dgemm('N', 'N', n, 2, n, 1.0, Ud, ld, B, 2, 0.0, Cm, 2, false, false, s));
   std::vector<double> c2(2 * n);
-  PDCHK(hipMemcpyAsync(c2.data(), Cm, 2 * n * 8, hipMemcpyDeviceToHost, s));
-  PDCHK(hipStreamSynchronize(s));
+  TU_CHK(hipMemcpyAsync(c2.data(), Cm, 2 * n * 8, hipMemcpyDeviceToHost, s));
+  TU_CHK(hipStreamSynchronize(s));
   g_rg.r.resize(n);
   for (long i = 0; i < n; ++i) g_rg.r[i] = c2[2 * i];
   if (bv_out) {
     std::vector<double> bv(n);
     for (long i = 0; i < n; ++i) bv[i] = c2[2 * i + 1];
-    if (uty_device) PDCHK(hipMemcpy(bv_out, bv.data(), n * 8, hipMemcpyHostToDevice));
+    if (uty_device) TU_CHK(hipMemcpy(bv_out, bv.data(), n * 8, hipMemcpyHostToDevice));
     else memcpy(bv_out, bv.data(), n * 8);
   }
   return ridge_install(n, lambda / (double)ns_test, msg);
@@ -291,22 +258,21 @@ int ridge_batch_x(int geno_kind, const void *geno, long l, long ld, bool device,
   const long row = plink ? (g_rg.grp.ni_total + 3) / 4 : g_rg.grp.ni_total; // elements of a row that are read
   for (long s0 = 0; s0 < l; s0 += MV_MAX_ROWS) {
     const long m = std::min(MV_MAX_ROWS, l - s0);
-    int rc = g_rg.work.reserve((size_t)mv_xtr_work(g_rg.grp.ni_total, m) * 8, msg);
+    int rc = g_rg.work.reserve((size_t)mv_xtr_work(g_rg.grp.ni_total, m) * 8, "prdt", msg);
     if (rc) return rc;
-    const char *gd = static_cast<const char *>(geno) + (size_t)s0 * ld * esz;
+    const void *gd = static_cast<const char *>(geno) + (size_t)s0 * ld * esz;
     double *ad = alpha_out + s0;
     long ldd = ld;
     if (!device) { // only the `row` leading elements of each host row are touched: the caller's last row may end there
-      if ((rc = g_rg.stage_in.reserve((size_t)m * row * esz, msg)) || (rc = g_rg.stage_out.reserve((size_t)m * 8, msg))) return rc;
-      PDCHK(hipMemcpy2DAsync(g_rg.stage_in.p, row * esz, gd, ld * esz, row * esz, m, hipMemcpyHostToDevice, s));
-      gd = g_rg.stage_in.as<char>();
+      if ((rc = g_rg.stage_out.reserve((size_t)m * 8, "prdt", msg)) ||
+          (rc = stage_rows(g_rg.stage_in, gd, m, row * esz, ld * esz, esz, s, "prdt", msg, gd, ldd)))
+        return rc;
       ad = g_rg.stage_out.as<double>();
-      ldd = row;
     }
-    PDCHK(launch_xtr(plink, gd, m, ldd, g_rg.grp.dev(), g_rg.r_full.as<double>(), g_rg.scale, ad, g_rg.work.as<double>(), s));
+    TU_CHK(launch_xtr(plink, gd, m, ldd, g_rg.grp.dev(), g_rg.r_full.as<double>(), g_rg.scale, ad, g_rg.work.as<double>(), s));
     if (!device) {
-      PDCHK(hipMemcpyAsync(alpha_out + s0, ad, (size_t)m * 8, hipMemcpyDeviceToHost, s));
-      PDCHK(hipStreamSynchronize(s));
+      TU_CHK(hipMemcpyAsync(alpha_out + s0, ad, (size_t)m * 8, hipMemcpyDeviceToHost, s));
+      TU_CHK(hipStreamSynchronize(s));
     }
   }
   return GEMMA_HIP_OK;
@@ -328,8 +294,8 @@ int prdt_begin_x(const int *indicator_idv, long ni_total, std::string &msg) {
   g_pd.last = nullptr;
   int rc = g_pd.grp.set(indicator_idv, ni_total, msg);
   if (rc) return rc;
-  if ((rc = g_pd.y.reserve(std::max<long>(g_pd.grp.n_b, 1) * 8, msg))) return rc;
-  PDCHK(hipMemset(g_pd.y.p, 0, std::max<long>(g_pd.grp.n_b, 1) * 8));
+  if ((rc = g_pd.y.reserve(std::max<long>(g_pd.grp.n_b, 1) * 8, "prdt", msg))) return rc;
+  TU_CHK(hipMemset(g_pd.y.p, 0, std::max<long>(g_pd.grp.n_b, 1) * 8));
   g_pd.active = true;
   return GEMMA_HIP_OK;
 }
@@ -338,7 +304,7 @@ int prdt_add_x(int geno_kind, const void *geno, long l, long ld, bool device, co
                std::string &msg) {
   const bool plink = geno_kind == GEMMA_GENO_PLINK_2BIT;
   const size_t esz = plink ? 1 : 8;
-  int rc = g_pd.work.reserve((size_t)mv_xw_work(g_pd.grp.ni_total, l) * 8, msg);
+  int rc = g_pd.work.reserve((size_t)mv_xw_work(g_pd.grp.ni_total, l) * 8, "prdt", msg);
   if (rc) return rc;
   const void *gd = geno;
   const double *wd = effect;
@@ -346,23 +312,22 @@ int prdt_add_x(int geno_kind, const void *geno, long l, long ld, bool device, co
   long ldd = ld;
   if (!device) { // only the leading elements of each host row that are read are copied
     const long row = plink ? (g_pd.grp.ni_total + 3) / 4 : g_pd.grp.ni_total;
-    if ((rc = g_pd.stage_in.reserve((size_t)l * row * esz, msg)) || (rc = g_pd.stage_w.reserve((size_t)l * 8, msg))) return rc;
-    PDCHK(hipMemcpy2DAsync(g_pd.stage_in.p, row * esz, geno, ld * esz, row * esz, l, hipMemcpyHostToDevice, s));
-    PDCHK(hipMemcpyAsync(g_pd.stage_w.p, effect, (size_t)l * 8, hipMemcpyHostToDevice, s));
-    gd = g_pd.stage_in.p;
+    if ((rc = g_pd.stage_w.reserve((size_t)l * 8, "prdt", msg)) ||
+        (rc = stage_rows(g_pd.stage_in, geno, l, row * esz, ld * esz, esz, s, "prdt", msg, gd, ldd)))
+      return rc;
+    TU_CHK(hipMemcpyAsync(g_pd.stage_w.p, effect, (size_t)l * 8, hipMemcpyHostToDevice, s));
     wd = g_pd.stage_w.as<double>();
-    ldd = row;
   }
   if (!device || !used_out) {
-    if ((rc = g_pd.used.reserve((size_t)l * 4, msg))) return rc;
+    if ((rc = g_pd.used.reserve((size_t)l * 4, "prdt", msg))) return rc;
     ud = g_pd.used.as<int>();
   }
   g_pd.last = s; // prdt_end waits for it: the device form is asynchronous on the caller's stream
-  PDCHK(launch_xw(plink, gd, l, ldd, g_pd.grp.dev(), wd, g_pd.grp.posb.as<int>(), g_pd.grp.n_b, g_pd.y.as<double>(), ud,
+  TU_CHK(launch_xw(plink, gd, l, ldd, g_pd.grp.dev(), wd, g_pd.grp.posb.as<int>(), g_pd.grp.n_b, g_pd.y.as<double>(), ud,
                   g_pd.work.as<double>(), s));
   if (!device) {
-    if (used_out) PDCHK(hipMemcpyAsync(used_out, ud, (size_t)l * 4, hipMemcpyDeviceToHost, s));
-    PDCHK(hipStreamSynchronize(s));
+    if (used_out) TU_CHK(hipMemcpyAsync(used_out, ud, (size_t)l * 4, hipMemcpyDeviceToHost, s));
+    TU_CHK(hipStreamSynchronize(s));
   }
   return GEMMA_HIP_OK;
 }
@@ -377,7 +342,7 @@ int prdt_add_bv_x(const double *G, long ni_total, long ldg, bool device, const d
   const long gcopy = device ? 0 : ni_total * ni_total;
   const long posd = (no + 1) / 2 + 1;
   const size_t doubles = (size_t)gcopy + ni_total + 2 + posd + (size_t)(2 * no + nf) * ldo + 4 * no;
-  int rc = g_pd.dense.reserve(doubles * 8, msg);
+  int rc = g_pd.dense.reserve(doubles * 8, "prdt", msg);
   if (rc) return rc;
   double *p = g_pd.dense.as<double>();
   double *Gc = p; p += gcopy;
@@ -394,37 +359,37 @@ int prdt_add_bv_x(const double *G, long ni_total, long ldg, bool device, const d
   const double *Gd = G;
   long ld = ldg;
   if (!device) {
-    PDCHK(hipMemcpy2DAsync(Gc, ni_total * 8, G, ldg * 8, ni_total * 8, ni_total, hipMemcpyHostToDevice, s));
+    TU_CHK(hipMemcpy2DAsync(Gc, ni_total * 8, G, ldg * 8, ni_total * 8, ni_total, hipMemcpyHostToDevice, s));
     Gd = Gc;
     ld = ni_total;
   }
-  PDCHK(hipMemcpyAsync(pos_a, gr.pos_a.data(), no * 4, hipMemcpyHostToDevice, s));
-  PDCHK(hipMemcpyAsync(u, u_hat, no * 8, hipMemcpyHostToDevice, s));
+  TU_CHK(hipMemcpyAsync(pos_a, gr.pos_a.data(), no * 4, hipMemcpyHostToDevice, s));
+  TU_CHK(hipMemcpyAsync(u, u_hat, no * 8, hipMemcpyHostToDevice, s));
   bv_rowsum_kernel<<<(unsigned)((ni_total + 3) / 4), 256, 0, s>>>(Gd, ld, ni_total, pos_a, no, gw);
   bv_wgw_kernel<<<1, 256, 0, s>>>(gw, pos_a, no, d);
   bv_gather_kernel<<<dim3(nb(no), (unsigned)no), 256, 0, s>>>(Gd, ld, pos_a, no, true, pos_a, no, gw, d, Goo, no); // dense: the solver's form
   bv_gather_kernel<<<dim3(nb(no), (unsigned)nf), 256, 0, s>>>(Gd, ld, gr.posb.as<int>(), nf, false, pos_a, no, gw, d, Gfo, ldo);
-  PDCHK(hipGetLastError());
+  TU_CHK(hipGetLastError());
   rc = eigh_device_x(Goo, no, U, ev, s, msg);
   if (rc) return rc;
   // Utu = U' u; Utu /= eval (pseudo-inverse); v = U Utu; y += Gfo v
-  PDCHK(launch_dgemm('T', 'N', no, 1, no, 1.0, U, no, u, 1, 0.0, utu, 1, false, false, s));
+  TU_CHK(launch_dgemm('T', 'N', no, 1, no, 1.0, U, no, u, 1, 0.0, utu, 1, false, false, s));
   bv_pinv_kernel<<<nb(no), 256, 0, s>>>(ev, no, utu);
-  PDCHK(hipGetLastError());
-  PDCHK(launch_dgemm('N', 'N', no, 1, no, 1.0, U, no, utu, 1, 0.0, v, 1, false, false, s));
-  PDCHK(launch_dgemm('N', 'N', nf, 1, no, 1.0, Gfo, ldo, v, 1, 1.0, g_pd.y.as<double>(), 1, false, false, s));
-  PDCHK(hipStreamSynchronize(s));
+  TU_CHK(hipGetLastError());
+  TU_CHK(launch_dgemm('N', 'N', no, 1, no, 1.0, U, no, utu, 1, 0.0, v, 1, false, false, s));
+  TU_CHK(launch_dgemm('N', 'N', nf, 1, no, 1.0, Gfo, ldo, v, 1, 1.0, g_pd.y.as<double>(), 1, false, false, s));
+  TU_CHK(hipStreamSynchronize(s));
   return GEMMA_HIP_OK;
 }
 
 int prdt_end_x(double pheno_mean, int probit, double *y_prdt, std::string &msg) {
   const long nf = g_pd.grp.n_b;
-  PDCHK(hipStreamSynchronize(g_pd.last)); // the adds of the device form may still be running on the caller's stream
+  TU_CHK(hipStreamSynchronize(g_pd.last)); // the adds of the device form may still be running on the caller's stream
   g_pd.last = nullptr;
   if (nf > 0) {
     prdt_tail_kernel<<<nb(nf), 256, 0, nullptr>>>(g_pd.y.as<double>(), nf, pheno_mean, probit);
-    PDCHK(hipGetLastError());
-    PDCHK(hipMemcpy(y_prdt, g_pd.y.p, nf * 8, hipMemcpyDeviceToHost));
+    TU_CHK(hipGetLastError());
+    TU_CHK(hipMemcpy(y_prdt, g_pd.y.p, nf * 8, hipMemcpyDeviceToHost));
   }
   prdt_release();
   return GEMMA_HIP_OK;

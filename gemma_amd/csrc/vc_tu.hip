@@ -15,6 +15,8 @@
 
 #include "../../include/gemma_hip.h"
 #include "../../include/gemma_vc_hybrid.hpp"
+#include "tu_common.h"
+#include "host_linalg.h"
 #include "spd_inv.hip.h"
 #include "vc.hip.h"
 #include "vc_tu.h"
@@ -28,9 +30,9 @@ struct VcState {
   long n = 0, ld = 0, ldk = 0;
   int nvc = 0, c = 0;
   std::vector<const double *> K; // device, ldk
-  double *Kown = nullptr;        // host kinships copied here (nvc x n x ld)
-  double *H = nullptr;           // H -> H^-1 -> P (n x ld)
-  double *Wd = nullptr, *Xd = nullptr, *Yd = nullptr, *partial = nullptr; // W (n x c); mat-vec operands (n x 2c or n x 16)
+  DevBuf Kown;                   // host kinships copied here (nvc x n x ld)
+  DevBuf H;                      // H -> H^-1 -> P (n x ld)
+  DevBuf Wd, Xd, Yd, partial;    // W (n x c); mat-vec operands (n x 2c or n x 16)
   std::vector<double> W, y, traceG;
   SpdWork spd;
   hipEvent_t ev[6] = {};
@@ -44,64 +46,6 @@ struct VcState {
 } g_vc;
 
 const hipStream_t S0 = nullptr;
-
-int herr(hipError_t e, const char *what, std::string &msg) {
-  msg = std::string(what) + ": " + hipGetErrorString(e);
-  return GEMMA_HIP_ERUNTIME;
-}
-#define VCCHK(expr)                                       \
-  do {                                                    \
-    hipError_t e_ = (expr);                               \
-    if (e_ != hipSuccess) return herr(e_, #expr, msg);    \
-  } while (0)
-
-int dalloc(double **p, size_t doubles, std::string &msg) {
-  if (hipMalloc((void **)p, std::max<size_t>(doubles, 1) * 8) != hipSuccess) {
-    (void)hipGetLastError();
-    *p = nullptr;
-    msg = "vc: cannot allocate " + std::to_string(doubles * 8) + " bytes of device memory";
-    return GEMMA_HIP_ENOMEM;
-  }
-  return GEMMA_HIP_OK;
-}
-
-void dfree(double *&p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-}
-
-// Gauss-Jordan inverse with partial pivoting (LUDecomp + LUInvert of the small matrices, src/mathfunc.cpp); false if singular
-bool small_inverse(std::vector<double> &A, int m) {
-  std::vector<double> I(m * m, 0.0);
-  for (int i = 0; i < m; ++i) I[i * m + i] = 1.0;
-  for (int k = 0; k < m; ++k) {
-    int p = k;
-    for (int i = k + 1; i < m; ++i)
-      if (std::fabs(A[i * m + k]) > std::fabs(A[p * m + k])) p = i;
-    if (A[p * m + k] == 0.0) return false;
-    if (p != k)
-      for (int j = 0; j < m; ++j) {
-        std::swap(A[k * m + j], A[p * m + j]);
-        std::swap(I[k * m + j], I[p * m + j]);
-      }
-    const double d = 1.0 / A[k * m + k];
-    for (int j = 0; j < m; ++j) {
-      A[k * m + j] *= d;
-      I[k * m + j] *= d;
-    }
-    for (int i = 0; i < m; ++i) {
-      if (i == k) continue;
-      const double f = A[i * m + k];
-      if (f == 0.0) continue;
-      for (int j = 0; j < m; ++j) {
-        A[i * m + j] -= f * A[k * m + j];
-        I[i * m + j] -= f * I[k * m + j];
-      }
-    }
-  }
-  A = I;
-  return true;
-}
 
 // true when W^T W (m x m) is numerically rank-deficient, whatever the units of W's columns: the test runs on the equilibrated
 // S = D^-1/2 W^T W D^-1/2 (D = its diagonal, so S_jj = 1), where a pivot of the partially pivoted elimination at or below
@@ -140,13 +84,14 @@ double dot(const double *a, const double *b, long n, long sa = 1, long sb = 1) {
 
 // out (n x m, host) = M X, X (n x m, host), m <= 16: one pass over M
 int matvec(const double *M, long ldm, const std::vector<double> &X, int m, std::vector<double> &out, std::string &msg) {
+  double *const Xd = g_vc.Xd.as<double>(), *const Yd = g_vc.Yd.as<double>();
   const long n = g_vc.n;
-  VCCHK(hipMemcpyAsync(g_vc.Xd, X.data(), (size_t)n * m * 8, hipMemcpyHostToDevice, S0));
-  hipLaunchKernelGGL(vc_matvec_kernel, dim3((unsigned)((n + 3) / 4)), dim3(VC_THREADS), 0, S0, M, n, ldm, g_vc.Xd, m, g_vc.Yd);
-  VCCHK(hipGetLastError());
+  TU_CHK(hipMemcpyAsync(Xd, X.data(), (size_t)n * m * 8, hipMemcpyHostToDevice, S0));
+  hipLaunchKernelGGL(vc_matvec_kernel, dim3((unsigned)((n + 3) / 4)), dim3(VC_THREADS), 0, S0, M, n, ldm, Xd, m, Yd);
+  TU_CHK(hipGetLastError());
   out.resize((size_t)n * m);
-  VCCHK(hipMemcpyAsync(out.data(), g_vc.Yd, (size_t)n * m * 8, hipMemcpyDeviceToHost, S0));
-  VCCHK(hipStreamSynchronize(S0));
+  TU_CHK(hipMemcpyAsync(out.data(), Yd, (size_t)n * m * 8, hipMemcpyDeviceToHost, S0));
+  TU_CHK(hipStreamSynchronize(S0));
   return GEMMA_HIP_OK;
 }
 
@@ -161,11 +106,11 @@ int traces(const std::vector<std::pair<const double *, long>> &a, const std::vec
     pr.b[p] = b[p].first;
     pr.ldb[p] = b[p].second;
   }
-  hipLaunchKernelGGL(vc_trace_kernel, dim3(VC_TRACE_BLOCKS), dim3(VC_THREADS), 0, S0, pr, g_vc.n, g_vc.partial);
-  VCCHK(hipGetLastError());
+  hipLaunchKernelGGL(vc_trace_kernel, dim3(VC_TRACE_BLOCKS), dim3(VC_THREADS), 0, S0, pr, g_vc.n, g_vc.partial.as<double>());
+  TU_CHK(hipGetLastError());
   std::vector<double> part((size_t)VC_TRACE_BLOCKS * pr.count);
-  VCCHK(hipMemcpyAsync(part.data(), g_vc.partial, part.size() * 8, hipMemcpyDeviceToHost, S0));
-  VCCHK(hipStreamSynchronize(S0));
+  TU_CHK(hipMemcpyAsync(part.data(), g_vc.partial.p, part.size() * 8, hipMemcpyDeviceToHost, S0));
+  TU_CHK(hipStreamSynchronize(S0));
   tr.assign(pr.count, 0.0);
   for (int blk = 0; blk < VC_TRACE_BLOCKS; ++blk)
     for (int p = 0; p < pr.count; ++p) tr[p] += part[(size_t)blk * pr.count + p];
@@ -174,7 +119,7 @@ int traces(const std::vector<std::pair<const double *, long>> &a, const std::vec
 
 int diagonal(const double *M, long ldm, std::vector<double> &d, std::string &msg) {
   d.resize(g_vc.n);
-  VCCHK(hipMemcpy2D(d.data(), 8, M, (ldm + 1) * 8, 8, g_vc.n, hipMemcpyDeviceToHost));
+  TU_CHK(hipMemcpy2D(d.data(), 8, M, (ldm + 1) * 8, 8, g_vc.n, hipMemcpyDeviceToHost));
   return GEMMA_HIP_OK;
 }
 
@@ -189,7 +134,7 @@ int assemble(const std::vector<const double *> &Ks, long ldk, const std::vector<
   }
   const unsigned grid = (unsigned)std::min<long>(g_vc.n, 4096);
   hipLaunchKernelGGL(vc_assemble_kernel, dim3(grid), dim3(VC_THREADS), 0, S0, mats, g_vc.n, ldk, s_e, out, ldo);
-  VCCHK(hipGetLastError());
+  TU_CHK(hipGetLastError());
   return GEMMA_HIP_OK;
 }
 
@@ -227,28 +172,22 @@ int spd_inverse_x(double *A, long n, long lda, double *logdet, long *bad_pivot, 
   const bool inplace = (lda % 2) == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0;
   if (inplace) return spd_inverse_device(A, n, lda, logdet, bad_pivot, g_vc.spd, s, msg);
   const long ld = (n + 1) & ~1L; // odd leading dimension: through an aligned copy
-  double *T = nullptr;
-  int rc = dalloc(&T, (size_t)n * ld, msg);
+  ScopedBuf Tb;
+  int rc = Tb.reserve((size_t)n * ld * 8, "vc", msg);
   if (rc) return rc;
+  double *T = Tb.as<double>();
   hipError_t e = hipMemcpy2DAsync(T, ld * 8, A, lda * 8, n * 8, n, hipMemcpyDeviceToDevice, s);
   if (e == hipSuccess) {
     rc = spd_inverse_device(T, n, ld, logdet, bad_pivot, g_vc.spd, s, msg);
     if (rc == 0) e = hipMemcpy2DAsync(A, lda * 8, T, ld * 8, n * 8, n, hipMemcpyDeviceToDevice, s);
     if (rc == 0 && e == hipSuccess) e = hipStreamSynchronize(s);
   }
-  (void)hipFree(T);
-  if (e != hipSuccess) return herr(e, "spd_inverse", msg);
+  if (e != hipSuccess) return hip_err(e, "spd_inverse", msg);
   return rc;
 }
 
 void vc_release_x() {
-  if (g_vc.Kown) (void)hipFree(g_vc.Kown);
-  g_vc.Kown = nullptr;
-  dfree(g_vc.H);
-  dfree(g_vc.Wd);
-  dfree(g_vc.Xd);
-  dfree(g_vc.Yd);
-  dfree(g_vc.partial);
+  g_vc.Kown.release(); g_vc.H.release(); g_vc.Wd.release(); g_vc.Xd.release(); g_vc.Yd.release(); g_vc.partial.release();
   g_vc.K.clear();
   g_vc.ready = false;
   for (auto &c : g_vc.cache) c.x.clear();
@@ -268,7 +207,7 @@ int vc_setup_x(long n, int n_vc, const double *const *K, long ldk, bool device, 
   vc_release_x();
   gemm_aux_init();
   if (!g_vc.ev[0])
-    for (auto &e : g_vc.ev) VCCHK(hipEventCreate(&e));
+    for (auto &e : g_vc.ev) TU_CHK(hipEventCreate(&e));
   g_vc.n = n;
   g_vc.nvc = n_vc;
   g_vc.c = c;
@@ -282,17 +221,18 @@ int vc_setup_x(long n, int n_vc, const double *const *K, long ldk, bool device, 
     for (int l = 0; l < n_vc; ++l) g_vc.K.push_back(K[l]);
   } else {
     g_vc.ldk = g_vc.ld;
-    if ((rc = dalloc(&g_vc.Kown, nn * n_vc, msg))) return rc;
+    if ((rc = g_vc.Kown.reserve(nn * n_vc * 8, "vc", msg))) return rc;
     for (int l = 0; l < n_vc; ++l) {
-      VCCHK(hipMemcpy2D(g_vc.Kown + l * nn, g_vc.ld * 8, K[l], ldk * 8, n * 8, n, hipMemcpyHostToDevice));
-      g_vc.K.push_back(g_vc.Kown + l * nn);
+      TU_CHK(hipMemcpy2D(g_vc.Kown.as<double>() + l * nn, g_vc.ld * 8, K[l], ldk * 8, n * 8, n, hipMemcpyHostToDevice));
+      g_vc.K.push_back(g_vc.Kown.as<double>() + l * nn);
     }
   }
   const int xw = std::max(2 * c, VC_MAX_VEC);
-  if ((rc = dalloc(&g_vc.H, nn, msg)) || (rc = dalloc(&g_vc.Wd, (size_t)n * c, msg)) || (rc = dalloc(&g_vc.Xd, (size_t)n * xw, msg)) ||
-      (rc = dalloc(&g_vc.Yd, (size_t)n * xw, msg)) || (rc = dalloc(&g_vc.partial, (size_t)VC_TRACE_BLOCKS * VC_MAX_PAIRS, msg)))
+  if ((rc = g_vc.H.reserve(nn * 8, "vc", msg)) || (rc = g_vc.Wd.reserve((size_t)n * c * 8, "vc", msg)) ||
+      (rc = g_vc.Xd.reserve((size_t)n * xw * 8, "vc", msg)) || (rc = g_vc.Yd.reserve((size_t)n * xw * 8, "vc", msg)) ||
+      (rc = g_vc.partial.reserve((size_t)VC_TRACE_BLOCKS * VC_MAX_PAIRS * 8, "vc", msg)))
     return rc;
-  VCCHK(hipMemcpy(g_vc.Wd, W, (size_t)n * c * 8, hipMemcpyHostToDevice));
+  TU_CHK(hipMemcpy(g_vc.Wd.p, W, (size_t)n * c * 8, hipMemcpyHostToDevice));
   // v_traceG: the mean diagonal of each (CenterMatrix(G)-centred) kinship, src/gemma.cpp:2341-2351
   g_vc.traceG.clear();
   for (int l = 0; l < n_vc; ++l) {
@@ -309,25 +249,23 @@ int vc_setup_x(long n, int n_vc, const double *const *K, long ldk, bool device, 
 }
 
 int vc_he_x(VcResult &R, std::string &msg) {
+  double *const Wd = g_vc.Wd.as<double>(), *const Xd = g_vc.Xd.as<double>(), *const Yd = g_vc.Yd.as<double>();
   const long n = g_vc.n, ld = g_vc.ld;
   const int nvc = g_vc.nvc, c = g_vc.c;
   const double r = (double)n / (double)(n - c);
   int rc;
   // K_scale: the W-centred, mean-diagonal-scaled copies (released at the end of the fit)
-  double *Ks = nullptr;
+  ScopedBuf Ksb;
   const size_t nn = (size_t)n * ld;
-  if ((rc = dalloc(&Ks, nn * nvc, msg))) return rc;
-  struct Free {
-    double *&p;
-    ~Free() { dfree(p); }
-  } free_ks{Ks};
+  if ((rc = Ksb.reserve(nn * nvc * 8, "vc", msg))) return rc;
+  double *Ks = Ksb.as<double>();
   std::vector<const double *> Kt;
   std::vector<double> traceG_new;
   // Q = W (W^T W)^-1
   std::vector<double> WtW(c * c), Q((size_t)n * c, 0.0);
   for (int a = 0; a < c; ++a)
     for (int e = 0; e < c; ++e) WtW[a * c + e] = dot(&g_vc.W[a], &g_vc.W[e], n, c, c);
-  if (rank_deficient(WtW, c) || !small_inverse(WtW, c)) { // no HE fit, no REML start
+  if (rank_deficient(WtW, c) || small_inverse(WtW, c) == SMALL_INVERSE_ZERO_PIVOT) { // no HE fit, no REML start
     msg = "vc: W^T W is singular";
     return GEMMA_HIP_EINVAL;
   }
@@ -336,12 +274,12 @@ int vc_he_x(VcResult &R, std::string &msg) {
       for (int e = 0; e < c; ++e) Q[i * c + a] += g_vc.W[i * c + e] * WtW[e * c + a];
   for (int l = 0; l < nvc; ++l) {
     double *T = Ks + l * nn;
-    VCCHK(hipMemcpy2DAsync(T, ld * 8, g_vc.K[l], g_vc.ldk * 8, n * 8, n, hipMemcpyDeviceToDevice, S0));
+    TU_CHK(hipMemcpy2DAsync(T, ld * 8, g_vc.K[l], g_vc.ldk * 8, n * 8, n, hipMemcpyDeviceToDevice, S0));
     // CenterMatrix(G, W) = G - Q (GW)^T - GW Q^T + Q (W^T G W) Q^T = G - [Q B] [B Q]^T, B = GW - Q (W^T G W) / 2
-    VCCHK(launch_dgemm('N', 'N', n, c, n, 1.0, T, ld, g_vc.Wd, c, 0.0, g_vc.Yd, c, false, false, S0));
+    TU_CHK(launch_dgemm('N', 'N', n, c, n, 1.0, T, ld, Wd, c, 0.0, Yd, c, false, false, S0));
     std::vector<double> GW((size_t)n * c), M(c * c), LR((size_t)n * 4 * c);
-    VCCHK(hipMemcpyAsync(GW.data(), g_vc.Yd, GW.size() * 8, hipMemcpyDeviceToHost, S0));
-    VCCHK(hipStreamSynchronize(S0));
+    TU_CHK(hipMemcpyAsync(GW.data(), Yd, GW.size() * 8, hipMemcpyDeviceToHost, S0));
+    TU_CHK(hipStreamSynchronize(S0));
     for (int a = 0; a < c; ++a)
       for (int e = 0; e < c; ++e) M[a * c + e] = dot(&g_vc.W[a], &GW[e], n, c, c);
     for (long i = 0; i < n; ++i)
@@ -353,9 +291,9 @@ int vc_he_x(VcResult &R, std::string &msg) {
         LR[(size_t)n * 2 * c + i * 2 * c + a] = b;             // R = [B Q]
         LR[(size_t)n * 2 * c + i * 2 * c + c + a] = Q[i * c + a];
       }
-    VCCHK(hipMemcpyAsync(g_vc.Xd, LR.data(), (size_t)n * 2 * c * 8, hipMemcpyHostToDevice, S0));
-    VCCHK(hipMemcpyAsync(g_vc.Yd, LR.data() + (size_t)n * 2 * c, (size_t)n * 2 * c * 8, hipMemcpyHostToDevice, S0));
-    VCCHK(launch_dgemm('N', 'T', n, n, 2 * c, -1.0, g_vc.Xd, 2 * c, g_vc.Yd, 2 * c, 1.0, T, ld, false, false, S0));
+    TU_CHK(hipMemcpyAsync(Xd, LR.data(), (size_t)n * 2 * c * 8, hipMemcpyHostToDevice, S0));
+    TU_CHK(hipMemcpyAsync(Yd, LR.data() + (size_t)n * 2 * c, (size_t)n * 2 * c * 8, hipMemcpyHostToDevice, S0));
+    TU_CHK(launch_dgemm('N', 'T', n, n, 2 * c, -1.0, Xd, 2 * c, Yd, 2 * c, 1.0, T, ld, false, false, S0));
     // ScaleMatrix: mean diagonal -> 1
     std::vector<double> dg;
     if ((rc = diagonal(T, ld, dg, msg))) return rc;
@@ -419,7 +357,7 @@ int vc_he_x(VcResult &R, std::string &msg) {
   for (int i = 0, p = 0; i < nvc; ++i)
     for (int j = i; j < nvc; ++j, ++p) S[i * nvc + j] = S[j * nvc + i] = tr[p] - r * (double)n;
   std::vector<double> Si = S;
-  if (!small_inverse(Si, nvc)) {
+  if (small_inverse(Si, nvc) == SMALL_INVERSE_ZERO_PIVOT) {
     msg = "vc: the Haseman-Elston matrix S is singular";
     return GEMMA_HIP_ERUNTIME;
   }
@@ -471,6 +409,7 @@ namespace {
 
 // UpdateParam + LogRL_dev12 at x (log sigma2, or sigma2 with noconstrain): f = dev1, J = dev2 (the AI matrix)
 int reml_eval(const std::vector<double> &x, bool noconstrain, std::vector<double> &f, std::vector<double> &J, std::string &msg) {
+  double *const H = g_vc.H.as<double>(), *const Wd = g_vc.Wd.as<double>(), *const Xd = g_vc.Xd.as<double>(), *const Yd = g_vc.Yd.as<double>();
   for (auto &cc : g_vc.cache)
     if (!cc.x.empty() && cc.x == x) {
       f = cc.f;
@@ -482,14 +421,14 @@ int reml_eval(const std::vector<double> &x, bool noconstrain, std::vector<double
   std::vector<double> sig(m);
   for (int i = 0; i < m; ++i) sig[i] = noconstrain ? x[i] : std::exp(x[i]);
   int rc;
-  VCCHK(hipEventRecord(g_vc.ev[0], S0));
-  if ((rc = assemble(g_vc.K, g_vc.ldk, std::vector<double>(sig.begin(), sig.begin() + nvc), sig[nvc], g_vc.H, ld, msg))) return rc;
-  VCCHK(hipEventRecord(g_vc.ev[1], S0));
+  TU_CHK(hipEventRecord(g_vc.ev[0], S0));
+  if ((rc = assemble(g_vc.K, g_vc.ldk, std::vector<double>(sig.begin(), sig.begin() + nvc), sig[nvc], H, ld, msg))) return rc;
+  TU_CHK(hipEventRecord(g_vc.ev[1], S0));
   double logdet = 0.0;
   long bad = -1;
   ++g_vc.evals;
   ++g_vc.invs;
-  rc = spd_inverse_device(g_vc.H, n, ld, &logdet, &bad, g_vc.spd, S0, msg);
+  rc = spd_inverse_device(H, n, ld, &logdet, &bad, g_vc.spd, S0, msg);
   if (rc) {
     if (rc == GEMMA_HIP_ENOTPD) {
       char b[256];
@@ -500,52 +439,52 @@ int reml_eval(const std::vector<double> &x, bool noconstrain, std::vector<double
     }
     return rc;
   }
-  VCCHK(hipEventRecord(g_vc.ev[2], S0));
+  TU_CHK(hipEventRecord(g_vc.ev[2], S0));
   // P = H^-1 - H^-1 W (W^T H^-1 W)^-1 W^T H^-1: HiW on the device, the c x c inverse on the host, a rank-c update on the GEMM
-  VCCHK(launch_dgemm('N', 'N', n, c, n, 1.0, g_vc.H, ld, g_vc.Wd, c, 0.0, g_vc.Yd, c, false, false, S0));
+  TU_CHK(launch_dgemm('N', 'N', n, c, n, 1.0, H, ld, Wd, c, 0.0, Yd, c, false, false, S0));
   std::vector<double> HiW((size_t)n * c), WHW(c * c), Qh((size_t)n * c, 0.0);
-  VCCHK(hipMemcpyAsync(HiW.data(), g_vc.Yd, HiW.size() * 8, hipMemcpyDeviceToHost, S0));
-  VCCHK(hipStreamSynchronize(S0));
+  TU_CHK(hipMemcpyAsync(HiW.data(), Yd, HiW.size() * 8, hipMemcpyDeviceToHost, S0));
+  TU_CHK(hipStreamSynchronize(S0));
   for (int a = 0; a < c; ++a)
     for (int e = 0; e < c; ++e) WHW[a * c + e] = dot(&g_vc.W[a], &HiW[e], n, c, c);
-  if (!small_inverse(WHW, c)) {
+  if (small_inverse(WHW, c) == SMALL_INVERSE_ZERO_PIVOT) {
     msg = "vc: W^T H^-1 W is singular";
     return GEMMA_HIP_ERUNTIME;
   }
   for (long i = 0; i < n; ++i)
     for (int a = 0; a < c; ++a)
       for (int e = 0; e < c; ++e) Qh[i * c + a] += HiW[i * c + e] * WHW[e * c + a];
-  VCCHK(hipMemcpyAsync(g_vc.Xd, Qh.data(), Qh.size() * 8, hipMemcpyHostToDevice, S0));
-  VCCHK(launch_dgemm('N', 'T', n, n, c, -1.0, g_vc.Xd, c, g_vc.Yd, c, 1.0, g_vc.H, ld, false, false, S0));
-  VCCHK(hipEventRecord(g_vc.ev[3], S0));
+  TU_CHK(hipMemcpyAsync(Xd, Qh.data(), Qh.size() * 8, hipMemcpyHostToDevice, S0));
+  TU_CHK(launch_dgemm('N', 'T', n, n, c, -1.0, Xd, c, Yd, c, 1.0, H, ld, false, false, S0));
+  TU_CHK(hipEventRecord(g_vc.ev[3], S0));
   // Py, K_i Py, P [K_i Py]
   std::vector<double> Py, KPy((size_t)n * m), PKPy, out;
-  if ((rc = matvec(g_vc.H, ld, g_vc.y, 1, Py, msg))) return rc;
+  if ((rc = matvec(H, ld, g_vc.y, 1, Py, msg))) return rc;
   for (int i = 0; i < nvc; ++i) {
     if ((rc = matvec(g_vc.K[i], g_vc.ldk, Py, 1, out, msg))) return rc;
     for (long k = 0; k < n; ++k) KPy[k * m + i] = out[k];
   }
   for (long k = 0; k < n; ++k) KPy[k * m + nvc] = Py[k];
-  if ((rc = matvec(g_vc.H, ld, KPy, m, PKPy, msg))) return rc;
+  if ((rc = matvec(H, ld, KPy, m, PKPy, msg))) return rc;
   for (auto &d : KPy)
     if (std::isnan(d)) d = 0.0;
   for (auto &d : PKPy)
     if (std::isnan(d)) d = 0.0;
-  VCCHK(hipEventRecord(g_vc.ev[4], S0));
+  TU_CHK(hipEventRecord(g_vc.ev[4], S0));
   // tr(P K_i), tr(P)
   std::vector<std::pair<const double *, long>> pa, pb;
   for (int i = 0; i < nvc; ++i) {
-    pa.push_back({g_vc.H, ld});
+    pa.push_back({H, ld});
     pb.push_back({g_vc.K[i], g_vc.ldk});
   }
   std::vector<double> tr, dg;
   if ((rc = traces(pa, pb, tr, msg))) return rc;
-  if ((rc = diagonal(g_vc.H, ld, dg, msg))) return rc;
+  if ((rc = diagonal(H, ld, dg, msg))) return rc;
   double trP = 0.0;
   for (double v : dg) trP += v;
   tr.push_back(trP);
-  VCCHK(hipEventRecord(g_vc.ev[5], S0));
-  VCCHK(hipEventSynchronize(g_vc.ev[5]));
+  TU_CHK(hipEventRecord(g_vc.ev[5], S0));
+  TU_CHK(hipEventSynchronize(g_vc.ev[5]));
   for (int k = 0; k < 5; ++k) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, g_vc.ev[k], g_vc.ev[k + 1]) == hipSuccess) g_vc.t[k] += ms * 1e-3;
@@ -620,7 +559,7 @@ int vc_reml_x(bool noconstrain, VcResult &R, std::vector<double> *iters, std::st
   std::vector<double> f, J;
   if ((rc = reml_eval(solver.x, noconstrain, f, J, msg))) return rc;
   std::vector<double> Hi = J;
-  if (!small_inverse(Hi, m)) {
+  if (small_inverse(Hi, m) == SMALL_INVERSE_ZERO_PIVOT) {
     msg = "vc: the average-information matrix is singular at the solution";
     return GEMMA_HIP_ERUNTIME;
   }
