@@ -32,6 +32,7 @@ SYMBOLS = [
     "gemma_hip_prdt_end", "gemma_hip_prdt_kin",
     "gemma_hip_mqs_begin", "gemma_hip_mqs_add", "gemma_hip_mqs_add_d", "gemma_hip_mqs_end", "gemma_hip_mqs_get",
     "gemma_hip_mqs_S", "gemma_hip_mqs_S_d", "gemma_hip_mqs_release",
+    "gemma_hip_cor_begin", "gemma_hip_cor_block", "gemma_hip_cor_block_d", "gemma_hip_cor_release",
 ]
 COMM_ID_BYTES = 128
 
@@ -219,6 +220,10 @@ def lib():
     L.gemma_hip_mqs_S.argtypes = [sz, sz, dp, dp, sz, sz, dp]
     L.gemma_hip_mqs_S_d.argtypes = [sz, sz, dp, dp, sz, sz, dp, vp]
     L.gemma_hip_mqs_release.argtypes = []
+    L.gemma_hip_cor_begin.argtypes = [sz, vp]
+    L.gemma_hip_cor_block.argtypes = [ci, vp, sz, sz, sz, vp, dp, dp]
+    L.gemma_hip_cor_block_d.argtypes = [ci, vp, sz, sz, sz, vp, dp, dp, vp]
+    L.gemma_hip_cor_release.argtypes = []
     for s in SYMBOLS:
         getattr(L, s)  # AttributeError if the library does not export what the header declares
     _lib = L

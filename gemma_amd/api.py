@@ -1187,6 +1187,138 @@ class MQS:
         L.check(L.lib().gemma_hip_mqs_release(), "MQS.Release")
 
 
+# ----------------------------------------------------------------------------- windowed SNP correlation (-calccor)
+def _sci6(v):
+    """`scientific << setprecision(6)` of an ostream"""
+    v = float(v)
+    if v != v:
+        return "-nan" if np.signbit(v) else "nan"
+    return "%.6e" % v
+
+
+class VARCOV:
+    """VARCOV (src/varcov.cpp) on the device, called where src/gemma.cpp:2046-2059 calls it (-calccor, a_mode 71):
+
+        v = VARCOV(indicator_idv, indicator_snp, chr, cM, bp, window_bp=300)   # chr / cM / bp of ALL SNPs, as snpInfo holds them
+        n_nb = v.CalcNB()                        # per SNP (0 where indicator_snp == 0)
+        var, cor, off = v.AnalyzePlink(bed_rows) # rows of the SNPs with indicator_snp != 0, in file order
+        v.WriteCov(path, snpinfo)                # prefix.cor.txt
+
+    var[j], cor[off[j]:off[j + 1]] belong to analysed SNP j.  The window of a SNP is exactly CalcNB's n_nb (the
+    reference's sliding buffer can carry leftover rows on input that is not sorted by position; on sorted input the two agree)."""
+
+    def __init__(self, indicator_idv, indicator_snp, chr, cM, bp, window_cm=0, window_bp=0, window_ns=0):
+        self.indicator_idv = np.ascontiguousarray(indicator_idv, dtype=np.int32)
+        self.indicator_snp = np.ascontiguousarray(indicator_snp, dtype=np.int32)
+        self.chr = [str(c) for c in chr]
+        self.cM = np.asarray(cM, dtype=np.float64)
+        self.bp = np.asarray(bp, dtype=np.int64)
+        ns = self.indicator_snp.size
+        if len(self.chr) != ns or self.cM.shape != (ns,) or self.bp.shape != (ns,):
+            raise ValueError("chr, cM and bp take one entry per SNP of indicator_snp")
+        self.window_cm, self.window_bp, self.window_ns = float(window_cm), int(window_bp), int(window_ns)
+        if self.window_cm == 0 and self.window_bp == 0 and self.window_ns == 0:
+            self.window_bp = 1000000  # src/param.cpp:629-630
+        self.ni_test = int((self.indicator_idv != 0).sum())
+        self.n_nb = None
+        self.var = self.cor = self.off = None
+
+    def CalcNB(self):
+        """VARCOV::CalcNB, src/varcov.cpp:168-217, branch for branch"""
+        ind, chr_, cM, bp = self.indicator_snp, self.chr, self.cM, self.bp
+        ns = ind.size
+        w_cm, w_bp, w_ns = self.window_cm, self.window_bp, self.window_ns
+        out = np.zeros(ns, dtype=np.int32)
+        for t in range(ns):
+            if ind[t] == 0:
+                continue
+            if chr_[t] == "-9" or (cM[t] == -9 and w_cm != 0) or (bp[t] == -9 and w_bp != 0):
+                continue
+            if t == ns - 1:
+                continue
+            t2, n_nb = t + 1, 0
+            while t2 < ns and chr_[t2] == chr_[t] and ind[t2] == 0:
+                t2 += 1
+            while (t2 < ns and chr_[t2] == chr_[t] and (cM[t2] - cM[t] < w_cm or w_cm == 0) and
+                   (bp[t2] - bp[t] < w_bp or w_bp == 0) and (n_nb < w_ns or w_ns == 0)):
+                t2 += 1
+                n_nb += 1
+                while t2 < ns and chr_[t2] == chr_[t] and ind[t2] == 0:
+                    t2 += 1
+            out[t] = n_nb
+        self.n_nb = out
+        return out
+
+    def _analyze(self, geno, geno_kind, batch):
+        if self.n_nb is None:
+            self.CalcNB()
+        nb = np.ascontiguousarray(self.n_nb[self.indicator_snp != 0])  # analysed SNPs only: the rows of geno
+        l = nb.size
+        if geno.shape[0] != l:
+            raise ValueError("geno holds %d rows, indicator_snp keeps %d SNPs" % (geno.shape[0], l))
+        off = np.zeros(l + 1, dtype=np.int64)
+        np.cumsum(nb, out=off[1:])
+        lib = L.lib()
+        L.check(lib.gemma_hip_cor_begin(self.indicator_idv.size, _ptr(self.indicator_idv)), "VARCOV.begin")
+        dev = _is_torch(geno)
+        if dev:
+            import torch
+            var = torch.empty(l, dtype=torch.float64, device=geno.device)
+            cor = torch.empty(max(int(off[-1]), 1), dtype=torch.float64, device=geno.device)
+            nb_t = torch.as_tensor(nb).to(geno.device)
+        else:
+            geno = np.ascontiguousarray(geno)
+            var, cor = np.zeros(l), np.zeros(max(int(off[-1]), 1))
+        for s0 in range(0, l, batch):  # batch outputs and the halo their windows reach into (re-read with the next block)
+            s1 = min(l, s0 + batch)
+            l_in = int(max(s1, (np.arange(s0, s1) + nb[s0:s1]).max() + 1)) - s0
+            blk = geno[s0:s0 + l_in]
+            if dev:
+                L.check(lib.gemma_hip_cor_block_d(geno_kind, C.c_void_p(blk.data_ptr()), l_in, _tld(geno), s1 - s0,
+                                                  C.c_void_p(nb_t[s0:s1].data_ptr()), C.c_void_p(var[s0:s1].data_ptr()),
+                                                  C.c_void_p(cor[int(off[s0]):].data_ptr()), _stream()), "VARCOV.block")
+            else:
+                L.check(lib.gemma_hip_cor_block(geno_kind, _ptr(blk), l_in, blk.strides[0] // blk.itemsize, s1 - s0, _ptr(nb[s0:s1]),
+                                                _ptr(var[s0:s1]), _ptr(cor[int(off[s0]):])), "VARCOV.block")
+        if dev:
+            import torch
+            torch.cuda.synchronize()
+        self.var, self.cor, self.off = var, cor[:int(off[-1])], off
+        return self.var, self.cor, self.off
+
+    def AnalyzePlink(self, bed_rows, batch=LMM_BATCH_SIZE):
+        """VARCOV::AnalyzePlink, src/varcov.cpp:348-446: bed_rows = .bed rows over all ni_total individuals."""
+        if not _is_torch(bed_rows):
+            bed_rows = np.asarray(bed_rows, dtype=np.uint8)
+        return self._analyze(bed_rows, L.GENO_PLINK_2BIT, batch)
+
+    def AnalyzeBimbam(self, G, batch=LMM_BATCH_SIZE):
+        """VARCOV::AnalyzeBimbam, src/varcov.cpp:249-346: G SNP-major over all individuals, NaN = NA."""
+        if not _is_torch(G):
+            G = np.asarray(G, dtype=np.float64)
+        return self._analyze(G, L.GENO_F64_SNP_MAJOR, batch)
+
+    def WriteCov(self, path, snpinfo, var=None, cor=None, off=None):
+        """VARCOV::WriteCov, src/varcov.cpp:74-145.  snpinfo: one (chr, rs, ps, n_miss, n_idv, a_minor, a_major, maf) per analysed
+        SNP; var / cor / off default to the last Analyze* call."""
+        var = self.var if var is None else var
+        cor = self.cor if cor is None else cor
+        off = self.off if off is None else off
+        if _is_torch(var):
+            var, cor = var.cpu().numpy(), cor.cpu().numpy()
+        with open(path, "w") as f:
+            f.write("chr\trs\tps\tn_mis\tn_obs\tallele1\tallele0\taf\twindow_size\tvar\tcor\n")
+            for j, (chr_, rs, ps, n_miss, n_idv, a1, a0, maf) in enumerate(snpinfo):
+                w = int(off[j + 1] - off[j])
+                f.write("%s\t%s\t%d\t%d\t%d\t%s\t%s\t%.3f\t%d\t%s\t" % (chr_, rs, ps, n_miss, n_idv, a1, a0, maf, w, _sci6(var[j])))
+                f.write(",".join(_sci6(v) for v in cor[off[j]:off[j + 1]]) if w else "NA")
+                f.write("\n")
+
+    @staticmethod
+    def Release():
+        L.check(L.lib().gemma_hip_cor_release(), "VARCOV.Release")
+
+
 _HEADER_SETS = dict(  # ReadHeader_io, src/gemma_io.cpp:2367-2427 (the a1 / a0 sets as the reference builds them: one name short each)
     rs=("rs", "RS", "snp", "SNP", "snps", "SNPS", "snpid", "SNPID", "rsid", "RSID", "MarkerName"),
     chr=("chr", "CHR"), pos=("ps", "PS", "pos", "POS", "base_position", "BASE_POSITION", "bp", "BP"), cm=("cm", "CM"),

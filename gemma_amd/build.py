@@ -14,11 +14,12 @@ UNITS = {
                       # the stages of the C ABI: textual parts of gemma_hip.hip (one translation unit around g_ctx)
                       "abi_kinship.inc.h", "abi_eigen_qc.inc.h", "abi_lmm_stage.inc.h", "abi_utx.inc.h", "abi_lmm_batch.inc.h",
                       "abi_mvlmm.inc.h", "abi_gxe_lm.inc.h", "abi_kept_comm.inc.h", "abi_vc.inc.h", "vc_tu.h", "abi_prdt.inc.h", "prdt_tu.h",
-                      "abi_mqs.inc.h", "mqs_tu.h"],
+                      "abi_mqs.inc.h", "mqs_tu.h", "abi_cor.inc.h", "cor_tu.h"],
     "eigh_tu.hip": ["dgemm_mfma.hip.h", "eigh.hip.h", "eigh2.hip.h", "eigh_tu.h", "tu_common.h"],  # the eigensolver: its own object file
     "vc_tu.hip": ["dgemm_mfma.hip.h", "spd_inv.hip.h", "vc.hip.h", "vc_tu.h", "tu_common.h", "host_linalg.h", "../../include/gemma_vc_hybrid.hpp"],  # -vc 1 / -vc 2
     "prdt_tu.hip": ["dgemm_mfma.hip.h", "geno_mv.hip.h", "dev_common.hip.h", "eigh_tu.h", "prdt_tu.h", "tu_common.h"],  # -bslmm 2 / -predict: genotype matrix-vector passes
     "mqs_tu.hip": ["dgemm_mfma.hip.h", "mqs.hip.h", "dev_common.hip.h", "mqs_tu.h", "tu_common.h", "host_linalg.h"],  # -gs / -vc 1 -beta: MQS kinships, S and its jackknife
+    "cor_tu.hip": ["dgemm_mfma.hip.h", "cor.hip.h", "dev_common.hip.h", "cor_tu.h", "tu_common.h"],  # -calccor: banded SNP correlation, int8 band kernel and fp64 panels
     "mvlmm_kernels.hip": ["mvlmm.hip.h", "mvlmm_kernels.hip.h"],
     "mvlmm_kernels_wide.hip": ["mvlmm.hip.h", "mvlmm_kernels.hip.h"],
     "mvlmm_kernels_rt.hip": ["mvlmm.hip.h", "mvlmm_kernels.hip.h"],  # the run-time (d, c) instance
@@ -26,7 +27,7 @@ UNITS = {
     "mvlmm_kernels_d7.hip": ["mvlmm.hip.h", "mvlmm_kernels.hip.h"],  # seven phenotypes (one wavefront per workgroup)
     "mvlmm_kernels_d8.hip": ["mvlmm.hip.h", "mvlmm_kernels.hip.h"],  # eight phenotypes, one covariate
 }
-PUBLIC_HEADER_USERS = ("gemma_hip.hip", "eigh_tu.hip", "vc_tu.hip", "prdt_tu.hip", "mqs_tu.hip")
+PUBLIC_HEADER_USERS = ("gemma_hip.hip", "eigh_tu.hip", "vc_tu.hip", "prdt_tu.hip", "mqs_tu.hip", "cor_tu.hip")
 SOURCES = list(UNITS)
 HEADERS = sorted({h for hs in UNITS.values() for h in hs})
 

@@ -18,6 +18,7 @@
 #include "vc_tu.h"
 #include "prdt_tu.h"
 #include "mqs_tu.h"
+#include "cor_tu.h"
 #include "ingest.hip.h"
 #include "lm_assoc.hip.h"
 #include "lmm_assoc.hip.h"
@@ -423,6 +424,7 @@ extern "C" void gemma_hip_shutdown(void) {
   vc_tu_shutdown();
   prdt_tu_shutdown();
   mqs_tu_shutdown();
+  cor_tu_shutdown();
   g_ctx.inited = false;
 }
 
@@ -526,3 +528,4 @@ extern "C" int gemma_hip_dgemm(char ta, char tb, size_t M, size_t N, size_t K, d
 #include "abi_vc.inc.h"
 #include "abi_prdt.inc.h"
 #include "abi_mqs.inc.h"
+#include "abi_cor.inc.h"

@@ -1,4 +1,4 @@
-// Host-side plumbing shared by gemma_hip.hip and the separately compiled feature units (eigh_tu, vc_tu, prdt_tu, mqs_tu): the owning
+// Host-side plumbing shared by gemma_hip.hip and the separately compiled feature units (eigh_tu, vc_tu, prdt_tu, mqs_tu, cor_tu): the owning
 // device buffer, HIP error reporting into a message string, and the staging copy of a block of host rows.
 #pragma once
 
@@ -11,7 +11,7 @@
 
 namespace gemma_hip {
 
-// A device allocation that grows and never shrinks.  No destructor: the states that hold these (g_ctx, g_rg, g_pd, g_vc, g_mqs) have
+// A device allocation that grows and never shrinks.  No destructor: the states that hold these (g_ctx, g_rg, g_pd, g_vc, g_mqs, g_cor) have
 // static lifetime, and a hipFree from a static destructor would run after the runtime is gone.  Every owner releases member by
 // member from its shutdown; a local that has to be freed on every return path is a ScopedBuf.
 struct DevBuf {

@@ -558,6 +558,33 @@ int gemma_hip_mqs_S(size_t n, size_t n_vc, const double *A, const double *K, siz
 int gemma_hip_mqs_S_d(size_t n, size_t n_vc, const double *A_d, const double *K_d, size_t ld, size_t n_cvt, double *S, void *stream);
 int gemma_hip_mqs_release(void);
 
+/* ---- Windowed SNP correlation: -calccor (a_mode 71), the prefix.cor.txt that -cor reads back -------------------------------------- */
+/* VARCOV::AnalyzePlink / AnalyzeBimbam (src/varcov.cpp:249-446) with Calc_Cor (:220-238), called where src/gemma.cpp:2046-2059 calls
+ * them.  With c the called mask, g the genotype and mu = sum g / sum c over the ANALYSED individuals, the column of a SNP is
+ * x = c (g - mu) (Plink_ReadOneSNP / Bimbam_ReadOneSNP, src/gemma_io.cpp:1069-1184, and the centring at src/varcov.cpp:308 / :408);
+ * var_t = x_t.x_t / n and cor_{t,k} = x_t.x_{t+k} / sqrt((x_t.x_t)(x_{t+k}.x_{t+k})) for k = 1 .. n_nb[t], counting analysed SNPs.
+ * cor_begin (replaces the set-up of src/varcov.cpp:257-276 / :357-376): indicator_idv over ni_total individuals (NULL: all
+ * analysed); n = the number of non-zero entries.
+ * cor_block (replaces the loop over t with its sliding X_mat, src/varcov.cpp:281-332 / :381-432): geno holds l_in >= l_out
+ * consecutive analysed SNPs (indicator_snp != 0) as they lie in the file (GEMMA_GENO_PLINK_2BIT, ld bytes per row;
+ * GEMMA_GENO_F64_SNP_MAJOR, ld doubles per row, NaN = missing); rows l_out .. l_in - 1 are the halo the windows of the first l_out
+ * reach into.  n_nb[l_out] = CalcNB's window sizes (src/varcov.cpp:168-217); var[l_out]; cor[sum n_nb], the windows one after the
+ * other: cor_{t,k} at (sum_{u < t} n_nb[u]) + k - 1 (may be NULL when every window is empty).  EINVAL when some t + n_nb[t] >= l_in,
+ * when n_nb[t] < 0, or before cor_begin.  The window of SNP t is exactly n_nb[t]: leftover rows of the reference's sliding buffer
+ *  are not reproduced.
+ * PLINK rows take the exact integer route: four int8 products per pair on the matrix units, combined in int64 before the one
+ * division and square root (n <= 2^20 analysed individuals; EINVAL above); the result does not depend on how the SNPs are cut into
+ * blocks.  fp64 rows take the fp64 matrix units.  A SNP without a called genotype gives NaN (var and every cor with it), a
+ * monomorphic one var = 0 and NaN correlations, as the reference's 0 / 0 does.  No atomics: two runs agree bit for bit.
+ * _d: geno, n_nb, var and cor on the device, on `stream`, which is synchronised once per block (the windows come to the host).
+ * cor_release (replaces the frees of src/varcov.cpp:340-345 / :440-445) returns all device memory of the state. */
+int gemma_hip_cor_begin(size_t ni_total, const int *indicator_idv);
+int gemma_hip_cor_block(int geno_kind, const void *geno, size_t l_in, size_t ld, size_t l_out, const int *n_nb, double *var,
+                        double *cor);
+int gemma_hip_cor_block_d(int geno_kind, const void *geno_d, size_t l_in, size_t ld, size_t l_out, const int *n_nb_d, double *var_d,
+                          double *cor_d, void *stream);
+int gemma_hip_cor_release(void);
+
 #ifdef __cplusplus
 }
 #endif

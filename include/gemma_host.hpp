@@ -1216,5 +1216,27 @@ private:
   size_t rows_seen = 0;
 };
 
+// class VARCOV, src/varcov.h: -calccor (a_mode 71).  The members CopyFromParam (src/varcov.cpp:45-67) fills; CalcNB, WriteCov and the
+// two block feeders are defined in gemma_io_host.hpp.  Called where src/gemma.cpp:2046-2059 calls the reference's class.
+class VARCOV {
+public:
+  std::string file_out, path_out, file_geno, file_bfile;
+  int d_pace = 100000;
+  double window_cm = 0;
+  size_t window_bp = 0, window_ns = 0;
+  std::vector<int> indicator_idv, indicator_snp;
+  std::vector<SNPINFO> snpInfo;
+  double time_opt = 0;
+  bool error = false; // set by AnalyzePlink / AnalyzeBimbam when a genotype file cannot be opened or ends early (they return void)
+
+  void CalcNB(std::vector<SNPINFO> &snpInfo_sort);
+  void WriteCov(const int flag, const std::vector<SNPINFO> &snpInfo_sub, const std::vector<std::vector<double>> &Cov_mat);
+  void AnalyzeBimbam();
+  void AnalyzePlink();
+
+private:
+  template <class ReadRows> void Analyze(int geno_kind, size_t row_len, ReadRows read_rows);
+};
+
 } // namespace gemma_amd
 #endif

@@ -17,6 +17,8 @@
 //                                           (src/gemma_io.cpp:2367-2718, :3363-3551, :3716-3870), ObtainWeight / UpdateSNP
 //                                           (src/param.cpp:2214-2296, :2420-2453), CalcVCss (src/vc.cpp:1309-1500), CalcS
 //                                           (src/param.cpp:1717-1812: the .bed rows go to gemma_hip_mqs_*), WriteMQS
+//   windowed SNP correlation (-calccor)     : VARCOV::CalcNB, WriteCov, AnalyzePlink, AnalyzeBimbam (src/varcov.cpp; the rows go to
+//                                           gemma_hip_cor_block in blocks of LMM_BATCH_SIZE outputs plus their halo)
 //
 // Nothing here computes on the host what the reference computes per SNP: counting, imputation and the filters run
 // in gemma_hip_snp_qc; the host side only tokenises text and moves bytes.  Text -> double conversion must give the
@@ -1774,6 +1776,192 @@ inline bool WriteMQS(const std::string &prefix, const Matrix *S, const Matrix *V
   if (Vq) ok = ok && WriteMatrix(Vq, prefix + ".Vq.txt");
   if (q) ok = ok && WriteVector(q, prefix + ".q.txt");
   return ok;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// windowed SNP correlation: -calccor (a_mode 71), src/gemma.cpp:2046-2059
+// ---------------------------------------------------------------------------------------------------------------
+// VARCOV::CalcNB, src/varcov.cpp:168-217, branch for branch: the number of right-hand neighbours of every analysed SNP
+inline void VARCOV::CalcNB(std::vector<SNPINFO> &snpInfo_sort) {
+  size_t t2 = 0, n_nb = 0;
+  for (size_t t = 0; t < indicator_snp.size(); ++t) {
+    if (indicator_snp[t] == 0) {
+      continue;
+    }
+
+    if (snpInfo_sort[t].chr == "-9" || (snpInfo_sort[t].cM == -9 && window_cm != 0) ||
+        (snpInfo_sort[t].base_position == -9 && window_bp != 0)) {
+      snpInfo_sort[t].n_nb = 0;
+      continue;
+    }
+
+    if (t == indicator_snp.size() - 1) {
+      snpInfo_sort[t].n_nb = 0;
+      continue;
+    }
+
+    t2 = t + 1;
+    n_nb = 0;
+
+    while (t2 < indicator_snp.size() && snpInfo_sort[t2].chr == snpInfo_sort[t].chr && indicator_snp[t2] == 0) {
+      t2++;
+    }
+
+    while (t2 < indicator_snp.size() && snpInfo_sort[t2].chr == snpInfo_sort[t].chr &&
+           (snpInfo_sort[t2].cM - snpInfo_sort[t].cM < window_cm || window_cm == 0) &&
+           (snpInfo_sort[t2].base_position - snpInfo_sort[t].base_position < (long int)window_bp || window_bp == 0) &&
+           (n_nb < window_ns || window_ns == 0)) {
+      t2++;
+      n_nb++;
+      while (t2 < indicator_snp.size() && snpInfo_sort[t2].chr == snpInfo_sort[t].chr && indicator_snp[t2] == 0) {
+        t2++;
+      }
+    }
+
+    snpInfo_sort[t].n_nb = n_nb;
+  }
+}
+
+// VARCOV::WriteCov, src/varcov.cpp:74-145: flag 0 writes the header, any other flag appends one line per row of Cov_mat
+// (row = var followed by the correlations of the window)
+inline void VARCOV::WriteCov(const int flag, const std::vector<SNPINFO> &snpInfo_sub, const std::vector<std::vector<double>> &Cov_mat) {
+  const std::string file_cov = path_out + "/" + file_out + ".cor.txt";
+  std::ofstream outfile;
+  if (flag == 0) {
+    outfile.open(file_cov.c_str(), std::ofstream::out);
+    if (!outfile) {
+      std::cout << "error writing file: " << file_cov << std::endl;
+      return;
+    }
+    outfile << "chr\trs\tps\tn_mis\tn_obs\tallele1\tallele0\taf\twindow_size\tvar\tcor" << std::endl;
+  } else {
+    outfile.open(file_cov.c_str(), std::ofstream::app);
+    if (!outfile) {
+      std::cout << "error writing file: " << file_cov << std::endl;
+      return;
+    }
+    for (size_t i = 0; i < Cov_mat.size(); i++) {
+      outfile << snpInfo_sub[i].chr << "\t" << snpInfo_sub[i].rs_number << "\t" << snpInfo_sub[i].base_position << "\t"
+              << snpInfo_sub[i].n_miss << "\t" << snpInfo_sub[i].n_idv << "\t" << snpInfo_sub[i].a_minor << "\t"
+              << snpInfo_sub[i].a_major << "\t" << std::fixed << std::setprecision(3) << snpInfo_sub[i].maf << "\t"
+              << Cov_mat[i].size() - 1 << "\t";
+      outfile << std::scientific << std::setprecision(6) << Cov_mat[i][0] << "\t";
+      if (Cov_mat[i].size() == 1) {
+        outfile << "NA";
+      } else {
+        for (size_t j = 1; j < Cov_mat[i].size(); j++) {
+          if (j == (Cov_mat[i].size() - 1)) outfile << Cov_mat[i][j];
+          else outfile << Cov_mat[i][j] << ",";
+        }
+      }
+      outfile << "\n";
+    }
+  }
+  outfile.close();
+  outfile.clear();
+}
+
+// The loop over t of src/varcov.cpp:281-338 / :381-438 in blocks: LMM_BATCH_SIZE output SNPs and the halo their windows reach
+// into go to gemma_hip_cor_block together; the halo rows are read again with the next block, nothing is kept across calls.
+// read_rows(first, count, dst) fetches the rows of analysed SNPs first .. first + count - 1 (false: read error).
+template <class ReadRows> inline void VARCOV::Analyze(int geno_kind, size_t row_len, ReadRows read_rows) {
+  CalcNB(snpInfo);
+  std::vector<size_t> keep;
+  std::vector<int> nb;
+  for (size_t t = 0; t < indicator_snp.size(); ++t)
+    if (indicator_snp[t] != 0) {
+      keep.push_back(t);
+      nb.push_back((int)snpInfo[t].n_nb);
+    }
+  std::vector<SNPINFO> snpInfo_sub;
+  std::vector<std::vector<double>> Cov_mat;
+  WriteCov(0, snpInfo_sub, Cov_mat);
+  enforce_hip(gemma_hip_cor_begin(indicator_idv.size(), indicator_idv.data()), "VARCOV");
+  const size_t l = keep.size(), B = io_block_rows(LMM_BATCH_SIZE);
+  const size_t elem = geno_kind == GEMMA_GENO_PLINK_2BIT ? 1 : sizeof(double);
+  std::vector<unsigned char> block;
+  std::vector<double> var, cor;
+  for (size_t s0 = 0; s0 < l; s0 += B) {
+    const size_t s1 = std::min(l, s0 + B);
+    size_t last = s1 - 1, total = 0;
+    for (size_t j = s0; j < s1; ++j) {
+      last = std::max(last, j + (size_t)nb[j]);
+      total += (size_t)nb[j];
+    }
+    const size_t l_in = last + 1 - s0, l_out = s1 - s0;
+    block.resize(l_in * row_len * elem);
+    if (!read_rows(s0, l_in, block.data())) { // the records of the earlier blocks are in the file; the state is given back
+      error = true;
+      enforce_hip(gemma_hip_cor_release(), "VARCOV");
+      return;
+    }
+    var.resize(l_out);
+    cor.resize(std::max<size_t>(total, 1));
+    enforce_hip(gemma_hip_cor_block(geno_kind, block.data(), l_in, row_len, l_out, nb.data() + s0, var.data(), cor.data()), "VARCOV");
+    snpInfo_sub.clear();
+    Cov_mat.assign(l_out, std::vector<double>());
+    size_t o = 0;
+    for (size_t j = s0; j < s1; ++j) {
+      std::vector<double> &row = Cov_mat[j - s0];
+      row.push_back(var[j - s0]);
+      row.insert(row.end(), cor.begin() + (long)o, cor.begin() + (long)(o + (size_t)nb[j]));
+      o += (size_t)nb[j];
+      snpInfo_sub.push_back(snpInfo[keep[j]]);
+    }
+    WriteCov(1, snpInfo_sub, Cov_mat);
+  }
+  enforce_hip(gemma_hip_cor_release(), "VARCOV");
+}
+
+// VARCOV::AnalyzePlink, src/varcov.cpp:348-446
+inline void VARCOV::AnalyzePlink() {
+  const std::string file_bed = file_bfile + ".bed";
+  std::ifstream infile(file_bed.c_str(), std::ios::binary);
+  if (!infile) {
+    std::cout << "error reading bed file:" << file_bed << std::endl;
+    error = true;
+    return;
+  }
+  const size_t n_bit = (indicator_idv.size() + 3) / 4;
+  std::vector<size_t> pos; // file index of the j-th analysed SNP
+  for (size_t t = 0; t < indicator_snp.size(); ++t)
+    if (indicator_snp[t] != 0) pos.push_back(t);
+  Analyze(GEMMA_GENO_PLINK_2BIT, n_bit, [&](size_t first, size_t count, unsigned char *dst) {
+    size_t t_next = pos[first];
+    if (read_bed_rows(infile, indicator_snp, t_next, n_bit, dst, count) != count) {
+      std::cout << "error reading bed file:" << file_bed << " (truncated)" << std::endl;
+      return false;
+    }
+    return true;
+  });
+}
+
+// VARCOV::AnalyzeBimbam, src/varcov.cpp:249-346.  The text cannot be repositioned: every block opens the file again and lets the
+// reader drop the lines before its first row unparsed.
+inline void VARCOV::AnalyzeBimbam() {
+  const size_t ni_total = indicator_idv.size();
+  std::vector<size_t> pos;
+  for (size_t t = 0; t < indicator_snp.size(); ++t)
+    if (indicator_snp[t] != 0) pos.push_back(t);
+  Analyze(GEMMA_GENO_F64_SNP_MAJOR, ni_total, [&](size_t first, size_t count, unsigned char *dst) {
+    BimbamReader rd(file_geno, ni_total);
+    if (!rd.ok()) {
+      std::cout << "error reading genotype file:" << file_geno << std::endl;
+      return false;
+    }
+    std::vector<int> sel(indicator_snp.size(), 0);
+    for (size_t j = first; j < first + count; ++j) sel[pos[j]] = 1;
+    double *X = reinterpret_cast<double *>(dst);
+    for (size_t got = 0; got < count;) {
+      const size_t r = rd.read_block(count - got, X + got * ni_total, ni_total, nullptr, &sel);
+      if (r == 0 || r == (size_t)-1) {
+        std::cout << "error reading genotype file:" << file_geno << " (truncated)" << std::endl;
+        return false;
+      }
+      got += r;
+    }
+    return true;
+  });
 }
 
 } // namespace gemma_amd
