@@ -33,6 +33,8 @@ SYMBOLS = [
     "gemma_hip_mqs_begin", "gemma_hip_mqs_add", "gemma_hip_mqs_add_d", "gemma_hip_mqs_end", "gemma_hip_mqs_get",
     "gemma_hip_mqs_S", "gemma_hip_mqs_S_d", "gemma_hip_mqs_release",
     "gemma_hip_cor_begin", "gemma_hip_cor_block", "gemma_hip_cor_block_d", "gemma_hip_cor_release",
+    "gemma_hip_ci_begin", "gemma_hip_ci_xwz", "gemma_hip_ci_xwz_d", "gemma_hip_ci_xwz_end", "gemma_hip_ci_xtxwz",
+    "gemma_hip_ci_xtxwz_d", "gemma_hip_ci_release",
 ]
 COMM_ID_BYTES = 128
 
@@ -224,6 +226,13 @@ def lib():
     L.gemma_hip_cor_block.argtypes = [ci, vp, sz, sz, sz, vp, dp, dp]
     L.gemma_hip_cor_block_d.argtypes = [ci, vp, sz, sz, sz, vp, dp, dp, vp]
     L.gemma_hip_cor_release.argtypes = []
+    L.gemma_hip_ci_begin.argtypes = [sz, vp, sz]
+    L.gemma_hip_ci_xwz.argtypes = [ci, vp, sz, sz, vp, dp, dp, C.POINTER(sz)]
+    L.gemma_hip_ci_xwz_d.argtypes = [ci, vp, sz, sz, vp, dp, dp, C.POINTER(sz), vp]
+    L.gemma_hip_ci_xwz_end.argtypes = [dp, dp]
+    L.gemma_hip_ci_xtxwz.argtypes = [ci, vp, sz, sz, dp]
+    L.gemma_hip_ci_xtxwz_d.argtypes = [ci, vp, sz, sz, dp, vp]
+    L.gemma_hip_ci_release.argtypes = []
     for s in SYMBOLS:
         getattr(L, s)  # AttributeError if the library does not export what the header declares
     _lib = L

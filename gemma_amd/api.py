@@ -1111,7 +1111,8 @@ class MQS:
         S, Svar, ns = m.Finish()               # prefix.S.txt = S on top of Svar, ns = the per-category SNP counts of size.txt
         K0 = m.Get(0, 0)                       # the centred + scaled kinship of category 0
 
-    slot=1 fills A beside the K of a finished slot=0 pass (the second CalcS of src/gemma.cpp:2198)."""
+    slot=1 fills A beside the K of a finished slot=0 pass (the second CalcS of src/gemma.cpp:2198); slot=2 does so on top of that
+    K, which is what the reference's second CalcS computes (its PlinkKin adds to the A the first CalcS left)."""
 
     def __init__(self, indicator_idv, W, n_vc):
         self.indicator_idv = np.ascontiguousarray(indicator_idv, dtype=np.int32)
@@ -1185,6 +1186,94 @@ class MQS:
     @staticmethod
     def Release():
         L.check(L.lib().gemma_hip_mqs_release(), "MQS.Release")
+
+
+# ----------------------------------------------------------------------------- MQS confidence intervals (-ci 1, -ci 2)
+class CI:
+    """The two genotype passes of the MQS confidence intervals on the device, called where src/gemma.cpp:2400-2554 calls PlinkXwz /
+    BimbamXwz and PlinkXtXwz / BimbamXtXwz (src/vc.cpp:2225-2437, :2480-2688):
+
+        ci = CI(indicator_idv, n_vc)
+        Xz, XWz, XtXWz, n_skipped = ci.AnalyzePlink(bed_rows, cat, z, w)   # rows of the analysed SNPs in file order; w None: -ci 1
+
+    Xz, XWz: ni_test x n_vc; XtXWz: one row per SNP row; n_skipped: SNPs without a called genotype or without variance among the
+    analysed individuals (zero rows of XtXWz; the reference divides by 0 there)."""
+
+    def __init__(self, indicator_idv, n_vc):
+        self.indicator_idv = np.ascontiguousarray(indicator_idv, dtype=np.int32)
+        self.n = int((self.indicator_idv != 0).sum())
+        self.n_vc = int(n_vc)
+
+    def _analyze(self, geno, geno_kind, cat, z, w, batch):
+        lib = L.lib()
+        l, n_vc = geno.shape[0], self.n_vc
+        dev = _is_torch(geno)
+        L.check(lib.gemma_hip_ci_begin(self.indicator_idv.size, _ptr(self.indicator_idv), n_vc), "CI.begin")
+        Xz, XWz = np.zeros((self.n, n_vc)), np.zeros((self.n, n_vc))
+        n_skipped, skipped = 0, C.c_size_t(0)
+        if dev:
+            import torch
+
+            def _t(v, dt, name):
+                if not _is_torch(v):
+                    return torch.as_tensor(np.ascontiguousarray(v, dtype=dt)).to(geno.device)
+                want = torch.int32 if dt is np.int32 else torch.float64
+                if v.dtype != want or v.device != geno.device or not v.is_contiguous() or tuple(v.shape) != (l,):
+                    raise ValueError("%s: a contiguous %s tensor with one entry per SNP row on the device of the rows" % (name, want))
+                return v
+            if not geno.is_contiguous():
+                raise ValueError("the genotype rows must be contiguous")
+            cat_t, z_t = _t(cat, np.int32, "cat"), _t(z, np.float64, "z")
+            w_t = None if w is None else _t(w, np.float64, "w")
+            out = torch.zeros((l, n_vc), dtype=torch.float64, device=geno.device)
+        else:
+            geno = np.ascontiguousarray(geno)
+            cat, z = np.ascontiguousarray(cat, dtype=np.int32), np.ascontiguousarray(z, dtype=np.float64)
+            w = None if w is None else np.ascontiguousarray(w, dtype=np.float64)
+            if cat.shape != (l,) or z.shape != (l,) or (w is not None and w.shape != (l,)):
+                raise ValueError("cat, z and w take one entry per SNP row")
+            out = np.zeros((l, n_vc))
+        for s0 in range(0, l, batch):  # pass 1
+            blk = geno[s0:s0 + batch]
+            if dev:
+                wp = C.c_void_p(w_t[s0:s0 + batch].data_ptr()) if w_t is not None else None
+                L.check(lib.gemma_hip_ci_xwz_d(geno_kind, C.c_void_p(blk.data_ptr()), blk.shape[0], _tld(geno),
+                                               C.c_void_p(cat_t[s0:s0 + batch].data_ptr()), C.c_void_p(z_t[s0:s0 + batch].data_ptr()), wp,
+                                               C.byref(skipped), _stream()), "CI.xwz")
+            else:
+                L.check(lib.gemma_hip_ci_xwz(geno_kind, _ptr(blk), blk.shape[0], blk.strides[0] // blk.itemsize, _ptr(cat[s0:s0 + batch]),
+                                             _ptr(z[s0:s0 + batch]), None if w is None else _ptr(w[s0:s0 + batch]), C.byref(skipped)),
+                        "CI.xwz")
+            n_skipped += skipped.value
+        L.check(lib.gemma_hip_ci_xwz_end(_ptr(Xz), _ptr(XWz)), "CI.xwz_end")
+        for s0 in range(0, l, batch):  # pass 2
+            blk, ob = geno[s0:s0 + batch], out[s0:s0 + batch]
+            if dev:
+                L.check(lib.gemma_hip_ci_xtxwz_d(geno_kind, C.c_void_p(blk.data_ptr()), blk.shape[0], _tld(geno),
+                                                 C.c_void_p(ob.data_ptr()), _stream()), "CI.xtxwz")
+            else:
+                L.check(lib.gemma_hip_ci_xtxwz(geno_kind, _ptr(blk), blk.shape[0], blk.strides[0] // blk.itemsize, _ptr(ob)), "CI.xtxwz")
+        if dev:
+            import torch
+            torch.cuda.synchronize()
+        return Xz, XWz, out, n_skipped
+
+    def AnalyzePlink(self, bed_rows, cat, z, w=None, batch=LMM_BATCH_SIZE):
+        """PlinkXwz then PlinkXtXwz, src/vc.cpp:2314-2437, :2568-2688: bed_rows = .bed rows over all ni_total individuals."""
+        if not _is_torch(bed_rows):
+            bed_rows = np.asarray(bed_rows, dtype=np.uint8)
+        return self._analyze(bed_rows, L.GENO_PLINK_2BIT, cat, z, w, batch)
+
+    def AnalyzeBimbam(self, G, cat, z, w=None, batch=LMM_BATCH_SIZE):
+        """BimbamXwz then BimbamXtXwz, src/vc.cpp:2225-2312, :2480-2566: G SNP-major over all individuals, NaN = NA.  The
+        individuals are the ones indicator_idv selects (the reference takes the first ni_test tokens of a line)."""
+        if not _is_torch(G):
+            G = np.asarray(G, dtype=np.float64)
+        return self._analyze(G, L.GENO_F64_SNP_MAJOR, cat, z, w, batch)
+
+    @staticmethod
+    def Release():
+        L.check(L.lib().gemma_hip_ci_release(), "CI.Release")
 
 
 # ----------------------------------------------------------------------------- windowed SNP correlation (-calccor)
@@ -1512,10 +1601,216 @@ def ReadFile_beta(file_beta, mapRS2cat, mapRS2wA):
                 ni_total=ni_total, ns_total=ns_total, ns_test=ns_test)
 
 
-def ObtainWeight(rs_analysed, setSnps_beta, mapRS2cat):
-    """PARAM::ObtainWeight without -wsnp / -wcat, src/param.cpp:2214-2296: weight 1 for every analysed SNP that is in the beta file
-    (when one is given) and in a category (when categories are given)."""
-    return {rs: 1.0 for rs in rs_analysed if (not setSnps_beta or rs in setSnps_beta) and (not mapRS2cat or rs in mapRS2cat)}
+def ObtainWeight(rs_analysed, setSnps_beta, mapRS2cat, mapRS2wcat=None):
+    """PARAM::ObtainWeight without -wsnp, src/param.cpp:2214-2296: weight 1 for every analysed SNP that is in the beta file (when
+    one is given), in the -wcat file (when one is given, :2235) and in a category (when categories are given)."""
+    return {rs: 1.0 for rs in rs_analysed if (not setSnps_beta or rs in setSnps_beta) and (not mapRS2wcat or rs in mapRS2wcat) and
+            (not mapRS2cat or rs in mapRS2cat)}
+
+
+def ReadFile_wcat(file_wcat, n_vc):
+    """The -wcat overload of ReadFile_wsnp, src/gemma_io.cpp:3281-3353 -> mapRS2wcat: per SNP its n_vc weights, one per column
+    that is not rs / chr / pos / cm / a1 / a0."""
+    mapRS2wcat = {}
+    with _open_text(file_wcat) as f:
+        lines = f.read().splitlines()
+    h = ReadHeader_io(lines[0])
+    rs = chr_ = pos = ""
+    for line in lines[1:]:
+        if not line.strip(" \t\r"):
+            continue
+        toks = _tokens(line)
+        weight = []
+        for i in range(h["coln"]):
+            tok, k = toks[i], i + 1
+            if h["rs_col"] == k:
+                rs = tok
+            elif h["chr_col"] == k:
+                chr_ = tok
+            elif h["pos_col"] == k:
+                pos = tok
+            elif k in (h["cm_col"], h["a1_col"], h["a0_col"]):
+                pass
+            else:
+                weight.append(_atof(tok))
+        if len(weight) != n_vc:
+            raise ValueError("Number of columns in the wcat file does not match that of cat file.")
+        if h["rs_col"] == 0:
+            rs = chr_ + ":" + pos
+        mapRS2wcat[rs] = weight
+    return mapRS2wcat
+
+
+def UpdateWeight(pve_flag, mapRS2wK, ni_test, ns, v_pve, mapRS2wcat, mapRS2cat):
+    """PARAM::UpdateWeight, src/param.cpp:2300-2349 -> mapRS2wA: 1 / (1 + sum_i ni_test / ns_i wcat_i pve_i)^2 per SNP of mapRS2wK
+    (in the map's order), normalised to mean 1 within each category.  pve_flag 1 clamps pve to [0, 1] (-vc 2), 0 does not (-ci 2)."""
+    n_vc = len(v_pve)
+    wsum, wcount = [0.0] * n_vc, [0.0] * n_vc
+    mapRS2wA = {}
+    for rs in sorted(mapRS2wK):
+        wc = mapRS2wcat.get(rs, [0.0] * n_vc)
+        d = 1.0
+        for i in range(n_vc):
+            if v_pve[i] >= 1 and pve_flag == 1:
+                d += float(ni_test) / float(ns[i]) * wc[i]
+            elif v_pve[i] <= 0 and pve_flag == 1:
+                d += 0
+            else:
+                d += float(ni_test) / float(ns[i]) * wc[i] * float(v_pve[i])
+        mapRS2wA[rs] = 1 / (d * d)
+        k = mapRS2cat[rs] if mapRS2cat else 0
+        wsum[k] += mapRS2wA[rs]
+        wcount[k] += 1
+    for i in range(n_vc):
+        wsum[i] = wsum[i] / wcount[i] if wcount[i] != 0 else float("nan")
+    for rs in mapRS2wA:
+        mapRS2wA[rs] /= wsum[mapRS2cat[rs] if mapRS2cat else 0]
+    return mapRS2wA
+
+
+def ReadFile_beta_z(file_beta, mapRS2wA):
+    """The (mapRS2wA, mapRS2A1, mapRS2z) overload of ReadFile_beta, src/gemma_io.cpp:3553-3714 -> (mapRS2A1, mapRS2z): the signed z
+    (from z, else beta / se, else 0) and the allele it refers to.  Without an allele column a1 stays the empty string."""
+    mapRS2A1, mapRS2z = {}, {}
+    with _open_text(file_beta) as f:
+        lines = f.read().splitlines()
+    h = ReadHeader_io(lines[0])
+    rs = chr_ = pos = a1 = ""
+    for line in lines[1:]:
+        if not line.strip(" \t\r"):
+            continue
+        toks = _tokens(line)
+        z = beta = se = 0.0
+        for i in range(h["coln"]):
+            tok, k = toks[i], i + 1
+            if h["rs_col"] == k:
+                rs = tok
+            if h["chr_col"] == k:
+                chr_ = tok
+            if h["pos_col"] == k:
+                pos = tok
+            if h["a1_col"] == k:
+                a1 = tok
+            if h["z_col"] == k:
+                z = _atof(tok)
+            if h["beta_col"] == k:
+                beta = _atof(tok)
+            if h["sebeta_col"] == k:
+                se = _atof(tok)
+        if h["rs_col"] == 0:
+            rs = chr_ + ":" + pos
+        if h["z_col"] != 0:
+            pass
+        elif h["beta_col"] != 0 and h["sebeta_col"] != 0:
+            z = beta / se if se != 0 else (float("nan") if beta == 0 else float("inf"))
+        else:
+            z = 0.0
+        if not mapRS2wA or rs in mapRS2wA:
+            mapRS2z[rs] = z
+            mapRS2A1[rs] = a1
+    return mapRS2A1, mapRS2z
+
+
+def UpdateSNPnZ(rs_analysed, a_minor, mapRS2wA, mapRS2A1, mapRS2z, mapRS2cat):
+    """PARAM::UpdateSNPnZ, src/param.cpp:2353-2416 (one genotype file) -> (keep, w, z, vec_cat): keep[t] says whether analysed SNP t
+    stays in indicator_snp (it has a weight); w, z, vec_cat run over the kept SNPs in file order.  z is negated when the beta
+    file's allele differs from the genotype file's minor allele -- for every SNP when the beta file names no allele."""
+    keep, w, z, vec_cat = [], [], [], []
+    for rs, a1 in zip(rs_analysed, a_minor):
+        if rs in mapRS2wA:
+            z.append(mapRS2z[rs] if a1 == mapRS2A1[rs] else -1 * mapRS2z[rs])
+            vec_cat.append(mapRS2cat[rs] if mapRS2cat else 0)
+            w.append(mapRS2wA[rs])
+            keep.append(True)
+        else:
+            keep.append(False)
+    return np.array(keep, dtype=bool), np.array(w, dtype=np.float64), np.array(z, dtype=np.float64), np.array(vec_cat, dtype=np.int32)
+
+
+def _read_numbers(path):
+    with _open_text(path) as f:
+        return [[_atof(t) for t in _tokens(line)] for line in f.read().splitlines() if line.strip(" \t\r")]
+
+
+def ReadFile_ref(file_ref):
+    """src/gemma_io.cpp:3987-4009 -> (S, Svar, s_vec, ni): prefix.S.txt (S on top of Svar) and prefix.size.txt (ns per category,
+    then the number of individuals)."""
+    size = [r[0] for r in _read_numbers(file_ref + ".size.txt")]
+    n_vc = len(size) - 1
+    M = np.array(_read_numbers(file_ref + ".S.txt"), dtype=np.float64)
+    if M.shape != (2 * n_vc, n_vc):
+        raise ValueError("%s.S.txt is %s, %s.size.txt names %d categories" % (file_ref, M.shape, file_ref, n_vc))
+    return M[:n_vc].copy(), M[n_vc:].copy(), np.array(size[:n_vc]), int(size[n_vc])
+
+
+def ReadFile_study(file_study):
+    """src/gemma_io.cpp:3961-3985 -> (Vq, q, s_vec, ni): prefix.Vq.txt, prefix.q.txt and prefix.size.txt."""
+    size = [r[0] for r in _read_numbers(file_study + ".size.txt")]
+    n_vc = len(size) - 1
+    Vq = np.array(_read_numbers(file_study + ".Vq.txt"), dtype=np.float64).reshape(n_vc, n_vc)
+    q = np.array([r[0] for r in _read_numbers(file_study + ".q.txt")], dtype=np.float64)
+    return Vq, q, np.array(size[:n_vc]), int(size[n_vc])
+
+
+def CalcVCss_study(file_study, file_ref):
+    """-study PREFIX -ref PREFIX without genotypes, src/gemma.cpp:2231-2330: ReadFile_study + ReadFile_ref + CalcVCss with the
+    study's SNP counts and sample size (:2299).  The reference panel's counts and ni_ref only go into the size vector the run
+    writes (:2305-2307): the `size` entry of the result."""
+    Vq, q, s_study, ni_study = ReadFile_study(file_study)
+    S, Svar, s_ref, ni_ref = ReadFile_ref(file_ref)
+    if len(s_study) != len(s_ref):
+        raise ValueError("%s names %d categories, %s names %d" % (file_study, len(s_study), file_ref, len(s_ref)))
+    est = CalcVCss(Vq, S, Svar, q, s_study, ni_study)
+    est["size"] = np.append(s_ref, float(ni_ref))
+    return est
+
+
+def CalcCIss(Xz, XWz, XtXWz, S_mat, Svar_mat, w, z, s_vec, vec_cat, v_pve):
+    """src/vc.cpp:2727-2950 -> dict(pve, se_pve, pve_total, se_pve_total, sigma2, se_sigma2, enrich, se_enrich): the standard errors
+    of given pve from the two genotype passes (class CI), S and Svar of the reference panel (ReadFile_ref), w / z / vec_cat of
+    UpdateSNPnZ and s_vec = the number of SNPs per category.  O(p n_vc^2 + n n_vc^2) on the host."""
+    Xz, XWz, XtXWz = (np.asarray(a, dtype=np.float64) for a in (Xz, XWz, XtXWz))
+    S_mat, Svar_mat = np.asarray(S_mat, dtype=np.float64), np.asarray(Svar_mat, dtype=np.float64)
+    w, z, s_vec, v_pve = (np.asarray(a, dtype=np.float64) for a in (w, z, s_vec, v_pve))
+    vec_cat = np.asarray(vec_cat, dtype=np.int64)
+    ni_test, n_vc = XWz.shape
+    zwz, zz = np.zeros(n_vc), np.zeros(n_vc)
+    np.add.at(zwz, vec_cat, w * z * z)
+    np.add.at(zz, vec_cat, z * z)
+    s_pve, s_snp = float(v_pve.sum()), float(s_vec.sum())
+    Xz_pve = Xz @ (v_pve / s_vec)
+    w_pve = (v_pve / s_vec)[vec_cat]
+    s0 = 1 - s_pve + float((zz * v_pve / s_vec).sum())
+    qvar = np.zeros((n_vc, n_vc))
+    for i in range(n_vc):
+        s1 = s0 - zwz[i] * (1 - s_pve) / s_vec[i]
+        WXtXWz = XtXWz[:, i] * w_pve
+        s1 -= (Xz_pve @ XWz[:, i]) / s_vec[i]
+        for j in range(n_vc):
+            s = s1 - zwz[j] * (1 - s_pve) / s_vec[j]
+            s += (WXtXWz @ XtXWz[:, j]) / (s_vec[i] * s_vec[j])
+            s += (XWz[:, i] @ XWz[:, j]) / (s_vec[i] * s_vec[j]) * (1 - s_pve)
+            s -= (Xz_pve @ XWz[:, j]) / s_vec[j]
+            qvar[i, j] = s
+    d = float(ni_test - 1)
+    qvar *= 2.0 / (d * d * d)
+    Si = np.linalg.inv(S_mat)
+    Var = np.zeros((n_vc, n_vc))
+    for i in range(n_vc):
+        for j in range(i, n_vc):
+            Var[i, j] = Var[j, i] = Svar_mat[i, j] * (v_pve[i] * v_pve[j]) + qvar[i, j]
+    Var = (Si @ Var) @ Si
+    sigma2 = v_pve / s_vec
+    enrich = v_pve / s_vec * s_snp / s_pve
+    se_pve = np.sqrt(np.diag(Var))
+    T = np.zeros((n_vc, n_vc))
+    for i in range(n_vc):
+        dd, d1 = v_pve[i] / s_pve, s_vec[i]
+        for j in range(n_vc):
+            T[i, j] = ((1 - dd) if i == j else (-1 * dd)) / d1 * s_snp / s_pve
+    se_enrich = np.sqrt(np.diag((T @ Var) @ T.T))
+    return dict(pve=v_pve.copy(), se_pve=se_pve, pve_total=s_pve, se_pve_total=float(np.sqrt(Var.sum())), sigma2=sigma2,
+                se_sigma2=se_pve / s_vec, enrich=enrich, se_enrich=se_enrich)
 
 
 def Calcq(n_block, vec_cat, vec_ni, vec_weight, vec_z2, n_vc):

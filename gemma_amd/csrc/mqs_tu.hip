@@ -17,6 +17,7 @@
 #include "host_linalg.h"
 #include "dgemm_mfma.hip.h"
 #include "mqs.hip.h"
+#include "ci.hip.h"
 #include "mqs_tu.h"
 
 namespace gemma_hip {
@@ -99,6 +100,7 @@ void mqs_release_x() {
 
 void mqs_tu_shutdown() {
   mqs_release_x();
+  ci_release_x();
   gemm_aux_destroy();
 }
 
@@ -114,13 +116,15 @@ int mqs_begin_x(long ni_total, const int *indicator, int n_vc, const double *W, 
     msg = "mqs_begin: " + std::to_string(n) + " analysed individuals for " + std::to_string(c) + " covariates";
     return GEMMA_HIP_EINVAL;
   }
+  const bool carry = slot == 2; // slot 2: slot 1 with A starting from the kept K instead of 0
+  if (carry) slot = 1;
   if (slot == 1) {
     if (!g_mqs.haveK || g_mqs.active) {
-      msg = "mqs_begin: slot 1 fills A beside the K of a finished slot 0 session, and there is none";
+      msg = std::string("mqs_begin: slot ") + (carry ? "2" : "1") + " fills A beside the K of a finished slot 0 session, and there is none";
       return GEMMA_HIP_EINVAL;
     }
     if (g_mqs.n != n || g_mqs.nvc != n_vc || g_mqs.ni_total != ni_total) {
-      msg = "mqs_begin: slot 1 with n = " + std::to_string(n) + ", n_vc = " + std::to_string(n_vc) + "; the kept K has n = " +
+      msg = std::string("mqs_begin: slot ") + (carry ? "2" : "1") + " with n = " + std::to_string(n) + ", n_vc = " + std::to_string(n_vc) + "; the kept K has n = " +
             std::to_string(g_mqs.n) + ", n_vc = " + std::to_string(g_mqs.nvc);
       return GEMMA_HIP_EINVAL;
     }
@@ -159,7 +163,10 @@ int mqs_begin_x(long ni_total, const int *indicator, int n_vc, const double *W, 
     else g_mqs.A.release();
     return rc;
   }
-  TU_CHK(hipMemset(M.p, 0, total * 8));
+  // The reference's second CalcS hands PlinkKin the A of the first one (the centred + scaled copy of K) and PlinkKin adds to what it
+  // is given (src/gemma_io.cpp:3103, :3120, :3136: beta = 1, no set_zero): slot 2 reproduces that sum, slot 1 starts from 0.
+  if (carry) TU_CHK(hipMemcpy(M.p, g_mqs.K.p, total * 8, hipMemcpyDeviceToDevice));
+  else TU_CHK(hipMemset(M.p, 0, total * 8));
   std::vector<double> Wt((size_t)c * ld, 0.0);
   for (long i = 0; i < n; ++i)
     for (int a = 0; a < c; ++a) Wt[(size_t)a * ld + i] = W[i * c + a];
@@ -356,6 +363,247 @@ int mqs_get_x(int slot, int i_vc, double *out, std::string &msg) {
   const double *M = ((slot == 1 && g_mqs.haveA) ? g_mqs.A : g_mqs.K).as<double>();
   const long n = g_mqs.n, ld = g_mqs.ld;
   TU_CHK(hipMemcpy2D(out, (size_t)n * 8, M + (size_t)i_vc * n * ld, (size_t)ld * 8, (size_t)n * 8, (size_t)n, hipMemcpyDeviceToHost));
+  return GEMMA_HIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ -ci 1 / -ci 2
+// The two genotype passes of the MQS confidence intervals (kernels: ci.hip.h), in place of
+//   PlinkXwz / BimbamXwz        src/vc.cpp:2314-2437, :2225-2312   (pass 1: one seekg, one daxpy per SNP there)
+//   PlinkXtXwz / BimbamXtXwz    src/vc.cpp:2568-2688, :2480-2566   (pass 2: n_vc ddots per SNP there)
+namespace {
+
+struct CiState {
+  int pass = 0;               // 0: none, 1: pass 1 open, 2: XWz finished, pass 2 open
+  long n = 0, ni_total = 0, words = 0, ldx = 0;
+  int nvc = 0;
+  DevBuf idx, amask;          // ints, 2-bit group mask
+  DevBuf acc;                 // n x 16: Xz | XWz over the analysed individuals
+  DevBuf Bf;                  // pass 2, 2-bit rows: XWz scattered to all individuals, 16 columns, zero rows between
+  DevBuf Bc;                  // pass 2, fp64 rows: XWz over the analysed individuals, 16 columns
+  DevBuf st, tab, bm, cat_d, z_d, w_d, flags, part, X, P, out, stage;
+} g_ci;
+
+// a buffer earlier asynchronous work may still read grows only after that work is done
+int ci_grow(DevBuf &b, size_t bytes, std::string &msg) {
+  if (bytes <= b.cap) return GEMMA_HIP_OK;
+  TU_CHK(hipDeviceSynchronize());
+  return b.reserve(bytes, "ci", msg);
+}
+
+int ci_stage(int geno_kind, const void *geno, long l, long &ld, hipStream_t s, const void *&src, std::string &msg) {
+  const bool plink = geno_kind == GEMMA_GENO_PLINK_2BIT;
+  const size_t row = plink ? (size_t)((g_ci.ni_total + 3) / 4) : (size_t)g_ci.ni_total * 8, pitch = (size_t)ld * (plink ? 1 : 8);
+  if ((size_t)l * row > g_ci.stage.cap) TU_CHK(hipDeviceSynchronize());
+  return stage_rows(g_ci.stage, geno, (size_t)l, row, pitch, plink ? 1 : 8, s, "ci", msg, src, ld);
+}
+
+// the per-SNP moments of a block (and, for fp64 rows, the centred rows in g_ci.X)
+int ci_stats(bool plink, const void *src, long l, long ld, hipStream_t s, std::string &msg) {
+  int rc;
+  if ((rc = ci_grow(g_ci.st, (size_t)l * sizeof(double2), msg))) return rc;
+  double2 *st = g_ci.st.as<double2>();
+  if (plink) {
+    const unsigned char *G = reinterpret_cast<const unsigned char *>(src);
+    const bool al = ((reinterpret_cast<uintptr_t>(src) & 3) == 0) && ((ld & 3) == 0);
+    const unsigned rows4 = (unsigned)((l + 3) / 4);
+    if (al)
+      hipLaunchKernelGGL(ci_stats_plink_kernel<true>, dim3(rows4), dim3(256), 0, s, G, ld, l, g_ci.amask.as<unsigned>(), g_ci.ni_total,
+                         g_ci.words, (int)g_ci.n, st);
+    else
+      hipLaunchKernelGGL(ci_stats_plink_kernel<false>, dim3(rows4), dim3(256), 0, s, G, ld, l, g_ci.amask.as<unsigned>(), g_ci.ni_total,
+                         g_ci.words, (int)g_ci.n, st);
+  } else {
+    if ((rc = ci_grow(g_ci.X, (size_t)l * g_ci.ldx * 8, msg))) return rc;
+    hipLaunchKernelGGL(ci_ingest_f64_kernel, dim3((unsigned)l), dim3(256), 0, s, reinterpret_cast<const double *>(src), ld, l,
+                       g_ci.idx.as<int>(), (int)g_ci.n, g_ci.X.as<double>(), g_ci.ldx, st);
+  }
+  TU_CHK(hipGetLastError());
+  return GEMMA_HIP_OK;
+}
+
+} // namespace
+
+void ci_release_x() {
+  DevBuf *all[] = {&g_ci.idx, &g_ci.amask, &g_ci.acc, &g_ci.Bf, &g_ci.Bc, &g_ci.st, &g_ci.tab, &g_ci.bm, &g_ci.cat_d, &g_ci.z_d,
+                   &g_ci.w_d, &g_ci.flags, &g_ci.part, &g_ci.X, &g_ci.P, &g_ci.out, &g_ci.stage};
+  for (DevBuf *b : all) b->release();
+  g_ci.pass = 0;
+  g_ci.n = g_ci.ni_total = g_ci.words = g_ci.ldx = 0;
+  g_ci.nvc = 0;
+}
+
+int ci_pass_x() { return g_ci.pass; }
+long ci_ni_total_x() { return g_ci.ni_total; }
+
+int ci_begin_x(long ni_total, const int *indicator, int n_vc, std::string &msg) {
+  std::vector<int> idx;
+  for (long i = 0; i < ni_total; ++i)
+    if (!indicator || indicator[i] != 0) idx.push_back((int)i);
+  const long n = (long)idx.size();
+  if (n < 1) {
+    msg = "ci_begin: no analysed individual";
+    return GEMMA_HIP_EINVAL;
+  }
+  TU_CHK(hipDeviceSynchronize());
+  ci_release_x();
+  gemm_aux_init();
+  const long words = (ni_total + 15) / 16;
+  std::vector<unsigned> am((size_t)words, 0u);
+  for (int p : idx) am[(size_t)(p >> 4)] |= 1u << (2 * (p & 15));
+  int rc;
+  if ((rc = g_ci.idx.reserve((size_t)n * sizeof(int), "ci", msg)) || (rc = g_ci.amask.reserve((size_t)words * sizeof(unsigned), "ci", msg)) ||
+      (rc = g_ci.acc.reserve((size_t)n * CI_COLS * 8, "ci", msg)) || (rc = g_ci.flags.reserve(2 * sizeof(int), "ci", msg))) {
+    ci_release_x();
+    return rc;
+  }
+  TU_CHK(hipMemcpy(g_ci.idx.p, idx.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+  TU_CHK(hipMemcpy(g_ci.amask.p, am.data(), (size_t)words * sizeof(unsigned), hipMemcpyHostToDevice));
+  TU_CHK(hipMemset(g_ci.acc.p, 0, (size_t)n * CI_COLS * 8));
+  g_ci.n = n;
+  g_ci.ni_total = ni_total;
+  g_ci.words = words;
+  g_ci.ldx = (n + 1) & ~1L;
+  g_ci.nvc = n_vc;
+  g_ci.pass = 1;
+  return GEMMA_HIP_OK;
+}
+
+int ci_xwz_x(int geno_kind, const void *geno, long l, long ld, const int *cat, const double *z, const double *w, bool device,
+             hipStream_t s, size_t *n_skipped, std::string &msg) {
+  const bool plink = geno_kind == GEMMA_GENO_PLINK_2BIT;
+  const long n = g_ci.n, words = g_ci.words;
+  const int nvc = g_ci.nvc;
+  int rc;
+  const void *src = geno;
+  const int *cat_d = cat;
+  const double *z_d = z, *w_d = w;
+  if (!device) {
+    for (long t = 0; t < l; ++t)
+      if (cat[t] < 0 || cat[t] >= nvc) {
+        msg = "ci_xwz: category " + std::to_string(cat[t]) + " of SNP " + std::to_string(t) + " with n_vc = " + std::to_string(nvc);
+        return GEMMA_HIP_EINVAL;
+      }
+    if ((rc = ci_grow(g_ci.cat_d, (size_t)l * sizeof(int), msg)) || (rc = ci_grow(g_ci.z_d, (size_t)l * 8, msg)) ||
+        (rc = ci_grow(g_ci.w_d, (size_t)l * 8, msg)) || (rc = ci_stage(geno_kind, geno, l, ld, s, src, msg)))
+      return rc;
+    TU_CHK(hipMemcpyAsync(g_ci.cat_d.p, cat, (size_t)l * sizeof(int), hipMemcpyHostToDevice, s));
+    TU_CHK(hipMemcpyAsync(g_ci.z_d.p, z, (size_t)l * 8, hipMemcpyHostToDevice, s));
+    if (w) TU_CHK(hipMemcpyAsync(g_ci.w_d.p, w, (size_t)l * 8, hipMemcpyHostToDevice, s));
+    cat_d = g_ci.cat_d.as<int>();
+    z_d = g_ci.z_d.as<double>();
+    w_d = w ? g_ci.w_d.as<double>() : nullptr;
+  }
+  const int parts = ci_parts(l, words);
+  const long ldp = words * 16;
+  if ((rc = ci_grow(g_ci.bm, (size_t)l * CI_COLS * 8, msg)) || (plink && (rc = ci_grow(g_ci.tab, (size_t)l * sizeof(double4), msg))) ||
+      (plink && (rc = ci_grow(g_ci.part, (size_t)parts * ldp * CI_COLS * 8, msg))) || (rc = ci_stats(plink, src, l, ld, s, msg)))
+    return rc;
+  int *flags = g_ci.flags.as<int>();
+  TU_CHK(hipMemsetAsync(flags, 0, 2 * sizeof(int), s));
+  const unsigned lb = (unsigned)((l + 255) / 256);
+  if (plink)
+    hipLaunchKernelGGL(ci_table_kernel<true>, dim3(lb), dim3(256), 0, s, g_ci.st.as<double2>(), cat_d, z_d, w_d, l, nvc,
+                       g_ci.tab.as<double4>(), g_ci.bm.as<double>(), flags);
+  else
+    hipLaunchKernelGGL(ci_table_kernel<false>, dim3(lb), dim3(256), 0, s, g_ci.st.as<double2>(), cat_d, z_d, w_d, l, nvc,
+                       (double4 *)nullptr, g_ci.bm.as<double>(), flags);
+  TU_CHK(hipGetLastError());
+  int fl[2];
+  TU_CHK(hipMemcpyAsync(fl, flags, sizeof fl, hipMemcpyDeviceToHost, s));
+  TU_CHK(hipStreamSynchronize(s));
+  if (fl[1]) { // nothing of the block is accumulated
+    msg = "ci_xwz: a category index of the block is outside 0 .. n_vc - 1 = " + std::to_string(nvc - 1);
+    return GEMMA_HIP_EINVAL;
+  }
+  if (n_skipped) *n_skipped = (size_t)fl[0];
+  double *acc = g_ci.acc.as<double>();
+  if (plink) {
+    const unsigned char *G = reinterpret_cast<const unsigned char *>(src);
+    const bool al = ((reinterpret_cast<uintptr_t>(src) & 3) == 0) && ((ld & 3) == 0);
+    const int rpp = (int)((l + parts - 1) / parts);
+    const dim3 grid((unsigned)((words + 4 * CI_TILES - 1) / (4 * CI_TILES)), (unsigned)parts);
+    if (al)
+      hipLaunchKernelGGL(ci_xwz_plink_kernel<true>, grid, dim3(256), 0, s, G, ld, l, g_ci.amask.as<unsigned>(), g_ci.ni_total, words,
+                         g_ci.tab.as<double4>(), g_ci.bm.as<double>(), rpp, g_ci.part.as<double>(), ldp);
+    else
+      hipLaunchKernelGGL(ci_xwz_plink_kernel<false>, grid, dim3(256), 0, s, G, ld, l, g_ci.amask.as<unsigned>(), g_ci.ni_total, words,
+                         g_ci.tab.as<double4>(), g_ci.bm.as<double>(), rpp, g_ci.part.as<double>(), ldp);
+    TU_CHK(hipGetLastError());
+    hipLaunchKernelGGL(ci_combine_kernel, dim3((unsigned)((n * CI_COLS + 255) / 256)), dim3(256), 0, s, g_ci.part.as<double>(), ldp, parts,
+                       g_ci.idx.as<int>(), n, acc);
+    TU_CHK(hipGetLastError());
+  } else {
+    // acc (n x 16) += X^T (n x l) bm (l x 16): the centred rows as [k = snp][m = individual] -> ('T', 'N')
+    TU_CHK(launch_dgemm('T', 'N', n, CI_COLS, l, 1.0, g_ci.X.as<double>(), g_ci.ldx, g_ci.bm.as<double>(), CI_COLS, 1.0, acc, CI_COLS,
+                        false, false, s));
+  }
+  if (!device) TU_CHK(hipStreamSynchronize(s)); // the caller's rows and the staging buffers are free again
+  return GEMMA_HIP_OK;
+}
+
+int ci_xwz_end_x(double *Xz, double *XWz, std::string &msg) {
+  const long n = g_ci.n;
+  const int nvc = g_ci.nvc;
+  TU_CHK(hipDeviceSynchronize());
+  std::vector<double> acc((size_t)n * CI_COLS);
+  TU_CHK(hipMemcpy(acc.data(), g_ci.acc.p, acc.size() * 8, hipMemcpyDeviceToHost));
+  std::vector<int> idx((size_t)n);
+  TU_CHK(hipMemcpy(idx.data(), g_ci.idx.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+  const long rows = ((g_ci.words + CI_GROUP - 1) / CI_GROUP) * CI_GROUP * 16;
+  std::vector<double> Bf((size_t)rows * CI_COLS, 0.0), Bc((size_t)n * CI_COLS, 0.0);
+  for (long j = 0; j < n; ++j)
+    for (int k = 0; k < nvc; ++k) {
+      const double xz = acc[(size_t)j * CI_COLS + k], xwz = acc[(size_t)j * CI_COLS + nvc + k];
+      if (Xz) Xz[j * nvc + k] = xz;
+      if (XWz) XWz[j * nvc + k] = xwz;
+      Bf[(size_t)idx[j] * CI_COLS + k] = xwz;
+      Bc[(size_t)j * CI_COLS + k] = xwz;
+    }
+  int rc;
+  if ((rc = g_ci.Bf.reserve(Bf.size() * 8, "ci", msg)) || (rc = g_ci.Bc.reserve(Bc.size() * 8, "ci", msg))) return rc;
+  TU_CHK(hipMemcpy(g_ci.Bf.p, Bf.data(), Bf.size() * 8, hipMemcpyHostToDevice));
+  TU_CHK(hipMemcpy(g_ci.Bc.p, Bc.data(), Bc.size() * 8, hipMemcpyHostToDevice));
+  g_ci.part.release(); // pass 1 only
+  g_ci.pass = 2;
+  return GEMMA_HIP_OK;
+}
+
+int ci_xtxwz_x(int geno_kind, const void *geno, long l, long ld, double *out, bool device, hipStream_t s, std::string &msg) {
+  const bool plink = geno_kind == GEMMA_GENO_PLINK_2BIT;
+  const long n = g_ci.n;
+  const int nvc = g_ci.nvc;
+  int rc;
+  const void *src = geno;
+  if (!device && (rc = ci_stage(geno_kind, geno, l, ld, s, src, msg))) return rc;
+  double *out_d = out;
+  if (!device) {
+    if ((rc = ci_grow(g_ci.out, (size_t)l * nvc * 8, msg))) return rc;
+    out_d = g_ci.out.as<double>();
+  }
+  if ((rc = ci_stats(plink, src, l, ld, s, msg))) return rc;
+  if (plink) {
+    const unsigned char *G = reinterpret_cast<const unsigned char *>(src);
+    const bool al = ((reinterpret_cast<uintptr_t>(src) & 3) == 0) && ((ld & 3) == 0);
+    const unsigned nb = (unsigned)((l + 15) / 16);
+    if (al)
+      hipLaunchKernelGGL(ci_xtxwz_plink_kernel<true>, dim3(nb), dim3(256), 0, s, G, ld, l, g_ci.ni_total, g_ci.words, g_ci.st.as<double2>(),
+                         g_ci.Bf.as<double>(), nvc, out_d);
+    else
+      hipLaunchKernelGGL(ci_xtxwz_plink_kernel<false>, dim3(nb), dim3(256), 0, s, G, ld, l, g_ci.ni_total, g_ci.words, g_ci.st.as<double2>(),
+                         g_ci.Bf.as<double>(), nvc, out_d);
+    TU_CHK(hipGetLastError());
+  } else {
+    if ((rc = ci_grow(g_ci.P, (size_t)l * CI_COLS * 8, msg))) return rc;
+    TU_CHK(launch_dgemm('N', 'N', l, CI_COLS, n, 1.0, g_ci.X.as<double>(), g_ci.ldx, g_ci.Bc.as<double>(), CI_COLS, 0.0, g_ci.P.as<double>(),
+                        CI_COLS, false, false, s));
+    hipLaunchKernelGGL(ci_scale_rows_kernel, dim3((unsigned)((l * nvc + 255) / 256)), dim3(256), 0, s, g_ci.P.as<double>(),
+                       g_ci.st.as<double2>(), l, nvc, out_d);
+    TU_CHK(hipGetLastError());
+  }
+  if (!device) {
+    TU_CHK(hipMemcpyAsync(out, out_d, (size_t)l * nvc * 8, hipMemcpyDeviceToHost, s));
+    TU_CHK(hipStreamSynchronize(s));
+  }
   return GEMMA_HIP_OK;
 }
 

@@ -532,7 +532,9 @@ int gemma_hip_prdt_kin(size_t ni, const double *G_full, const int *indicator_phe
  * mqs_begin: indicator_idv over ni_total individuals (NULL: all analysed; n = the number of non-zero entries), n_vc in 1..8
  * categories, W (n x n_cvt on the host, n_cvt in 1..64, with the intercept; (W^T W)^-1 is formed on the host, EINVAL when
  * singular).  slot 0 starts over, fills K and makes A = K (CalcS with an empty mapRS2wA); slot 1 needs the finished K of a slot 0
- * session with the same ni_total, n and n_vc, keeps it and fills A (the second CalcS of src/gemma.cpp:2198).
+ * session with the same ni_total, n and n_vc, keeps it and fills A (the second CalcS of src/gemma.cpp:2198).  slot 2 is slot 1 with
+ * A starting from the kept, centred + scaled K instead of 0: the reference's PlinkKin adds to the matrix it is handed, and its second
+ * CalcS hands it the A of the first, so this is the A that -vc 2 -beta of the reference computes.
  * mqs_add: l SNP-major rows (GEMMA_GENO_PLINK_2BIT, ld bytes per row; GEMMA_GENO_F64_SNP_MAJOR, ld doubles per row, NaN = missing)
  * of the SNPs with indicator_snp != 0, cat[l] = mapRS2cat of each SNP (0 when n_vc == 1; < 0: the SNP is in no category or has no
  * weight and is skipped; >= n_vc: EINVAL, nothing of the block is accumulated), weight[l] = mapRS2weight (NULL: 1).  Per SNP: mean
@@ -557,6 +559,34 @@ int gemma_hip_mqs_get(int slot, size_t i_vc, double *out);
 int gemma_hip_mqs_S(size_t n, size_t n_vc, const double *A, const double *K, size_t ld, size_t n_cvt, double *S);
 int gemma_hip_mqs_S_d(size_t n, size_t n_vc, const double *A_d, const double *K_d, size_t ld, size_t n_cvt, double *S, void *stream);
 int gemma_hip_mqs_release(void);
+
+/* ---- MQS confidence intervals: -ci 1 / -ci 2 (a_mode 66 / 67), the two genotype passes under CalcCIss ------------------------------ */
+/* In place of PlinkXwz / BimbamXwz (src/vc.cpp:2314-2437, :2225-2312) and PlinkXtXwz / BimbamXtXwz (:2568-2688, :2480-2566), called
+ * where src/gemma.cpp:2400-2554 calls them.  Over the n analysed individuals a SNP has mu = mean of its called genotypes,
+ * var = (sum g^2 + mu^2 n_miss) / n - mu^2 and x_i = g_i - mu (0 where missing); there is no covariate residual here.
+ * ci_begin: indicator_idv over ni_total individuals (NULL: all analysed), n_vc in 1..8 categories.
+ * ci_xwz (pass 1, block by block): l SNP-major rows (GEMMA_GENO_PLINK_2BIT, ld bytes per row; GEMMA_GENO_F64_SNP_MAJOR, ld doubles
+ * per row, NaN = missing) of the analysed SNPs in file order, cat[l] in 0 .. n_vc - 1 (anything else: EINVAL, nothing of the block
+ * is accumulated), z[l], w[l] (NULL: 1, -ci 1).  One pass over the block accumulates Xz[i][c] += z / sqrt(var) x_i and
+ * XWz[i][c] += w z / sqrt(var) x_i for c = cat of the SNP.  A SNP without a called genotype or with var == 0 among the analysed
+ * individuals contributes nothing and is counted in *n_skipped (may be NULL; of this block; always on the host): the reference
+ * divides by 0 there.  _d: geno, cat, z and w on the device, on `stream`, which is synchronised once per block.
+ * ci_xwz_end: ends pass 1; Xz, XWz (n x n_vc, row-major, either may be NULL) to the host; XWz stays on the device for pass 2.
+ * ci_xtxwz (pass 2, block by block): XtXWz[s][j] = (sum_i x_si XWz[i][j]) / sqrt(var_s), l x n_vc row-major; the row of a skipped
+ * SNP is 0.  _d: geno and XtXWz on the device, asynchronous on `stream`.
+ * The 2-bit route runs both passes on v_mfma_f64_16x16x4_f64 from the packed calls; the fp64 route centres the rows and uses the
+ * fp64 GEMM.  All sums run in an order fixed by the shapes: repeated sessions agree bit for bit.  Calls out of order (anything
+ * before ci_begin, ci_xtxwz before ci_xwz_end, ci_xwz after it) return GEMMA_HIP_EINVAL and leave the state as it was.
+ * ci_release returns all device memory of the state (as does gemma_hip_shutdown). */
+int gemma_hip_ci_begin(size_t ni_total, const int *indicator_idv, size_t n_vc);
+int gemma_hip_ci_xwz(int geno_kind, const void *geno, size_t l, size_t ld, const int *cat, const double *z, const double *w,
+                     size_t *n_skipped);
+int gemma_hip_ci_xwz_d(int geno_kind, const void *geno_d, size_t l, size_t ld, const int *cat_d, const double *z_d, const double *w_d,
+                       size_t *n_skipped, void *stream);
+int gemma_hip_ci_xwz_end(double *Xz, double *XWz);
+int gemma_hip_ci_xtxwz(int geno_kind, const void *geno, size_t l, size_t ld, double *XtXWz);
+int gemma_hip_ci_xtxwz_d(int geno_kind, const void *geno_d, size_t l, size_t ld, double *XtXWz_d, void *stream);
+int gemma_hip_ci_release(void);
 
 /* ---- Windowed SNP correlation: -calccor (a_mode 71), the prefix.cor.txt that -cor reads back -------------------------------------- */
 /* VARCOV::AnalyzePlink / AnalyzeBimbam (src/varcov.cpp:249-446) with Calc_Cor (:220-238), called where src/gemma.cpp:2046-2059 calls

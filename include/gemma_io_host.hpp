@@ -17,6 +17,10 @@
 //                                           (src/gemma_io.cpp:2367-2718, :3363-3551, :3716-3870), ObtainWeight / UpdateSNP
 //                                           (src/param.cpp:2214-2296, :2420-2453), CalcVCss (src/vc.cpp:1309-1500), CalcS
 //                                           (src/param.cpp:1717-1812: the .bed rows go to gemma_hip_mqs_*), WriteMQS
+//   MQS confidence intervals (-ci 1, -ci 2)   : ReadFile_wsnp (-wcat), ObtainWeight with -wcat, UpdateWeight, UpdateSNPnZ,
+//                                           ReadFile_beta (signed z and allele), ReadFile_ref, ReadFile_study, CalcCIss
+//                                           (src/vc.cpp:2727-2950), PlinkXwz / PlinkXtXwz, BimbamXwz / BimbamXtXwz (the rows go to
+//                                           gemma_hip_ci_*), CalcVCssBeta (-vc 1 / -vc 2 with -beta), CalcVCssStudy (-study -ref)
 //   windowed SNP correlation (-calccor)     : VARCOV::CalcNB, WriteCov, AnalyzePlink, AnalyzeBimbam (src/varcov.cpp; the rows go to
 //                                           gemma_hip_cor_block in blocks of LMM_BATCH_SIZE outputs plus their halo)
 //
@@ -1724,7 +1728,8 @@ inline void CalcVCss(const Matrix *Vq, const Matrix *S_mat, const Matrix *Svar_m
 // PARAM::CalcS on a PLINK set, src/param.cpp:1717-1812 with PlinkKin(..., mapRS2weight, mapRS2cat, ...), src/gemma_io.cpp:2947-3170:
 // the .bed rows of the SNPs with indicator_snp != 0 go to the device in blocks with their category (-1: no category or no
 // weight) and weight; S (2 n_vc x n_vc: S on top of Svar) and ns (n_vc) come back.  slot 0: K, and A = K (empty mapRS2wA);
-// slot 1: A beside the K of the previous call (src/gemma.cpp:2198).
+// slot 1: A beside the K of the previous call, from 0; slot 2: the same with A starting from that K, centred and scaled, which
+// is what the reference's second call computes (src/gemma.cpp:2198: PlinkKin adds to the A the first call left).
 inline bool CalcS(const std::string &file_bed, const std::vector<int> &indicator_idv, const std::vector<int> &indicator_snp,
                   const std::map<std::string, double> &mapRS2weight, const std::map<std::string, size_t> &mapRS2cat,
                   const std::vector<SNPINFO> &snpInfo, const Matrix *W, const size_t n_vc, Matrix *S, Vector *ns, const int slot = 0) {
@@ -1776,6 +1781,490 @@ inline bool WriteMQS(const std::string &prefix, const Matrix *S, const Matrix *V
   if (Vq) ok = ok && WriteMatrix(Vq, prefix + ".Vq.txt");
   if (q) ok = ok && WriteVector(q, prefix + ".q.txt");
   return ok;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// MQS confidence intervals (-ci 1 / -ci 2, a_mode 66 / 67, src/gemma.cpp:2400-2554) and the LDSC-weighted second round of
+// -vc 2 -beta (a_mode 62, src/gemma.cpp:2182-2212)
+// ---------------------------------------------------------------------------------------------------------------
+// ReadFile_wsnp, the -wcat overload, src/gemma_io.cpp:3281-3353: per SNP its n_vc weights, one per column that names nothing else
+inline bool ReadFile_wsnp(const std::string &file_wcat, const size_t n_vc, std::map<std::string, std::vector<double>> &mapRS2wvector) {
+  mapRS2wvector.clear();
+  TextFile infile(file_wcat);
+  if (!infile.ok()) {
+    std::cout << "error! fail to open snp weight file: " << file_wcat << std::endl;
+    return false;
+  }
+  std::vector<double> weight(n_vc, 0.0);
+  std::string line, rs, chr, pos;
+  HEADER header;
+  infile.getline(line);
+  ReadHeader_io(line, header);
+  while (infile.getline(line)) {
+    if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+    const char *p = line.data(), *end = p + line.size(), *b, *e;
+    size_t t = 0;
+    for (size_t i = 0; i < header.coln; i++) {
+      if (!detail::next_token(p, end, b, e)) throw std::runtime_error("Parsing input file '" + file_wcat + "' failed");
+      const std::string tok(b, e);
+      if (header.rs_col == i + 1) rs = tok;
+      else if (header.chr_col == i + 1) chr = tok;
+      else if (header.pos_col == i + 1) pos = tok;
+      else if (header.cm_col == i + 1 || header.a1_col == i + 1 || header.a0_col == i + 1) continue;
+      else {
+        if (t < n_vc) weight[t] = atof(tok.c_str());
+        t++;
+      }
+    }
+    if (t != n_vc) {
+      std::cout << "error! Number of columns in the wcat file does not match that of cat file.";
+      return false;
+    }
+    if (header.rs_col == 0) rs = chr + ":" + pos;
+    mapRS2wvector[rs] = weight;
+  }
+  return true;
+}
+
+// PARAM::ObtainWeight with the mapRS2wcat membership test of src/param.cpp:2233-2236 (still without -wsnp)
+inline void ObtainWeight(const std::vector<SNPINFO> &snpInfo, const std::vector<int> &indicator_snp,
+                         const std::set<std::string> &setSnps_beta, const std::map<std::string, std::vector<double>> &mapRS2wcat,
+                         const std::map<std::string, size_t> &mapRS2cat, std::map<std::string, double> &mapRS2wK) {
+  mapRS2wK.clear();
+  for (size_t i = 0; i < snpInfo.size(); i++) {
+    if (indicator_snp[i] == 0) continue;
+    const std::string &rs = snpInfo[i].rs_number;
+    if ((setSnps_beta.size() == 0 || setSnps_beta.count(rs) != 0) && (mapRS2wcat.size() == 0 || mapRS2wcat.count(rs) != 0) &&
+        (mapRS2cat.size() == 0 || mapRS2cat.count(rs) != 0))
+      mapRS2wK[rs] = 1;
+  }
+}
+
+// PARAM::UpdateWeight, src/param.cpp:2300-2349: pve_flag 0 leaves pve as it is (-ci 2), 1 clamps it to [0, 1] (-vc 2)
+inline void UpdateWeight(const size_t pve_flag, const std::map<std::string, double> &mapRS2wK, const size_t ni_test, const Vector *ns,
+                         const std::vector<double> &v_pve, const std::map<std::string, std::vector<double>> &mapRS2wcat,
+                         const std::map<std::string, size_t> &mapRS2cat, std::map<std::string, double> &mapRS2wA) {
+  const size_t n_vc = v_pve.size();
+  double d;
+  std::vector<double> wsum(n_vc, 0.0), wcount(n_vc, 0.0);
+  const std::vector<double> none(n_vc, 0.0);
+  for (std::map<std::string, double>::const_iterator it = mapRS2wK.begin(); it != mapRS2wK.end(); ++it) {
+    const std::vector<double> &wc = mapRS2wcat.count(it->first) != 0 ? mapRS2wcat.at(it->first) : none;
+    d = 1;
+    for (size_t i = 0; i < n_vc; i++) {
+      if (v_pve[i] >= 1 && pve_flag == 1) {
+        d += (double)ni_test / ns->data[i * ns->stride] * wc[i];
+      } else if (v_pve[i] <= 0 && pve_flag == 1) {
+        d += 0;
+      } else {
+        d += (double)ni_test / ns->data[i * ns->stride] * wc[i] * v_pve[i];
+      }
+    }
+    mapRS2wA[it->first] = 1 / (d * d);
+    const size_t k = mapRS2cat.size() == 0 ? 0 : mapRS2cat.at(it->first);
+    wsum[k] += mapRS2wA[it->first];
+    wcount[k]++;
+  }
+  for (size_t i = 0; i < n_vc; i++) wsum[i] /= wcount[i];
+  for (std::map<std::string, double>::iterator it = mapRS2wA.begin(); it != mapRS2wA.end(); ++it)
+    it->second /= wsum[mapRS2cat.size() == 0 ? 0 : mapRS2cat.at(it->first)];
+}
+
+// ReadFile_beta, the (mapRS2wA, mapRS2A1, mapRS2z) overload, src/gemma_io.cpp:3553-3714: the signed z (from z, else beta / se, else
+// 0) and the allele it refers to; without an allele column a1 stays empty
+inline void ReadFile_beta(const std::string &file_beta, const std::map<std::string, double> &mapRS2wA,
+                          std::map<std::string, std::string> &mapRS2A1, std::map<std::string, double> &mapRS2z) {
+  mapRS2A1.clear();
+  mapRS2z.clear();
+  TextFile infile(file_beta);
+  if (!infile.ok()) {
+    std::cout << "error! fail to open beta file: " << file_beta << std::endl;
+    return;
+  }
+  std::string line, rs, chr, pos, a1;
+  HEADER header;
+  infile.getline(line);
+  ReadHeader_io(line, header);
+  if (header.z_col == 0 && (header.beta_col == 0 || header.sebeta_col == 0)) std::cout << "error! missing z scores in the beta file." << std::endl;
+  while (infile.getline(line)) {
+    if (line.find_first_not_of(" \t\r") == std::string::npos) continue;
+    const char *p = line.data(), *end = p + line.size(), *b, *e;
+    double z = 0, beta = 0, se_beta = 0;
+    for (size_t i = 0; i < header.coln; i++) {
+      if (!detail::next_token(p, end, b, e)) throw std::runtime_error("Parsing input file '" + file_beta + "' failed");
+      const std::string tok(b, e);
+      if (header.rs_col == i + 1) rs = tok;
+      if (header.chr_col == i + 1) chr = tok;
+      if (header.pos_col == i + 1) pos = tok;
+      if (header.a1_col == i + 1) a1 = tok;
+      if (header.z_col == i + 1) z = atof(tok.c_str());
+      if (header.beta_col == i + 1) beta = atof(tok.c_str());
+      if (header.sebeta_col == i + 1) se_beta = atof(tok.c_str());
+    }
+    if (header.rs_col == 0) rs = chr + ":" + pos;
+    if (header.z_col != 0) {
+    } else if (header.beta_col != 0 && header.sebeta_col != 0) {
+      z = beta / se_beta;
+    } else {
+      z = 0;
+    }
+    if (mapRS2wA.size() == 0 || mapRS2wA.count(rs) != 0) {
+      mapRS2z[rs] = z;
+      mapRS2A1[rs] = a1;
+    }
+  }
+}
+
+// PARAM::UpdateSNPnZ, src/param.cpp:2353-2416, single-file branch: w, z (negated when the beta file's allele is not the minor
+// allele of the genotype file) and vec_cat of the SNPs that have a weight, in file order; the others leave indicator_snp
+inline void UpdateSNPnZ(const std::vector<SNPINFO> &snpInfo, std::vector<int> &indicator_snp, const std::map<std::string, double> &mapRS2wA,
+                        const std::map<std::string, std::string> &mapRS2A1, const std::map<std::string, double> &mapRS2z,
+                        const std::map<std::string, size_t> &mapRS2cat, std::vector<double> &w, std::vector<double> &z,
+                        std::vector<size_t> &vec_cat) {
+  w.clear();
+  z.clear();
+  vec_cat.clear();
+  for (size_t i = 0; i < snpInfo.size(); i++) {
+    if (indicator_snp[i] == 0) continue;
+    const std::string &rs = snpInfo[i].rs_number, &a1 = snpInfo[i].a_minor;
+    if (mapRS2wA.count(rs) != 0) {
+      if (a1 == mapRS2A1.at(rs)) z.push_back(mapRS2z.at(rs));
+      else z.push_back(-1 * mapRS2z.at(rs));
+      vec_cat.push_back(mapRS2cat.size() == 0 ? 0 : mapRS2cat.at(rs));
+      w.push_back(mapRS2wA.at(rs));
+    } else {
+      indicator_snp[i] = 0;
+    }
+  }
+}
+
+namespace detail {
+inline bool read_numbers(const std::string &file, std::vector<double> &v) {
+  std::ifstream f(file.c_str());
+  if (!f) {
+    std::cout << "error! fail to open file: " << file << std::endl;
+    return false;
+  }
+  v.clear();
+  double d;
+  while (f >> d) v.push_back(d);
+  return true;
+}
+} // namespace detail
+
+// ReadFile_ref, src/gemma_io.cpp:3987-4009: prefix.S.txt (S on top of Svar) and prefix.size.txt (ns per category, then ni)
+inline bool ReadFile_ref(const std::string &file_ref, std::vector<double> &S_mat, std::vector<double> &Svar_mat, std::vector<double> &s_vec,
+                         size_t &ni) {
+  std::vector<double> s, S;
+  if (!detail::read_numbers(file_ref + ".size.txt", s) || !detail::read_numbers(file_ref + ".S.txt", S) || s.size() < 2) return false;
+  const size_t n_vc = s.size() - 1;
+  if (S.size() != 2 * n_vc * n_vc) return false;
+  S_mat.assign(S.begin(), S.begin() + n_vc * n_vc);
+  Svar_mat.assign(S.begin() + n_vc * n_vc, S.end());
+  s_vec.assign(s.begin(), s.begin() + n_vc);
+  ni = (size_t)s[n_vc];
+  return true;
+}
+
+// ReadFile_study, src/gemma_io.cpp:3961-3985: prefix.Vq.txt, prefix.q.txt and prefix.size.txt
+inline bool ReadFile_study(const std::string &file_study, std::vector<double> &Vq_mat, std::vector<double> &q_vec, std::vector<double> &s_vec,
+                           size_t &ni) {
+  std::vector<double> s;
+  if (!detail::read_numbers(file_study + ".size.txt", s) || s.size() < 2) return false;
+  const size_t n_vc = s.size() - 1;
+  if (!detail::read_numbers(file_study + ".Vq.txt", Vq_mat) || !detail::read_numbers(file_study + ".q.txt", q_vec) ||
+      Vq_mat.size() != n_vc * n_vc || q_vec.size() != n_vc)
+    return false;
+  s_vec.assign(s.begin(), s.begin() + n_vc);
+  ni = (size_t)s[n_vc];
+  return true;
+}
+
+// PlinkXwz, src/vc.cpp:2314-2437, for Xz (w = 1) and XWz in ONE pass over the file: the .bed rows of the SNPs with
+// indicator_snp != 0 go to gemma_hip_ci_xwz in blocks.  w == NULL: -ci 1 (XWz = Xz).  Starts the session; Xz, XWz: ni_test x n_vc.
+inline bool PlinkXwz(const std::string &file_bed, const std::vector<int> &indicator_idv, const std::vector<int> &indicator_snp,
+                     const std::vector<size_t> &vec_cat, const std::vector<double> *w, const std::vector<double> &z, const size_t n_vc,
+                     Matrix *Xz, Matrix *XWz, size_t *n_skipped = nullptr) {
+  std::ifstream infile(file_bed.c_str(), std::ios::binary);
+  if (!infile) {
+    std::cout << "error reading bed file:" << file_bed << std::endl;
+    return false;
+  }
+  if (Xz->tda != Xz->size2 || XWz->tda != XWz->size2 || Xz->size2 != n_vc || XWz->size2 != n_vc)
+    throw HipError(GEMMA_HIP_EINVAL, "PlinkXwz: contiguous Xz and XWz (ni_test x n_vc)");
+  const size_t ni_total = indicator_idv.size(), n_bit = (ni_total + 3) / 4;
+  const std::vector<int> cat(vec_cat.begin(), vec_cat.end());
+  enforce_hip(gemma_hip_ci_begin(ni_total, indicator_idv.data(), n_vc), "PlinkXwz");
+  const size_t B = io_block_rows(LMM_BATCH_SIZE);
+  std::vector<unsigned char> block(B * n_bit);
+  size_t t_next = 0, done = 0, skipped = 0;
+  if (n_skipped) *n_skipped = 0;
+  for (;;) {
+    const size_t l = read_bed_rows(infile, indicator_snp, t_next, n_bit, block.data(), B);
+    if (l == (size_t)-1) {
+      std::cout << "error reading bed file:" << file_bed << " (truncated)" << std::endl;
+      return false;
+    }
+    if (l == 0) break;
+    if (done + l > cat.size() || done + l > z.size()) throw HipError(GEMMA_HIP_EINVAL, "PlinkXwz: fewer z-scores than analysed SNPs");
+    enforce_hip(gemma_hip_ci_xwz(GEMMA_GENO_PLINK_2BIT, block.data(), l, n_bit, cat.data() + done, z.data() + done,
+                                 w ? w->data() + done : nullptr, &skipped), "PlinkXwz");
+    if (n_skipped) *n_skipped += skipped;
+    done += l;
+  }
+  enforce_hip(gemma_hip_ci_xwz_end(Xz->data, XWz->data), "PlinkXwz");
+  return true;
+}
+
+// PlinkXtXwz, src/vc.cpp:2568-2688, after PlinkXwz (the finished XWz is on the device): XtXWz is ns_test x n_vc
+inline bool PlinkXtXwz(const std::string &file_bed, const std::vector<int> &indicator_idv, const std::vector<int> &indicator_snp,
+                       const size_t n_vc, Matrix *XtXWz) {
+  std::ifstream infile(file_bed.c_str(), std::ios::binary);
+  if (!infile) {
+    std::cout << "error reading bed file:" << file_bed << std::endl;
+    return false;
+  }
+  if (XtXWz->tda != n_vc || XtXWz->size2 != n_vc) throw HipError(GEMMA_HIP_EINVAL, "PlinkXtXwz: contiguous XtXWz (ns_test x n_vc)");
+  const size_t n_bit = (indicator_idv.size() + 3) / 4, B = io_block_rows(LMM_BATCH_SIZE);
+  std::vector<unsigned char> block(B * n_bit);
+  size_t t_next = 0, done = 0;
+  for (;;) {
+    const size_t l = read_bed_rows(infile, indicator_snp, t_next, n_bit, block.data(), B);
+    if (l == (size_t)-1) {
+      std::cout << "error reading bed file:" << file_bed << " (truncated)" << std::endl;
+      return false;
+    }
+    if (l == 0) break;
+    if (done + l > XtXWz->size1) throw HipError(GEMMA_HIP_EINVAL, "PlinkXtXwz: fewer rows of XtXWz than analysed SNPs");
+    enforce_hip(gemma_hip_ci_xtxwz(GEMMA_GENO_PLINK_2BIT, block.data(), l, n_bit, XtXWz->data + done * n_vc), "PlinkXtXwz");
+    done += l;
+  }
+  return true;
+}
+
+// BimbamXwz, src/vc.cpp:2225-2312, for Xz and XWz in ONE pass over the text file: the rows of the SNPs with indicator_snp != 0 over
+// all ni_total individuals (NaN = NA) go to gemma_hip_ci_xwz in blocks.  The individuals are the ones indicator_idv selects; the
+// reference takes the first ni_test tokens of a line (:2263-2279).
+inline bool BimbamXwz(const std::string &file_geno, const std::vector<int> &indicator_idv, const std::vector<int> &indicator_snp,
+                      const std::vector<size_t> &vec_cat, const std::vector<double> *w, const std::vector<double> &z, const size_t n_vc,
+                      Matrix *Xz, Matrix *XWz, size_t *n_skipped = nullptr) {
+  const size_t ni_total = indicator_idv.size();
+  BimbamReader rd(file_geno, ni_total);
+  if (!rd.ok()) {
+    std::cout << "error reading genotype file:" << file_geno << std::endl;
+    return false;
+  }
+  if (Xz->tda != Xz->size2 || XWz->tda != XWz->size2 || Xz->size2 != n_vc || XWz->size2 != n_vc)
+    throw HipError(GEMMA_HIP_EINVAL, "BimbamXwz: contiguous Xz and XWz (ni_test x n_vc)");
+  const std::vector<int> cat(vec_cat.begin(), vec_cat.end());
+  enforce_hip(gemma_hip_ci_begin(ni_total, indicator_idv.data(), n_vc), "BimbamXwz");
+  const size_t B = bimbam_block_rows(ni_total, LMM_BATCH_SIZE);
+  BlockPrefetch pf(B * ni_total * sizeof(double), [&](void *slot, int) -> size_t {
+    if (rd.lines_read() >= indicator_snp.size()) return 0;
+    return rd.read_block(B, static_cast<double *>(slot), ni_total, nullptr, &indicator_snp);
+  });
+  size_t done = 0, skipped = 0;
+  if (n_skipped) *n_skipped = 0;
+  for (;;) {
+    void *slot = nullptr;
+    const size_t l = pf.next(slot);
+    if (l == (size_t)-1) return false;
+    if (l == 0) break;
+    if (done + l > cat.size() || done + l > z.size()) throw HipError(GEMMA_HIP_EINVAL, "BimbamXwz: fewer z-scores than analysed SNPs");
+    enforce_hip(gemma_hip_ci_xwz(GEMMA_GENO_F64_SNP_MAJOR, slot, l, ni_total, cat.data() + done, z.data() + done,
+                                 w ? w->data() + done : nullptr, &skipped), "BimbamXwz");
+    if (n_skipped) *n_skipped += skipped;
+    done += l;
+  }
+  enforce_hip(gemma_hip_ci_xwz_end(Xz->data, XWz->data), "BimbamXwz");
+  return true;
+}
+
+// BimbamXtXwz, src/vc.cpp:2480-2566, after BimbamXwz: XtXWz is ns_test x n_vc
+inline bool BimbamXtXwz(const std::string &file_geno, const std::vector<int> &indicator_idv, const std::vector<int> &indicator_snp,
+                        const size_t n_vc, Matrix *XtXWz) {
+  const size_t ni_total = indicator_idv.size();
+  BimbamReader rd(file_geno, ni_total);
+  if (!rd.ok()) {
+    std::cout << "error reading genotype file:" << file_geno << std::endl;
+    return false;
+  }
+  if (XtXWz->tda != n_vc || XtXWz->size2 != n_vc) throw HipError(GEMMA_HIP_EINVAL, "BimbamXtXwz: contiguous XtXWz (ns_test x n_vc)");
+  const size_t B = bimbam_block_rows(ni_total, LMM_BATCH_SIZE);
+  BlockPrefetch pf(B * ni_total * sizeof(double), [&](void *slot, int) -> size_t {
+    if (rd.lines_read() >= indicator_snp.size()) return 0;
+    return rd.read_block(B, static_cast<double *>(slot), ni_total, nullptr, &indicator_snp);
+  });
+  size_t done = 0;
+  for (;;) {
+    void *slot = nullptr;
+    const size_t l = pf.next(slot);
+    if (l == (size_t)-1) return false;
+    if (l == 0) break;
+    if (done + l > XtXWz->size1) throw HipError(GEMMA_HIP_EINVAL, "BimbamXtXwz: fewer rows of XtXWz than analysed SNPs");
+    enforce_hip(gemma_hip_ci_xtxwz(GEMMA_GENO_F64_SNP_MAJOR, slot, l, ni_total, XtXWz->data + done * n_vc), "BimbamXtXwz");
+    done += l;
+  }
+  return true;
+}
+
+// CalcCIss, src/vc.cpp:2727-2950, with detail::small_inverse in place of the LU calls
+inline void CalcCIss(const Matrix *Xz, const Matrix *XWz, const Matrix *XtXWz, const Matrix *S_mat, const Matrix *Svar_mat,
+                     const std::vector<double> &w, const std::vector<double> &z, const Vector *s_vec, const std::vector<size_t> &vec_cat,
+                     const std::vector<double> &v_pve, std::vector<double> &v_se_pve, double &pve_total, double &se_pve_total,
+                     std::vector<double> &v_sigma2, std::vector<double> &v_se_sigma2, std::vector<double> &v_enrich,
+                     std::vector<double> &v_se_enrich) {
+  const size_t n_vc = XWz->size2, ns_test = w.size(), ni_test = XWz->size1;
+  auto sv = [&](size_t i) { return s_vec->data[i * s_vec->stride]; };
+  auto at = [](const Matrix *M, size_t i, size_t j) { return M->data[i * M->tda + j]; };
+  std::vector<double> w_pve(ns_test), zwz(n_vc, 0.0), zz(n_vc, 0.0), Xz_pve(ni_test, 0.0), WXtXWz(ns_test);
+  std::vector<double> Si(n_vc * n_vc), Var(n_vc * n_vc, 0.0), qvar(n_vc * n_vc, 0.0);
+  double d, s0, s1, s, s_pve = 0, s_snp = 0;
+  for (size_t i = 0; i < ns_test; i++) {
+    zwz[vec_cat[i]] += z[i] * w[i] * z[i];
+    zz[vec_cat[i]] += z[i] * z[i];
+  }
+  for (size_t i = 0; i < n_vc; i++) {
+    s_pve += v_pve[i];
+    s_snp += sv(i);
+    const double a = v_pve[i] / sv(i);
+    for (size_t k = 0; k < ni_test; k++) Xz_pve[k] += a * at(Xz, k, i);
+  }
+  for (size_t i = 0; i < ns_test; i++) w_pve[i] = v_pve[vec_cat[i]] / sv(vec_cat[i]);
+  s0 = 1 - s_pve;
+  for (size_t i = 0; i < n_vc; i++) s0 += zz[i] * v_pve[i] / sv(i);
+  auto dot_cols = [&](const Matrix *A, size_t i, const Matrix *Bm, size_t j, size_t rows) {
+    double r = 0;
+    for (size_t k = 0; k < rows; k++) r += at(A, k, i) * at(Bm, k, j);
+    return r;
+  };
+  for (size_t i = 0; i < n_vc; i++) {
+    s1 = s0;
+    s1 -= zwz[i] * (1 - s_pve) / sv(i);
+    for (size_t k = 0; k < ns_test; k++) WXtXWz[k] = at(XtXWz, k, i) * w_pve[k];
+    d = 0;
+    for (size_t k = 0; k < ni_test; k++) d += Xz_pve[k] * at(XWz, k, i);
+    s1 -= d / sv(i);
+    for (size_t j = 0; j < n_vc; j++) {
+      s = s1;
+      s -= zwz[j] * (1 - s_pve) / sv(j);
+      d = 0;
+      for (size_t k = 0; k < ns_test; k++) d += WXtXWz[k] * at(XtXWz, k, j);
+      s += d / (sv(i) * sv(j));
+      d = dot_cols(XWz, i, XWz, j, ni_test);
+      s += d / (sv(i) * sv(j)) * (1 - s_pve);
+      d = 0;
+      for (size_t k = 0; k < ni_test; k++) d += Xz_pve[k] * at(XWz, k, j);
+      s -= d / sv(j);
+      qvar[i * n_vc + j] = s;
+    }
+  }
+  d = (double)(ni_test - 1);
+  for (double &v : qvar) v *= 2.0 / (d * d * d);
+  for (size_t i = 0; i < n_vc; i++)
+    for (size_t j = 0; j < n_vc; j++) Si[i * n_vc + j] = at(S_mat, i, j);
+  if (!detail::small_inverse(Si, n_vc)) throw std::runtime_error("CalcCIss: S is singular");
+  for (size_t i = 0; i < n_vc; i++)
+    for (size_t j = i; j < n_vc; j++) {
+      d = at(Svar_mat, i, j);
+      d *= v_pve[i] * v_pve[j];
+      d += qvar[i * n_vc + j];
+      Var[i * n_vc + j] = Var[j * n_vc + i] = d;
+    }
+  Var = detail::matmul(detail::matmul(Si, Var, n_vc), Si, n_vc);
+  v_sigma2.clear();
+  v_enrich.clear();
+  v_se_pve.clear();
+  v_se_sigma2.clear();
+  v_se_enrich.clear();
+  for (size_t i = 0; i < n_vc; i++) {
+    v_sigma2.push_back(v_pve[i] / sv(i));
+    v_enrich.push_back(v_pve[i] / sv(i) * s_snp / s_pve);
+  }
+  for (size_t i = 0; i < n_vc; i++) {
+    d = std::sqrt(Var[i * n_vc + i]);
+    v_se_pve.push_back(d);
+    v_se_sigma2.push_back(d / sv(i));
+  }
+  pve_total = 0;
+  se_pve_total = 0;
+  for (size_t i = 0; i < n_vc; i++) {
+    pve_total += v_pve[i];
+    for (size_t j = 0; j < n_vc; j++) se_pve_total += Var[i * n_vc + j];
+  }
+  se_pve_total = std::sqrt(se_pve_total);
+  std::vector<double> T(n_vc * n_vc);
+  for (size_t i = 0; i < n_vc; i++) {
+    d = v_pve[i] / s_pve;
+    const double d1 = sv(i);
+    for (size_t j = 0; j < n_vc; j++) T[i * n_vc + j] = (i == j ? (1 - d) : -1 * d) / d1 * s_snp / s_pve;
+  }
+  const std::vector<double> VarEnrich = detail::matmul(detail::matmul(T, Var, n_vc), T, n_vc, true);
+  for (size_t i = 0; i < n_vc; i++) v_se_enrich.push_back(std::sqrt(VarEnrich[i * n_vc + i]));
+}
+
+// The estimates of CalcVCss / CalcCIss, as PARAM keeps them
+struct VCEST {
+  std::vector<double> v_pve, v_se_pve, v_sigma2, v_se_sigma2, v_enrich, v_se_enrich;
+  double pve_total = 0, se_pve_total = 0;
+};
+
+// The -beta branch of a_mode 61 / 62 on a PLINK set, src/gemma.cpp:2102-2220: ObtainWeight, UpdateSNP, ReadFile_beta, Calcq, CalcS,
+// CalcVCss -- and for a_mode 62 (ldsc) the second round of :2182-2212: UpdateWeight from the first round's pve, ReadFile_beta and
+// Calcq with those weights, CalcS for A beside the kept K, CalcVCss.  The second CalcS uses slot 2: the reference's PlinkKin adds
+// to the A the first round left.  S: 2 n_vc x n_vc, s: n_vc + 1 (ns per category, then ni_test).
+inline bool CalcVCssBeta(const std::string &file_bed, const std::string &file_beta, const std::vector<int> &indicator_idv,
+                         std::vector<int> &indicator_snp, const std::vector<SNPINFO> &snpInfo, const std::map<std::string, size_t> &mapRS2cat,
+                         const std::map<std::string, std::vector<double>> &mapRS2wcat, const Matrix *W, const size_t n_vc,
+                         const size_t n_block, const bool ldsc, Matrix *S, Matrix *Vq, Vector *q, Vector *s, size_t &ni_study,
+                         size_t &ns_study, size_t &ns_test, VCEST &est) {
+  std::set<std::string> setSnps_beta;
+  if (!ReadFile_snps_header(file_beta, setSnps_beta)) return false;
+  std::map<std::string, double> mapRS2wA, mapRS2wK;
+  ObtainWeight(snpInfo, indicator_snp, setSnps_beta, mapRS2wcat, mapRS2cat, mapRS2wK);
+  UpdateSNP(snpInfo, indicator_snp, mapRS2wK);
+  Matrix S_mat = matrix_view(S->data, n_vc, n_vc), Svar_mat = matrix_view(S->data + n_vc * n_vc, n_vc, n_vc);
+  Vector s_vec = vector_view(s->data, n_vc);
+  std::vector<size_t> vec_cat, vec_ni;
+  std::vector<double> vec_weight, vec_z2;
+  size_t ni_test = 0;
+  for (int v : indicator_idv) ni_test += v != 0;
+  ReadFile_beta(file_beta, mapRS2cat, mapRS2wK, vec_cat, vec_ni, vec_weight, vec_z2, ni_study, ns_study, ns_test);
+  Calcq(n_block, vec_cat, vec_ni, vec_weight, vec_z2, Vq, q, &s_vec);
+  if (!CalcS(file_bed, indicator_idv, indicator_snp, mapRS2wK, mapRS2cat, snpInfo, W, n_vc, S, &s_vec, 0)) return false;
+  CalcVCss(Vq, &S_mat, &Svar_mat, q, &s_vec, (double)ni_study, est.v_pve, est.v_se_pve, est.pve_total, est.se_pve_total, est.v_sigma2,
+           est.v_se_sigma2, est.v_enrich, est.v_se_enrich);
+  if (ldsc) {
+    size_t ns_total = 0;
+    UpdateWeight(1, mapRS2wK, ni_study, &s_vec, est.v_pve, mapRS2wcat, mapRS2cat, mapRS2wA);
+    ReadFile_beta(file_beta, mapRS2cat, mapRS2wA, vec_cat, vec_ni, vec_weight, vec_z2, ni_study, ns_total, ns_test);
+    Calcq(n_block, vec_cat, vec_ni, vec_weight, vec_z2, Vq, q, &s_vec);
+    if (!CalcS(file_bed, indicator_idv, indicator_snp, mapRS2wA, mapRS2cat, snpInfo, W, n_vc, S, &s_vec, 2)) return false;
+    CalcVCss(Vq, &S_mat, &Svar_mat, q, &s_vec, (double)ni_study, est.v_pve, est.v_se_pve, est.pve_total, est.se_pve_total, est.v_sigma2,
+             est.v_se_sigma2, est.v_enrich, est.v_se_enrich);
+  }
+  s->data[n_vc * s->stride] = (double)ni_test;
+  return true;
+}
+
+// -study PREFIX -ref PREFIX without genotypes, src/gemma.cpp:2231-2330: ReadFile_study + ReadFile_ref + CalcVCss with the study's
+// SNP counts and sample size (:2299); the reference panel's counts and ni_ref only go into the size vector it writes (:2305-2307),
+// returned in size_out (n_vc + 1) when given
+inline bool CalcVCssStudy(const std::string &file_study, const std::string &file_ref, VCEST &est, std::vector<double> *size_out = nullptr) {
+  std::vector<double> Vq, q, s_study, S, Svar, s_ref;
+  size_t ni_study = 0, ni_ref = 0;
+  if (!ReadFile_study(file_study, Vq, q, s_study, ni_study) || !ReadFile_ref(file_ref, S, Svar, s_ref, ni_ref) || q.size() != s_ref.size())
+    return false;
+  const size_t n_vc = q.size();
+  Matrix Vm = matrix_view(Vq.data(), n_vc, n_vc), Sm = matrix_view(S.data(), n_vc, n_vc), Sv = matrix_view(Svar.data(), n_vc, n_vc);
+  Vector qv = vector_view(q.data(), n_vc), sv = vector_view(s_study.data(), n_vc);
+  CalcVCss(&Vm, &Sm, &Sv, &qv, &sv, (double)ni_study, est.v_pve, est.v_se_pve, est.pve_total, est.se_pve_total, est.v_sigma2,
+           est.v_se_sigma2, est.v_enrich, est.v_se_enrich);
+  if (size_out) {
+    *size_out = s_ref;
+    size_out->push_back((double)ni_ref);
+  }
+  return true;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
