@@ -35,7 +35,10 @@ SYMBOLS = [
     "gemma_hip_cor_begin", "gemma_hip_cor_block", "gemma_hip_cor_block_d", "gemma_hip_cor_release",
     "gemma_hip_ci_begin", "gemma_hip_ci_xwz", "gemma_hip_ci_xwz_d", "gemma_hip_ci_xwz_end", "gemma_hip_ci_xtxwz",
     "gemma_hip_ci_xtxwz_d", "gemma_hip_ci_release",
+    "gemma_hip_lmm_multi_setup", "gemma_hip_lmm_multi_setup_d", "gemma_hip_lmm_multi_setup_kept", "gemma_hip_lmm_multi_batch",
+    "gemma_hip_lmm_multi_batch_d",
 ]
+LMM_MULTI_MAX = 64
 COMM_ID_BYTES = 128
 
 OK, EINVAL, ENODEV, ENOMEM, ERUNTIME, ESTATE, ENOCONV, ENOTPD = range(8)
@@ -174,6 +177,11 @@ def lib():
     L.gemma_hip_kept_U_get.argtypes = [dp, dp]
     L.gemma_hip_calc_utx_kept.argtypes = [dp, sz, sz, dp]
     L.gemma_hip_lmm_setup_kept.argtypes = [C.POINTER(LmmCfg), dp, dp]
+    L.gemma_hip_lmm_multi_setup.argtypes = [C.POINTER(LmmCfg), sz, dp, dp, dp, dp, dp, dp]
+    L.gemma_hip_lmm_multi_setup_d.argtypes = [C.POINTER(LmmCfg), sz, dp, dp, dp, dp, dp, dp, vp]
+    L.gemma_hip_lmm_multi_setup_kept.argtypes = [C.POINTER(LmmCfg), sz, dp, dp, dp, dp]
+    L.gemma_hip_lmm_multi_batch.argtypes = [ci, vp, sz, sz, vp]
+    L.gemma_hip_lmm_multi_batch_d.argtypes = [ci, vp, sz, sz, vp, vp]
     L.gemma_hip_dbg_i8_digits.argtypes = [sz, C.POINTER(ci)]
     L.gemma_hip_dbg_last_utx_path.argtypes = [C.POINTER(ci)]
     L.gemma_hip_dbg_last_utx_kernel.argtypes = [C.POINTER(UtxKernelInfo)]

@@ -512,6 +512,87 @@ class LMM:
             self.finish()
         return self.sumStat
 
+    # -- T phenotypes over one U^T x (gemma_hip_lmm_multi_*) ----------------------------
+    def setup_multi(self, U, eval_, UtW, UtY, l_mle_null=None, logl_mle_H0=None, plink=False):
+        """lmm_setup for the T columns of UtY (n x T) at once: same individuals, kinship and covariates.  l_mle_null /
+        logl_mle_H0: T values each (a_mode 2, 3, 4, 9); self.l_mle_null / self.logl_mle_H0 are not read."""
+        n = U.shape[0]
+        T = UtY.shape[1]
+        nul = None if l_mle_null is None else np.ascontiguousarray(l_mle_null, dtype=np.float64)
+        lgl = None if logl_mle_H0 is None else np.ascontiguousarray(logl_mle_H0, dtype=np.float64)
+        for v in (nul, lgl):
+            if v is not None and v.size != T:
+                raise ValueError("LMM.setup_multi: %d null values for %d phenotypes" % (v.size, T))
+        pn = _ptr(nul) if nul is not None else None
+        pl = _ptr(lgl) if lgl is not None else None
+        if _is_torch(U):
+            c = UtW.shape[1] if UtW.dim() == 2 else 1
+            cfg = self._cfg(n, c, plink)
+            UtY = UtY.contiguous()
+            self._keep = (U, eval_, UtW, UtY)  # U, eval: borrowed by the library until finish()
+            rc = L.lib().gemma_hip_lmm_multi_setup_d(C.byref(cfg), T, pn, pl, C.c_void_p(U.data_ptr()),
+                                                     C.c_void_p(eval_.data_ptr()), C.c_void_p(UtW.data_ptr()),
+                                                     C.c_void_p(UtY.data_ptr()), _stream())
+        else:
+            UtW = np.ascontiguousarray(UtW, dtype=np.float64).reshape(n, -1)
+            c = UtW.shape[1]
+            cfg = self._cfg(n, c, plink)
+            U_c = _np64(np.ascontiguousarray(U), "U")
+            ev_c = np.ascontiguousarray(eval_, dtype=np.float64)
+            UtY_c = np.ascontiguousarray(UtY, dtype=np.float64)
+            rc = L.lib().gemma_hip_lmm_multi_setup(C.byref(cfg), T, pn, pl, _ptr(U_c), _ptr(ev_c), _ptr(UtW), _ptr(UtY_c))
+        L.check(rc, "LMM.setup_multi")
+        self.ni_test, self.n_cvt, self.n_ph = n, c, T
+        self._active = True
+
+    def batch_multi(self, geno, geno_kind, out=None, l=None, ld=None):
+        """One block of SNPs -> (T, l) SUMSTAT records (numpy), or a (T, l, 8) device tensor (torch): U^T x once, the per-SNP
+        stage per phenotype."""
+        T = self.n_ph
+        if _is_torch(geno):
+            import torch
+            l = geno.shape[0] if l is None else l
+            ld = _tld(geno) if ld is None else ld
+            if out is None:
+                out = torch.empty((T, l, 8), dtype=torch.float64, device=geno.device)
+            rc = L.lib().gemma_hip_lmm_multi_batch_d(geno_kind, C.c_void_p(geno.data_ptr()), l, ld,
+                                                     C.c_void_p(out.data_ptr()), _stream())
+            L.check(rc, "LMM.batch_multi")
+            return out
+        if geno_kind == L.GENO_F64_IDV_MAJOR:
+            l = geno.shape[1] if l is None else l
+        else:
+            l = geno.shape[0] if l is None else l
+        ld = (geno.strides[0] // geno.itemsize) if ld is None else ld
+        if out is None:
+            out = np.zeros((T, l), dtype=SUMSTAT_DTYPE)
+        L.check(L.lib().gemma_hip_lmm_multi_batch(geno_kind, _ptr(geno), l, ld, _ptr(out)), "LMM.batch_multi")
+        return out
+
+    def AnalyzeMulti(self, U, eval_, UtW, UtY, geno, geno_kind=L.GENO_F64_SNP_MAJOR, plink=False, indicator_idv=None,
+                     l_mle_null=None, logl_mle_H0=None, batch=LMM_BATCH_SIZE):
+        """LMM::Analyze for every column of UtY (n x T) over ONE pass of the genotypes: returns (and keeps in self.sumStat) a (T, p)
+        record array, row t what Analyze gives for UtY[:, t].  Nulls that are not given are fitted per phenotype (CalcLambdaNull)."""
+        UtY = np.ascontiguousarray(UtY, dtype=np.float64).reshape(len(eval_), -1)
+        T = UtY.shape[1]
+        if l_mle_null is None or logl_mle_H0 is None:
+            fits = [CalcLambdaNull(eval_, UtW, UtY[:, t], self.l_min, self.l_max, self.n_region) for t in range(T)]
+            if l_mle_null is None:
+                l_mle_null = [f["l_mle_null"] for f in fits]
+            if logl_mle_H0 is None:
+                logl_mle_H0 = [f["logl_mle_H0"] for f in fits]
+        self.setup_multi(U, eval_, UtW, UtY, l_mle_null, logl_mle_H0, plink=plink)
+        try:
+            if indicator_idv is not None:
+                self.set_indicator(indicator_idv)
+            outs = []
+            for s0 in range(0, geno.shape[0], batch):
+                outs.append(self.batch_multi(geno[s0:s0 + batch], geno_kind))
+            self.sumStat = np.concatenate(outs, axis=1) if outs else np.zeros((T, 0), dtype=SUMSTAT_DTYPE)
+        finally:
+            self.finish()
+        return self.sumStat
+
     def AnalyzeBimbam(self, U, eval_, UtW, Uty, X_snpmajor_nan):
         """src/lmm.cpp:1660-1706 with the file reader factored out: X is SNP-major over the analysed
         individuals, NaN = "NA"."""

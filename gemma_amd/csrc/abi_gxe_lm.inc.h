@@ -7,6 +7,7 @@
 extern "C" int gemma_hip_lmm_set_env(const double *env) {
   NEED_INIT();
   if (!g_ctx.lmm_active) return fail(GEMMA_HIP_ESTATE, "lmm_set_env before lmm_setup");
+  NEED_SINGLE("lmm_set_env");
   if (!env) return fail(GEMMA_HIP_EINVAL, "lmm_set_env: null pointer");
   const size_t n = g_ctx.cfg.n, c = g_ctx.cfg.n_cvt;
   if (c + 2 > (size_t)GEN_CMAX_WIDE)
@@ -137,6 +138,7 @@ extern "C" int gemma_hip_dbg_utx(int kind, const void *geno, size_t l, size_t ld
 extern "C" int gemma_hip_lmm_batch(int kind, const void *geno, size_t l, size_t ld, gemma_sumstat *out) {
   NEED_INIT();
   if (!g_ctx.lmm_active) return fail(GEMMA_HIP_ESTATE, "lmm_batch before lmm_setup");
+  NEED_SINGLE("lmm_batch");
   if (l == 0) return GEMMA_HIP_OK;
   const size_t n = g_ctx.cfg.n;
   const size_t per_row = (kind == GEMMA_GENO_PLINK_2BIT && g_ctx.have_map) ? g_ctx.ni_total : n;
@@ -376,6 +378,7 @@ extern "C" int gemma_hip_lmm_finish(double *time_UtX_min, double *time_opt_min) 
   g_ctx.mv_ready = g_ctx.mv_gxe = false;
   g_ctx.gxe_flip.release();
   g_ctx.gxe_ready = false;
+  multi_release();
   g_ctx.U = g_ctx.eval = g_ctx.Uty = nullptr;
   g_ctx.U_even_of = nullptr;
   g_ctx.U_even.release();

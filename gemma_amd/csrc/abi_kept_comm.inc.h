@@ -243,6 +243,7 @@ static void pipe_release() {
 extern "C" int gemma_hip_lmm_batch_submit(int kind, const void *geno, size_t l, size_t ld) {
   NEED_INIT();
   if (!g_ctx.lmm_active) return fail(GEMMA_HIP_ESTATE, "lmm_batch_submit before lmm_setup");
+  NEED_SINGLE("lmm_batch_submit");
   if (g_ctx.pipe_count >= 2) return fail(GEMMA_HIP_ESTATE, "lmm_batch_submit: two blocks already in flight (collect first)");
   if (l == 0) return fail(GEMMA_HIP_EINVAL, "lmm_batch_submit: empty block");
   int dummy = 0;

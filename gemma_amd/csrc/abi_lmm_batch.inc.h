@@ -257,6 +257,7 @@ extern "C" int gemma_hip_lmm_pipe_flush(void *stream) {
 extern "C" int gemma_hip_lmm_batch_pipe_d(int kind, const void *geno, size_t l, size_t ld, gemma_sumstat *out_d, void *stream) {
   NEED_INIT();
   if (!g_ctx.lmm_active) return fail(GEMMA_HIP_ESTATE, "lmm_batch_pipe before lmm_setup");
+  NEED_SINGLE("lmm_batch_pipe");
   if (l == 0) return GEMMA_HIP_OK;
   int rc = check_batch_args("lmm_batch_pipe", kind, geno, l, ld, out_d);
   if (rc) return rc;
@@ -326,6 +327,7 @@ extern "C" int gemma_hip_lmm_batch_d(int kind, const void *geno, size_t l, size_
                                      void *stream) {
   NEED_INIT();
   if (!g_ctx.lmm_active) return fail(GEMMA_HIP_ESTATE, "lmm_batch before lmm_setup");
+  NEED_SINGLE("lmm_batch");
   if (l == 0) return GEMMA_HIP_OK;
   int rc = check_batch_args("lmm_batch", kind, geno, l, ld, out_d);
   if (rc) return rc;
@@ -347,6 +349,7 @@ extern "C" int gemma_hip_lmm_batch_d(int kind, const void *geno, size_t l, size_
 extern "C" int gemma_hip_lmm_gene_batch_d(const double *Y_d, size_t l, size_t ld, gemma_sumstat *out_d, void *stream) {
   NEED_INIT();
   if (!g_ctx.lmm_active) return fail(GEMMA_HIP_ESTATE, "lmm_gene_batch before lmm_setup");
+  NEED_SINGLE("lmm_gene_batch");
   if (l == 0) return GEMMA_HIP_OK;
   const size_t n = g_ctx.cfg.n, c = g_ctx.cfg.n_cvt;
   if (!Y_d || !out_d || ld < n) return fail(GEMMA_HIP_EINVAL, "lmm_gene_batch: ld=%zu < n=%zu", ld, n);
@@ -396,6 +399,7 @@ extern "C" int gemma_hip_lmm_gene_batch_d(const double *Y_d, size_t l, size_t ld
 extern "C" int gemma_hip_lmm_gene_batch(const double *Y, size_t l, size_t ld, gemma_sumstat *out) {
   NEED_INIT();
   if (!g_ctx.lmm_active) return fail(GEMMA_HIP_ESTATE, "lmm_gene_batch before lmm_setup");
+  NEED_SINGLE("lmm_gene_batch");
   if (l == 0) return GEMMA_HIP_OK;
   const size_t n = g_ctx.cfg.n;
   if (!Y || !out || ld < n) return fail(GEMMA_HIP_EINVAL, "lmm_gene_batch: ld=%zu < n=%zu", ld, n);

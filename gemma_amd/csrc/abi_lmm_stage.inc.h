@@ -3,6 +3,34 @@
 // This part: the per-SNP stage of LMM::Analyze: setup (lmm_setup*), fixed-lambda tables, Chebyshev series, launch_assoc.
 
 // ------------------------------------------------------------------------------ LMM
+// Phenotype slots of a multi setup (Ctx::PhenoSlot): the live members <-> a parked slot
+static void slot_swap(Ctx::PhenoSlot &p) {
+  std::swap(g_ctx.assoc_proto, p.proto);
+  std::swap(g_ctx.Uty, p.Uty);
+  std::swap(g_ctx.grid_R, p.grid_R); std::swap(g_ctx.grid_F, p.grid_F);
+  std::swap(g_ctx.cheb_R, p.cheb_R); std::swap(g_ctx.cheb_F, p.cheb_F);
+  std::swap(g_ctx.carry, p.carry);
+  std::swap(g_ctx.carry_flip, p.carry_flip);
+  std::swap(g_ctx.grid_geom, p.grid_geom); std::swap(g_ctx.cheb_geom, p.cheb_geom);
+  std::swap(g_ctx.cheb_mid, p.cheb_mid); std::swap(g_ctx.cheb_inv_half, p.cheb_inv_half);
+  std::swap(g_ctx.cheb_qmask, p.cheb_qmask);
+}
+static void multi_release() {
+  for (auto &p : g_ctx.slots) {
+    p.grid_R.release(); p.grid_F.release(); p.cheb_R.release(); p.cheb_F.release(); p.carry.release();
+  }
+  g_ctx.slots.clear();
+  g_ctx.multi_Yt.release(); g_ctx.multi_R.release(); g_ctx.multi_T_buf.release();
+  g_ctx.multi_T = 0;
+  g_ctx.multi_G = 0;
+}
+// the single-phenotype entry points after a multi setup: the live slot is nobody's
+#define NEED_SINGLE(who)                                                                                                  \
+  do {                                                                                                                    \
+    if (g_ctx.multi_T)                                                                                                    \
+      return fail(GEMMA_HIP_ESTATE, who ": the setup holds %zu phenotypes (gemma_hip_lmm_multi_batch)", g_ctx.multi_T);   \
+  } while (0)
+
 static int lmm_common_setup(const gemma_lmm_cfg *cfg) {
   if (!cfg) return fail(GEMMA_HIP_EINVAL, "lmm_setup: null cfg");
   if (cfg->n == 0 || cfg->n_cvt == 0) return fail(GEMMA_HIP_EINVAL, "lmm_setup: n=%zu n_cvt=%zu", cfg->n, cfg->n_cvt);
@@ -15,6 +43,7 @@ static int lmm_common_setup(const gemma_lmm_cfg *cfg) {
   if (cfg->n <= cfg->n_cvt + 1) return fail(GEMMA_HIP_EINVAL, "lmm_setup: n <= n_cvt + 1");
   if (cfg->n > 0x7fffffffUL) return fail(GEMMA_HIP_EINVAL, "lmm_setup: n too large");
   g_ctx.cfg = *cfg;
+  if (g_ctx.multi_T) multi_release(); // a multi setup that was not finished: its slots go with it
   {
     // the eigensolver's workspace pool (gemma_hip_eigh_reserve / GEMMA_HIP_EIGH_CACHE): a pool that holds more than a quarter of
     // the device would stand in the way of this setup's own buffers (n = 50 000: 100+ GB idle beside 70 GB of digit planes)
@@ -194,16 +223,17 @@ static int make_grid(hipStream_t s) {
 // table_v2_kernel + table_reduce_kernel (lmm_grid.hip.h): T = [X.X | X] * R with RG * 16 rows per wave and the K range cut
 // into slices; tg == nullptr: the dense fixed-lambda table of all l rows, else the per-interval gather tables
 static bool table_v2_enabled() { return g_ctx.knobs.table_v2 != 0; }
+// K slices: a function of n ALONE (a SNP's sums must not depend on the batch it arrives in: sharded == unsharded, and
+// tests/test_gpu_parity.py::test_lmm_reference_xlarge_layout_and_batching compares bits across batch sizes); 16 slices of
+// >= 32 chunks give ~5000 waves for a 20 000-row batch at n = 20 000
+static int table_ksplit(int nc) { return std::max(1, std::min(16, nc / 32)); }
 template <int NBX, int NBA, int RG>
 static int launch_table_v2_t(const GridGeom &gg, const double *UtX, size_t l, size_t ld, const double *R, double *T,
                              const TableGather *tg, int nint, hipStream_t s) {
   constexpr int NB16 = (NBX + NBA) * 16;
   const size_t rows_per_block = (size_t)RG * 16 * 4;
   const size_t bx = (l + rows_per_block - 1) / rows_per_block;
-  // K slices: a function of n ALONE (a SNP's sums must not depend on the batch it arrives in: sharded == unsharded, and
-  // tests/test_gpu_parity.py::test_lmm_reference_xlarge_layout_and_batching compares bits across batch sizes); 16 slices of
-  // >= 32 chunks give ~5000 waves for a 20 000-row batch at n = 20 000
-  const int ksplit = std::max(1, std::min(16, gg.nc / 32));
+  const int ksplit = table_ksplit(gg.nc);
   const size_t planes = tg ? (size_t)nint : 1;
   if (g_ctx.table_P.reserve(planes * (size_t)ksplit * l * NB16 * 8))
     return fail(GEMMA_HIP_ENOMEM, "lmm_assoc: table partial sums (%zu bytes)", planes * (size_t)ksplit * l * NB16 * 8);
@@ -420,7 +450,15 @@ extern "C" int gemma_hip_lmm_set_indicator(const int *indicator_idv, size_t ni_t
   return GEMMA_HIP_OK;
 }
 
-static int launch_assoc(const double *UtX, size_t l, size_t ld, gemma_sumstat *out_d, hipStream_t s) {
+// does a batch of this proto take the fixed-lambda table (and with it the bracket-interval series)?
+static bool assoc_takes_tables(const AssocArgs &a, const double *UtX, size_t ld) {
+  const size_t sel = g_ctx.knobs.force_generic ? 99 : g_ctx.cfg.n_cvt;
+  return a.have_grid && sel <= 4 && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(UtX) & 15) == 0 &&
+         a.a_mode != 3; // mode 3 (score only) never searches lambda
+}
+// shared_T: the live slot's fixed-lambda table of these rows, already computed (launch_table_multi); nullptr: computed here
+static int launch_assoc(const double *UtX, size_t l, size_t ld, gemma_sumstat *out_d, hipStream_t s,
+                        const double *shared_T = nullptr) {
   AssocArgs a = g_ctx.assoc_proto;
   a.UtX = UtX;
   a.ld = (long)ld;
@@ -435,14 +473,13 @@ static int launch_assoc(const double *UtX, size_t l, size_t ld, gemma_sumstat *o
     // GEMMA_HIP_FORCE_GENERIC=1 routes every covariate count through the multi-pass kernel (tests)
     const size_t sel = g_ctx.knobs.force_generic ? 99 : g_ctx.cfg.n_cvt;
     a.grid_T = nullptr;
-    if (a.have_grid && sel <= 4 && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(UtX) & 15) == 0 &&
-        a.a_mode != 3) { // mode 3 (score only) never searches lambda
+    if (assoc_takes_tables(a, UtX, ld)) {
       // The tables are an accelerator, not a requirement: when their buffers do not fit (the K-slice partial sums are
       // planes x slices x l x 80 doubles -- 1.6 GB at l = n = 20000, c = 1) the batch falls back to the streaming evaluations
       // (the round-1 path, same statistics) instead of failing.
-      int rc = launch_grid_table(UtX, l, ld, s);
+      int rc = shared_T ? GEMMA_HIP_OK : launch_grid_table(UtX, l, ld, s);
       if (rc && rc != GEMMA_HIP_ENOMEM) return rc;
-      a.grid_T = rc ? nullptr : g_ctx.grid_T.as<double>();
+      a.grid_T = rc ? nullptr : (shared_T ? shared_T : g_ctx.grid_T.as<double>());
       a.cheb_T = nullptr;
       a.cheb_slots = nullptr;
       a.cheb_res = nullptr;
@@ -496,6 +533,7 @@ extern "C" int gemma_hip_lmm_assoc_d(const double *UtX_d, size_t l, size_t ld_ut
                                      void *stream) {
   NEED_INIT();
   if (!g_ctx.lmm_active) return fail(GEMMA_HIP_ESTATE, "lmm_assoc before lmm_setup");
+  NEED_SINGLE("lmm_assoc");
   if (l == 0) return GEMMA_HIP_OK;
   if (!UtX_d || !out_d || ld_utx < g_ctx.cfg.n) return fail(GEMMA_HIP_EINVAL, "lmm_assoc: bad UtX/ld");
   {

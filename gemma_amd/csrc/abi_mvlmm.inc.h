@@ -147,6 +147,7 @@ extern "C" int gemma_hip_mvlmm_set(size_t d, const double *UtY, const gemma_mvlm
   NEED_INIT();
   g_ctx.knobs.load();
   if (!g_ctx.lmm_active) return fail(GEMMA_HIP_ESTATE, "mvlmm_set before lmm_setup");
+  NEED_SINGLE("mvlmm_set");
   if (!UtY || !nf) return fail(GEMMA_HIP_EINVAL, "mvlmm_set: null pointer");
   gemma_mvlmm_opt o;
   mv_default_opt(o, opt);

@@ -65,6 +65,7 @@ struct Knobs {
   int overlap_chunks = 4;  // GEMMA_HIP_OVERLAP_CHUNKS
   int table_v2 = 1;        // GEMMA_HIP_TABLE_V2
   int table_pf = 0;        // GEMMA_HIP_TABLE_PF
+  int multi_table = 1;     // GEMMA_HIP_MULTI_TABLE: 0 = gemma_hip_lmm_multi_batch computes every phenotype's fixed-lambda table on its own
   int force_generic = 0;   // GEMMA_HIP_FORCE_GENERIC
   int assoc_variant = 44;  // GEMMA_HIP_ASSOC_VARIANT
   int mvlmm_rt = 0;        // GEMMA_HIP_MVLMM_RT
@@ -105,6 +106,8 @@ struct Knobs {
     table_v2 = (et && et[0] == '0') ? 0 : 1;
     const char *ep = getenv("GEMMA_HIP_TABLE_PF");
     table_pf = (ep && ep[0] == '1') ? 1 : 0;
+    const char *em = getenv("GEMMA_HIP_MULTI_TABLE");
+    multi_table = (em && em[0] == '0') ? 0 : 1;
     const char *eg = getenv("GEMMA_HIP_FORCE_GENERIC");
     force_generic = (eg && eg[0] == '1') ? 1 : 0;
     assoc_variant = geti("GEMMA_HIP_ASSOC_VARIANT", 44);
@@ -220,6 +223,24 @@ struct Ctx {
   GridGeom grid_geom;
   int carry_flip = 0;
   AssocArgs assoc_proto;
+  // What of a setup belongs to the PHENOTYPE (gemma_hip_lmm_multi_setup): the members above of the same names are the live slot --
+  // the only one of a single-phenotype setup -- and slot_swap() exchanges them with a parked one around the per-SNP stage of that
+  // phenotype.  Everything else of the setup (U and its digit planes, eval, UtWt, the log-determinant ends inside the proto, idx_map,
+  // cheb_iv / cheb_D / cheb_Ck..Lk, the per-batch buffers) exists once.
+  struct PhenoSlot {
+    AssocArgs proto;               // with its own l_mle_null / logl_mle_H0 and the pointers into this slot's tables
+    const double *Uty = nullptr;
+    DevBuf grid_R, grid_F, cheb_R, cheb_F, carry;
+    GridGeom grid_geom, cheb_geom;
+    double cheb_mid[ASSOC_MAX_REGION], cheb_inv_half[ASSOC_MAX_REGION];
+    unsigned long long cheb_qmask = 0;
+    int carry_flip = 0;
+  };
+  std::vector<PhenoSlot> slots;    // multi setup: T parked slots (the live members are then nobody's)
+  size_t multi_T = 0;              // 0: single-phenotype setup
+  DevBuf multi_Yt;                 // U^T Y transposed (T x n): slot t's Uty is row t
+  DevBuf multi_R, multi_T_buf;     // shared table: a group's weight matrix (one per group, back to back) and its G tables
+  int multi_G = 0;                 // phenotypes per pass of the shared table product (0: no shared table for this setup)
 
   // linear model (-lm) state
   bool lm_active = false;
@@ -395,6 +416,10 @@ extern "C" void gemma_hip_shutdown(void) {
   g_ctx.i8_mean.release(); g_ctx.i8_meta.release(); g_ctx.i8_rowsur.release(); g_ctx.i8_colsum.release(); g_ctx.i8_surlist.release();
   g_ctx.i8_ready = g_ctx.i8_colsum_ready = false;
   g_ctx.table_P.release(); g_ctx.U_even.release();
+  for (auto &p : g_ctx.slots) { p.grid_R.release(); p.grid_F.release(); p.cheb_R.release(); p.cheb_F.release(); p.carry.release(); }
+  g_ctx.slots.clear();
+  g_ctx.multi_Yt.release(); g_ctx.multi_R.release(); g_ctx.multi_T_buf.release();
+  g_ctx.multi_T = 0;
   g_ctx.U_even_of = nullptr;
   pipe_release(); // pinned slots, copy stream and events of the pipelined host-block path
   xp_release();
@@ -525,6 +550,7 @@ extern "C" int gemma_hip_dgemm(char ta, char tb, size_t M, size_t N, size_t K, d
 #include "abi_mvlmm.inc.h"
 #include "abi_gxe_lm.inc.h"
 #include "abi_kept_comm.inc.h"
+#include "abi_lmm_multi.inc.h"
 #include "abi_vc.inc.h"
 #include "abi_prdt.inc.h"
 #include "abi_mqs.inc.h"

@@ -343,6 +343,77 @@ __global__ __launch_bounds__(256) void table_reduce_kernel(const double *__restr
     T[row * nb16 + col] = v;
 }
 
+// ---- the dense fixed-lambda tables of a GROUP of phenotypes from one read of U^T x (gemma_hip_lmm_multi_batch).  Of the columns
+// of [X.X | X] * R only the nq columns x . y_t w_q belong to a phenotype; the weight matrix of a group is
+//   [ x.x : NBX blocks | x . w_a : c * nq columns | x . y_1 : nq | ... | x . y_G : nq ]   (the x . u group packed, MULTI_NBA blocks)
+// in the operand order of grid_weights_kernel, and the product is table_v2_kernel<2, MULTI_NBA, MULTI_RG> ITSELF on that matrix
+// (one body: a wrapper around a shared device function changed the code generated for the existing instantiations).
+// An entry of a table is one row of U^T x against one weight column over one k sequence -- the chunk order, the k order inside a
+// chunk, the K slices (a function of n alone) and the slice-order sum are table_v2_kernel's and table_reduce_kernel's -- so every
+// entry is the same bits as the phenotype's own table_v2_kernel + table_reduce_kernel give, whichever column block it sits in
+// and however many row groups the wave holds.
+// table_multi_reduce_kernel sums the slices and scatters the columns into G tables of the single-phenotype layout (grid_ld,
+// grid_xa0, columns a * nq + q): the y columns of a phenotype start at c * nq, no multiple of 16, and straddle column blocks.
+// The accumulator budget is that instantiation's, the one c = 4 runs today (2 row groups x 10 column blocks of
+// v_mfma_f64_16x16x4_f64: 160 accumulator registers of 256): 128 columns of the x . u group hold c + G <= 5 vectors.
+constexpr int MULTI_NBA = 8, MULTI_RG = 2, MULTI_GMAX = 4;
+struct MultiWeights {
+  const double *Uty[MULTI_GMAX];
+  int G;
+};
+__global__ void grid_weights_multi_kernel(AssocArgs g, GridGeom gg, int c, MultiWeights mw, double *__restrict__ Rp) {
+  const int nb = gg.nbx + MULTI_NBA;
+  const long total = (long)gg.nc * nb * 256;
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const int j = (int)(e & 3), col = (int)((e >> 2) & 15), kq = (int)((e >> 6) & 3);
+  const long r = e >> 8;
+  const int cb = (int)(r % nb);
+  const long chunk = r / nb;
+  const long k = chunk * 16 + 4 * kq + j;
+  double v = 0.0;
+  if (k < g.n) {
+    if (cb < gg.nbx) {
+      const int q = cb * 16 + col;
+      if (q < gg.nq) v = grid_weight(g.eval, g.lam_grid, q, k);
+    } else {
+      const int idx = (cb - gg.nbx) * 16 + col;
+      const int a = idx / gg.nq, q = idx - a * gg.nq;
+      if (a < c + mw.G) {
+        const double u = (a < c) ? g.UtWt[(long)a * g.n + k] : mw.Uty[a - c][k];
+        v = u * grid_weight(g.eval, g.lam_grid, q, k);
+      }
+    }
+  }
+  Rp[e] = v;
+}
+struct TableMulti {
+  const double *P; // partial sums of the product: [ks * cap + row] * nb16m + col
+  int ksplit;
+  long cap, l;
+  int nb16m;       // columns of P
+  int nb16;        // columns of one phenotype's table (grid_ld)
+  int y0, nq;      // a table's y columns: [y0, y0 + nq); phenotype g of the group has them at y0 + g * nq in P
+  double *T;       // G tables, tstride doubles apart
+  long tstride;
+};
+// grid = (ceil(l * nb16 / 256), G)
+__global__ __launch_bounds__(256) void table_multi_reduce_kernel(TableMulti m) {
+  const int g = blockIdx.y;
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= m.l * m.nb16) return;
+  const long row = e / m.nb16;
+  const int col = (int)(e - row * m.nb16);
+  int src = col;
+  if (col >= m.y0) src = (col - m.y0 < m.nq) ? col + g * m.nq : -1; // behind the y columns: the zero padding of the last block
+  double v = 0.0;
+  if (src >= 0) {
+    const double *p = m.P + row * m.nb16m + src;
+    for (int ks = 0; ks < m.ksplit; ++ks) v += p[(long)ks * m.cap * m.nb16m];
+  }
+  m.T[(long)g * m.tstride + row * m.nb16 + col] = v;
+}
+
 // ------------------------------------------------------------------ Chebyshev tables of the bracket intervals
 // (lmm_search.hip.h).  Per lmm_setup and interval: c_k(delta_i), the series coefficients of t -> H_i(t) and of
 // t -> 1 - H_i(t) (cheb_coeff_kernel), from them the weight matrix of the table product in MFMA operand order

@@ -241,6 +241,33 @@ int gemma_hip_lmm_assoc_d(const double *UtX_d, size_t l, size_t ld_utx, gemma_su
  * minutes, the unit of LMM::time_UtX / time_opt (src/lmm.cpp:1523,1556) */
 int gemma_hip_lmm_finish(double *time_UtX_min, double *time_opt_min);
 
+/* ---- T univariate LMMs over one U^T x (trait panels) ------------------------------------------------------ */
+/* T phenotypes on the same individuals, kinship and covariates: a block is ingested and rotated (U^T x) ONCE and the per-SNP
+ * stage of LMM::Analyze runs for every phenotype.  The records of phenotype t are, bit for bit, those of gemma_hip_lmm_setup with
+ * column t of UtY and cfg's null fields set to l_mle_null[t] / logl_mle_H0[t], followed by gemma_hip_lmm_batch on the same blocks
+ * in the same order (each phenotype has its own PLINK beta / se carry chain).  The scan runs on ONE set of analysed individuals:
+ * per-phenotype missingness is not supported -- the caller analyses the individuals that have every phenotype (and covariate), as
+ * the reference does for `-n a b c` (ProcessCvtPhen).
+ * UtY: n x T row-major (the layout gemma_hip_mvlmm_null takes); l_mle_null / logl_mle_H0: T values each (read for a_mode 2/3/4/9 as
+ * cfg's two fields are; may be NULL for a_mode 1); cfg's own two null fields are ignored.  T = 1..GEMMA_LMM_MULTI_MAX, else
+ * GEMMA_HIP_EINVAL; tables that do not fit: GEMMA_HIP_ENOMEM with the byte count in the message.  gemma_hip_lmm_set_indicator and
+ * gemma_hip_lmm_finish serve both forms; a single-phenotype batch entry point after a multi setup, and a multi batch after a
+ * single-phenotype setup, return GEMMA_HIP_ESTATE.  No multi form of -gxe, -gene, batch_pipe_d, batch_submit / collect, mvLMM.
+ * The fixed-lambda tables of up to 5 - n_cvt phenotypes at a time come from one read of U^T x (GEMMA_HIP_MULTI_TABLE=0: one read
+ * per phenotype; the same bits either way). */
+#define GEMMA_LMM_MULTI_MAX 64
+int gemma_hip_lmm_multi_setup(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null, const double *logl_mle_H0,
+                              const double *U, const double *eval, const double *UtW, const double *UtY);
+/* device pointers; U_d and eval_d are borrowed until gemma_hip_lmm_finish, UtW_d and UtY_d are read by work queued on `stream` */
+int gemma_hip_lmm_multi_setup_d(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null, const double *logl_mle_H0,
+                                const double *U_d, const double *eval_d, const double *UtW_d, const double *UtY_d, void *stream);
+/* on the kept U (gemma_hip_eigh_kept_K / gemma_hip_eigh_keep); UtW, UtY: host */
+int gemma_hip_lmm_multi_setup_kept(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null, const double *logl_mle_H0,
+                                   const double *UtW, const double *UtY);
+/* one block: ingest + U^T x once, then the per-SNP stage for every phenotype.  out: T x l records, phenotype-major (out[t * l + s]). */
+int gemma_hip_lmm_multi_batch(int geno_kind, const void *geno, size_t l, size_t ld, gemma_sumstat *out);
+int gemma_hip_lmm_multi_batch_d(int geno_kind, const void *geno_d, size_t l, size_t ld, gemma_sumstat *out_d, void *stream);
+
 /* ---- multivariate LMM (-lmm 1..4 -n a b c ...) ------------------------------------ */
 /* MVLMM::AnalyzeBimbam / AnalyzePlink, src/mvlmm.cpp:2972-3416 / :3418-3899, and with opt->gxe the interaction test of
  * AnalyzeBimbamGXE / AnalyzePlinkGXE (:3970-4414 / :4416-4870).  d phenotypes (1..GEMMA_MV_DMAX), n_cvt covariates with

@@ -721,6 +721,65 @@ public:
     finish();
   }
 
+  // ---- T univariate scans over ONE pass of the genotypes (gemma_hip_lmm_multi_*; the reference runs `-n t` once per trait) ----
+  // UtY: ni_test x T (column t = U^T y_t), l_mle_null_multi / logl_mle_H0_multi: the T null fits (CalcLambdaNull per column; read
+  // for a_mode 2, 3, 4, 9).  One set of analysed individuals: those that have every phenotype.  sumStatMulti[t] is what Analyze*
+  // leaves in sumStat for phenotype t, bit for bit; WriteFilesMulti writes it through WriteFiles.
+  std::vector<std::vector<SUMSTAT>> sumStatMulti;
+  std::vector<double> l_mle_null_multi, logl_mle_H0_multi;
+
+  void AnalyzePlinkMulti(const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY) {
+    const std::string file_bed = file_bfile + ".bed";
+    std::ifstream infile(file_bed.c_str(), std::ios::binary);
+    if (!infile) throw std::runtime_error("error reading genotype (.bed) file");
+    const size_t T = setup_multi(U, eval, UtW, UtY, 1);
+    enforce_hip(gemma_hip_lmm_set_indicator(indicator_idv.data(), indicator_idv.size()), "AnalyzePlinkMulti");
+    const size_t n_bit = (ni_total + 3) / 4;
+    const size_t B = io_block_rows(LMM_BATCH_SIZE);
+    std::vector<gemma_sumstat> out(T * B);
+    size_t t_next = 0;
+    const std::vector<int> keep = analysed_snps();
+    BlockPrefetch pf(B * n_bit, [&](void *slot, int) {
+      return read_bed_rows(infile, keep, t_next, n_bit, static_cast<unsigned char *>(slot), B);
+    });
+    for (;;) {
+      void *slot = nullptr;
+      const size_t l = pf.next(slot);
+      if (l == (size_t)-1) throw std::runtime_error("error reading genotype (.bed) file (truncated)");
+      if (l == 0) break;
+      batch_compute_multi(GEMMA_GENO_PLINK_2BIT, slot, l, n_bit, out);
+    }
+    finish();
+  }
+
+  // the pull-style block source of AnalyzeFeed (include/gemma_io_host.hpp: AnalyzeBimbamMulti feeds it from the text file)
+  void AnalyzeFeedMulti(const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY, RowFeeder &feed,
+                        size_t max_rows, size_t ld) {
+    const size_t T = setup_multi(U, eval, UtW, UtY, 0);
+    std::vector<gemma_sumstat> out(T * max_rows);
+    for (;;) {
+      const double *X = nullptr;
+      const size_t l = feed(X);
+      if (l == 0) break;
+      if (l > max_rows) throw HipError(GEMMA_HIP_EINVAL, "AnalyzeFeedMulti: block larger than max_rows");
+      batch_compute_multi(GEMMA_GENO_F64_SNP_MAJOR, X, l, ld, out);
+    }
+    finish();
+  }
+
+  // one .assoc.txt per phenotype: path_out/names[t].assoc.txt, each what WriteFiles writes for a single-phenotype run
+  void WriteFilesMulti(const std::vector<std::string> &names) {
+    if (names.size() != sumStatMulti.size()) throw HipError(GEMMA_HIP_EINVAL, "WriteFilesMulti: one name per phenotype");
+    const std::string keep_out = file_out;
+    for (size_t t = 0; t < names.size(); ++t) {
+      file_out = names[t];
+      sumStat.swap(sumStatMulti[t]);
+      WriteFiles();
+      sumStat.swap(sumStatMulti[t]);
+    }
+    file_out = keep_out;
+  }
+
   // WriteFiles, src/lmm.cpp:101-225
   void WriteFiles() {
     const std::string file_str = path_out + "/" + file_out + ".assoc.txt";
@@ -778,6 +837,37 @@ private:
     else
       enforce_hip(gemma_hip_lmm_setup(&cfg, U->data, eval->data, UtW->data, Uty->data), "LMM::Analyze");
     sumStat.clear();
+  }
+  size_t setup_multi(const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY, int plink) {
+    if ((!kept_U && U->tda != U->size2) || UtW->tda != UtW->size2 || eval->stride != 1 || UtY->tda != UtY->size2)
+      throw HipError(GEMMA_HIP_EINVAL, "LMM: contiguous U/UtW/eval/UtY required");
+    if (shard_world > 1) throw HipError(GEMMA_HIP_EINVAL, "LMM: the multi-phenotype scan is not sharded over ranks");
+    const size_t T = UtY->size2;
+    if (a_mode != 1 && (l_mle_null_multi.size() != T || logl_mle_H0_multi.size() != T))
+      throw HipError(GEMMA_HIP_EINVAL, "LMM: l_mle_null_multi / logl_mle_H0_multi need one value per phenotype");
+    ni_test = UtY->size1;
+    n_cvt = UtW->size2;
+    gemma_lmm_cfg cfg;
+    cfg.a_mode = a_mode; cfg.n = ni_test; cfg.n_cvt = n_cvt; cfg.l_min = l_min; cfg.l_max = l_max;
+    cfg.n_region = n_region; cfg.l_mle_null = 0.0; cfg.logl_mle_H0 = 0.0; cfg.plink_nan_rule = plink;
+    const double *nul = l_mle_null_multi.size() == T ? l_mle_null_multi.data() : nullptr;
+    const double *lgl = logl_mle_H0_multi.size() == T ? logl_mle_H0_multi.data() : nullptr;
+    if (kept_U)
+      enforce_hip(gemma_hip_lmm_multi_setup_kept(&cfg, T, nul, lgl, UtW->data, UtY->data), "LMM::AnalyzeMulti");
+    else
+      enforce_hip(gemma_hip_lmm_multi_setup(&cfg, T, nul, lgl, U->data, eval->data, UtW->data, UtY->data), "LMM::AnalyzeMulti");
+    sumStatMulti.assign(T, std::vector<SUMSTAT>());
+    return T;
+  }
+  void batch_compute_multi(int kind, const void *geno, size_t l, size_t ld, std::vector<gemma_sumstat> &out) {
+    if (l == 0) return;
+    enforce_hip(gemma_hip_lmm_multi_batch(kind, geno, l, ld, out.data()), "batch_compute (multi)");
+    for (size_t t = 0; t < sumStatMulti.size(); ++t)
+      for (size_t i = 0; i < l; ++i) {
+        const gemma_sumstat &o = out[t * l + i];
+        SUMSTAT s = {o.beta, o.se, o.lambda_remle, o.lambda_mle, o.p_wald, o.p_lrt, o.p_score, o.logl_H1};
+        sumStatMulti[t].push_back(s);
+      }
   }
   // batch_compute, src/lmm.cpp:1513-1564
   void batch_compute(int kind, const void *geno, size_t l, size_t ld, std::vector<gemma_sumstat> &out) {

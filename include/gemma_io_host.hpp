@@ -927,6 +927,27 @@ inline void AnalyzeBimbam(LMM &lmm, const Matrix *U, const Vector *eval, const M
   lmm.AnalyzeFeed(U, eval, UtW, Uty, feed, B, n);
 }
 
+// the same for T phenotypes over one pass of the file (LMM::AnalyzeFeedMulti)
+inline void AnalyzeBimbamMulti(LMM &lmm, const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY) {
+  const size_t ni_total = lmm.indicator_idv.size(), n = UtY->size1;
+  BimbamReader rd(lmm.file_geno, ni_total);
+  if (!rd.ok()) throw std::runtime_error("error reading genotype file");
+  const size_t B = bimbam_block_rows(n, LMM_BATCH_SIZE);
+  const std::vector<int> keep = lmm.analysed_snps();
+  BlockPrefetch pf(B * n * sizeof(double), [&](void *slot, int) -> size_t {
+    if (rd.lines_read() >= keep.size()) return 0;
+    return rd.read_block(B, static_cast<double *>(slot), n, nullptr, &keep, lmm.indicator_idv.data());
+  });
+  LMM::RowFeeder feed = [&](const double *&X) -> size_t {
+    void *slot = nullptr;
+    const size_t l = pf.next(slot);
+    if (l == (size_t)-1) throw std::runtime_error("Problem reading geno file (not enough genotypes in line)");
+    X = static_cast<const double *>(slot);
+    return l;
+  };
+  lmm.AnalyzeFeedMulti(U, eval, UtW, UtY, feed, B, n);
+}
+
 // MVLMM::AnalyzeBimbam, src/mvlmm.cpp:2972-3416, over the same threaded reader (mv.file_geno, mv.indicator_idv / _snp)
 inline void AnalyzeBimbam(MVLMM &mv, const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY) {
   const size_t ni_total = mv.indicator_idv.size(), n = U->size1;
