@@ -35,7 +35,7 @@ def _is_torch(x):
 def _np64(a, name):
     if not isinstance(a, np.ndarray) or a.dtype != np.float64:
         raise TypeError("%s must be a float64 numpy array" % name)
-    if a.ndim == 2 and a.strides[1] != 8:
+    if a.ndim == 2 and a.size and a.strides[1] != 8:  # (numpy gives an empty array strides of 0: K == 0 is C = beta C)
         raise ValueError("%s must be row-major with unit column stride" % name)
     return a
 
@@ -54,7 +54,7 @@ def _stream():
 
 
 def _tld(t):
-    if t.dim() != 2 or t.stride(1) != 1:
+    if t.dim() != 2 or (t.numel() and t.stride(1) != 1):  # (an empty tensor's strides may be 0)
         raise ValueError("device matrices must be 2-D row-major")
     return t.stride(0) if t.shape[0] > 1 else t.shape[1]
 
