@@ -29,7 +29,7 @@ SYMBOLS = [
     "gemma_hip_ridge_setup", "gemma_hip_ridge_setup_d", "gemma_hip_ridge_setup_kept", "gemma_hip_ridge_set_r",
     "gemma_hip_ridge_set_indicator", "gemma_hip_ridge_batch", "gemma_hip_ridge_batch_d", "gemma_hip_ridge_finish",
     "gemma_hip_prdt_begin", "gemma_hip_prdt_add", "gemma_hip_prdt_add_d", "gemma_hip_prdt_add_bv", "gemma_hip_prdt_add_bv_d",
-    "gemma_hip_prdt_end", "gemma_hip_prdt_kin",
+    "gemma_hip_prdt_end", "gemma_hip_prdt_kin", "gemma_hip_prdt_kin_mv_apply", "gemma_hip_prdt_kin_mv_apply_d", "gemma_hip_prdt_kin_mv",
     "gemma_hip_mqs_begin", "gemma_hip_mqs_add", "gemma_hip_mqs_add_d", "gemma_hip_mqs_end", "gemma_hip_mqs_get",
     "gemma_hip_mqs_S", "gemma_hip_mqs_S_d", "gemma_hip_mqs_release",
     "gemma_hip_cor_begin", "gemma_hip_cor_block", "gemma_hip_cor_block_d", "gemma_hip_cor_release",
@@ -222,6 +222,9 @@ def lib():
     L.gemma_hip_prdt_add_bv_d.argtypes = [dp, sz, sz, dp, sz, vp]
     L.gemma_hip_prdt_end.argtypes = [cd, ci, dp]
     L.gemma_hip_prdt_kin.argtypes = [sz, dp, vp, dp, sz, dp, cd, cd, sz, dp, dp]
+    L.gemma_hip_prdt_kin_mv_apply.argtypes = [sz, sz, dp, vp, dp, sz, dp, dp, dp, dp, dp]
+    L.gemma_hip_prdt_kin_mv_apply_d.argtypes = [sz, sz, dp, sz, vp, dp, sz, dp, dp, dp, dp, dp, vp]
+    L.gemma_hip_prdt_kin_mv.argtypes = [sz, sz, dp, vp, dp, sz, dp, cd, cd, sz, C.POINTER(MvOpt), dp, C.POINTER(MvNull)]
     L.gemma_hip_mqs_begin.argtypes = [sz, vp, sz, dp, sz, ci]
     L.gemma_hip_mqs_add.argtypes = [ci, vp, sz, sz, vp, dp]
     L.gemma_hip_mqs_add_d.argtypes = [ci, vp, sz, sz, vp, dp, vp]

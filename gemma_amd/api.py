@@ -1157,6 +1157,71 @@ class PRDT:
         return Y, dict(vg=fit[0], ve=fit[1], l_remle=fit[2])
 
     @staticmethod
+    def _mv_args(G_full, indicator_pheno, W_full, Y_full):
+        ind = np.ascontiguousarray(indicator_pheno, dtype=np.int32)
+        if ind.ndim != 2:
+            raise ValueError("indicator_pheno must be ni x d")
+        ni, d = ind.shape
+        W_c = np.ascontiguousarray(np.asarray(W_full, dtype=np.float64).reshape(ni, -1))
+        Y_c = np.ascontiguousarray(Y_full, dtype=np.float64)
+        if Y_c.shape != (ni, d):
+            raise ValueError("Y_full must be %d x %d" % (ni, d))
+        if _is_torch(G_full):
+            if tuple(G_full.shape) != (ni, ni):
+                raise ValueError("G_full must be %d x %d" % (ni, ni))
+            G_c = G_full
+        else:
+            G_c = _np64(np.ascontiguousarray(G_full), "G_full")
+            if G_c.shape != (ni, ni):
+                raise ValueError("G_full must be %d x %d" % (ni, ni))
+        return ind, ni, d, G_c, W_c, Y_c, np.zeros(max(int((ind == 0).sum()), 1))
+
+    @staticmethod
+    def _mv_fill(Y_c, ind, y_miss):
+        Y = Y_c.copy()
+        Y[ind == 0] = y_miss[:int((ind == 0).sum())]  # boolean assignment runs in row-major order: i * d + a
+        return Y
+
+    @staticmethod
+    def MvnormApply(G_full, indicator_pheno, W_full, Y_full, Vg, Ve, B):
+        """The Kronecker system of a_mode 43 alone, for given Vg, Ve (d x d) and B (d x n_cvt): every unobserved (i, a) is
+        predicted from the observed entries through H = Gc (x) Vg + I (x) Ve (the else branch of src/gemma.cpp:1821-1871 with
+        PRDT::MvnormPrdt) without H_full.  G_full: numpy, or a torch tensor on the device (not changed).  Returns Y_full with the
+        missing entries filled."""
+        ind, ni, d, G_c, W_c, Y_c, y_miss = PRDT._mv_args(G_full, indicator_pheno, W_full, Y_full)
+        c = W_c.shape[1]
+        Vg_c, Ve_c = (np.ascontiguousarray(M, dtype=np.float64) for M in (Vg, Ve))
+        B_c = np.ascontiguousarray(np.asarray(B, dtype=np.float64).reshape(d, -1))
+        if Vg_c.shape != (d, d) or Ve_c.shape != (d, d) or B_c.shape != (d, c):
+            raise ValueError("Vg, Ve must be %d x %d and B %d x %d" % (d, d, d, c))
+        if _is_torch(G_c):
+            rc = L.lib().gemma_hip_prdt_kin_mv_apply_d(ni, d, C.c_void_p(G_c.data_ptr()), _tld(G_c), _ptr(ind), _ptr(W_c), c, _ptr(Y_c),
+                                                       _ptr(Vg_c), _ptr(Ve_c), _ptr(B_c), _ptr(y_miss), _stream())
+        else:
+            rc = L.lib().gemma_hip_prdt_kin_mv_apply(ni, d, _ptr(G_c), _ptr(ind), _ptr(W_c), c, _ptr(Y_c), _ptr(Vg_c), _ptr(Ve_c),
+                                                     _ptr(B_c), _ptr(y_miss))
+        L.check(rc, "PRDT.MvnormApply")
+        return PRDT._mv_fill(Y_c, ind, y_miss)
+
+    @staticmethod
+    def MvnormPrdtMulti(G_full, indicator_pheno, W_full, Y_full, l_min=1e-5, l_max=1e5, n_region=10, em_iter=10000, nr_iter=100,
+                        em_prec=1e-4, nr_prec=1e-4):
+        """-predict from a kinship alone (a_mode 43) for several phenotypes, the whole block of src/gemma.cpp:1732-1897: the null
+        model is fitted on the individuals with every trait (their kinship centred and decomposed, the REMLE fit of
+        CalcMvLmmVgVeBeta), then every missing (individual, trait) entry is predicted.  indicator_pheno, Y_full: ni x d.
+        Returns (Y_full with the missing entries filled, dict(Vg, Ve, B, logl_remle))."""
+        ind, ni, d, G_c, W_c, Y_c, y_miss = PRDT._mv_args(G_full, indicator_pheno, W_full, Y_full)
+        if _is_torch(G_c):
+            raise TypeError("G_full must be a numpy array (MvnormApply takes a device matrix)")
+        c = W_c.shape[1]
+        opt, nf = L.MvOpt(em_iter, nr_iter, em_prec, nr_prec, 1e-3, 0, 0), L.MvNull()
+        L.check(L.lib().gemma_hip_prdt_kin_mv(ni, d, _ptr(G_c), _ptr(ind), _ptr(W_c), c, _ptr(Y_c), l_min, l_max, n_region,
+                                              C.byref(opt), _ptr(y_miss), C.byref(nf)), "PRDT.MvnormPrdtMulti")
+        g = lambda a, r, k: np.array(a[:r * k]).reshape(r, k)
+        return PRDT._mv_fill(Y_c, ind, y_miss), dict(Vg=g(nf.Vg_remle, d, d), Ve=g(nf.Ve_remle, d, d), B=g(nf.B_remle, d, c),
+                                                     logl_remle=nf.logl_remle_H0)
+
+    @staticmethod
     def WriteFilesFull(path, Y_full, indicator_cvt=None):
         """PRDT::WriteFiles(gsl_matrix *), src/prdt.cpp:104-131: one row per individual, NA without covariates, a tab after
         every value."""

@@ -17,7 +17,7 @@ UNITS = {
                       "abi_mqs.inc.h", "mqs_tu.h", "abi_cor.inc.h", "cor_tu.h"],
     "eigh_tu.hip": ["dgemm_mfma.hip.h", "eigh.hip.h", "eigh2.hip.h", "eigh_tu.h", "tu_common.h"],  # the eigensolver: its own object file
     "vc_tu.hip": ["dgemm_mfma.hip.h", "spd_inv.hip.h", "vc.hip.h", "vc_tu.h", "tu_common.h", "host_linalg.h", "../../include/gemma_vc_hybrid.hpp"],  # -vc 1 / -vc 2
-    "prdt_tu.hip": ["dgemm_mfma.hip.h", "geno_mv.hip.h", "dev_common.hip.h", "eigh_tu.h", "prdt_tu.h", "tu_common.h"],  # -bslmm 2 / -predict: genotype matrix-vector passes
+    "prdt_tu.hip": ["dgemm_mfma.hip.h", "geno_mv.hip.h", "dev_common.hip.h", "eigh_tu.h", "prdt_tu.h", "tu_common.h", "spd_inv.hip.h", "prdt_mv.hip.h"],  # -bslmm 2 / -predict: genotype matrix-vector passes; the Kronecker system of -predict with a kinship alone
     "mqs_tu.hip": ["dgemm_mfma.hip.h", "mqs.hip.h", "ci.hip.h", "dev_common.hip.h", "mqs_tu.h", "tu_common.h", "host_linalg.h"],  # -gs / -vc 1 -beta: MQS kinships, S and its jackknife; -ci: the two genotype passes
     "cor_tu.hip": ["dgemm_mfma.hip.h", "cor.hip.h", "dev_common.hip.h", "cor_tu.h", "tu_common.h"],  # -calccor: banded SNP correlation, int8 band kernel and fp64 panels
     "mvlmm_kernels.hip": ["mvlmm.hip.h", "mvlmm_kernels.hip.h"],

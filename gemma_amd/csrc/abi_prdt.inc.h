@@ -223,3 +223,147 @@ extern "C" int gemma_hip_prdt_kin(size_t ni, const double *G_full, const int *in
   if ((rc = gemma_hip_dgemm('N', 'N', n, 1, n, 1.0, Hoo.data(), n, res.data(), 1, 0.0, x.data(), 1))) return rc;
   return gemma_hip_dgemm('N', 'N', m, 1, n, 1.0, Hmo.data(), n, x.data(), 1, 1.0, y_miss, 1);
 }
+
+// Mode 43 for several phenotypes: the Kronecker system on the device (prdt_mv.hip.h), see include/gemma_hip.h
+static int prdt_kin_mv_check(const char *who, size_t ni, size_t d, const double *G, size_t ldg, const int *ind, const double *W, size_t c,
+                             const double *Y, size_t extra, size_t *n_miss) {
+  if (ni == 0 || !G || !ind || !W || !Y || ldg < ni) return fail(GEMMA_HIP_EINVAL, "%s: ni = %zu, ldg = %zu or a null pointer", who, ni, ldg);
+  if (d < 2) return fail(GEMMA_HIP_EINVAL, "%s: %zu phenotypes (2..%d)", who, d, MV_DMAX);
+  int rc = mv_check_dims(who, d, c, extra);
+  if (rc) return rc;
+  if (ni > 65535) return fail(GEMMA_HIP_EINVAL, "%s: more than 65535 individuals", who);
+  size_t m = 0;
+  for (size_t k = 0; k < ni * d; ++k) m += ind[k] == 0;
+  if (m == ni * d) return fail(GEMMA_HIP_EINVAL, "%s: no phenotype is observed", who);
+  *n_miss = m;
+  return GEMMA_HIP_OK;
+}
+
+static int prdt_kin_mv_apply_common(size_t ni, size_t d, const double *G, size_t ldg, int g_where, const int *ind, const double *W,
+                                    size_t c, const double *Y, const double *Vg, const double *Ve, const double *B, double *y_miss,
+                                    void *stream) {
+  size_t m = 0;
+  int rc = prdt_kin_mv_check("prdt_kin_mv_apply", ni, d, G, ldg, ind, W, c, Y, 0, &m);
+  if (rc) return rc;
+  if (!Vg || !Ve || !B) return fail(GEMMA_HIP_EINVAL, "prdt_kin_mv_apply: Vg, Ve or B is NULL");
+  if (m == 0) return GEMMA_HIP_OK;
+  if (!y_miss) return fail(GEMMA_HIP_EINVAL, "prdt_kin_mv_apply: y_miss is NULL");
+  std::string msg;
+  long bad = -1;
+  rc = prdt_mv_apply_x((long)ni, (long)d, G, (long)ldg, g_where, ind, W, (long)c, Y, Vg, Ve, B, y_miss, &bad, S(stream), msg);
+  return ret(rc, msg);
+}
+
+extern "C" int gemma_hip_prdt_kin_mv_apply(size_t ni, size_t d, const double *G_full, const int *indicator_pheno, const double *W_full,
+                                           size_t n_cvt, const double *Y_full, const double *Vg, const double *Ve, const double *B,
+                                           double *y_miss) {
+  NEED_INIT();
+  return prdt_kin_mv_apply_common(ni, d, G_full, ni, 0, indicator_pheno, W_full, n_cvt, Y_full, Vg, Ve, B, y_miss, nullptr);
+}
+
+extern "C" int gemma_hip_prdt_kin_mv_apply_d(size_t ni, size_t d, const double *G_full_d, size_t ldg, const int *indicator_pheno,
+                                             const double *W_full, size_t n_cvt, const double *Y_full, const double *Vg, const double *Ve,
+                                             const double *B, double *y_miss, void *stream) {
+  NEED_INIT();
+  return prdt_kin_mv_apply_common(ni, d, G_full_d, ldg, 1, indicator_pheno, W_full, n_cvt, Y_full, Vg, Ve, B, y_miss, stream);
+}
+
+extern "C" int gemma_hip_prdt_kin_mv(size_t ni, size_t d, const double *G_full, const int *indicator_pheno, const double *W_full,
+                                     size_t n_cvt, const double *Y_full, double l_min, double l_max, size_t n_region,
+                                     const gemma_mvlmm_opt *opt, double *y_miss, gemma_mvlmm_null *fit) {
+  NEED_INIT();
+  if (d == 1) { // the reference takes the univariate branch (src/gemma.cpp:1790-1820)
+    double fit3[3] = {0.0, 0.0, 0.0};
+    const int rc1 = gemma_hip_prdt_kin(ni, G_full, indicator_pheno, W_full, n_cvt, Y_full, l_min, l_max, n_region, y_miss, fit3);
+    if (rc1 == GEMMA_HIP_OK && fit) {
+      memset(fit, 0, sizeof *fit);
+      fit->Vg_remle[0] = fit3[0];
+      fit->Ve_remle[0] = fit3[1];
+    }
+    return rc1;
+  }
+  size_t m = 0;
+  int rc = prdt_kin_mv_check("prdt_kin_mv", ni, d, G_full, ni, indicator_pheno, W_full, n_cvt, Y_full, 1, &m);
+  if (rc) return rc;
+  const size_t c = n_cvt;
+  std::vector<int> pos; // the individuals with every phenotype: the null fit's (cPar.indicator_idv)
+  for (size_t i = 0; i < ni; ++i) {
+    bool full = true;
+    for (size_t a = 0; a < d; ++a) full = full && indicator_pheno[i * d + a] != 0;
+    if (full) pos.push_back((int)i);
+  }
+  const size_t n = pos.size();
+  if (n <= c + 1) return fail(GEMMA_HIP_EINVAL, "prdt_kin_mv: %zu individuals with every phenotype, %zu covariates", n, c);
+  if (m > 0 && !y_miss) return fail(GEMMA_HIP_EINVAL, "prdt_kin_mv: y_miss is NULL");
+  // G_full to the device once; G of the complete individuals taken from it and centred there (:1757-1773)
+  std::string msg;
+  double *Gd = nullptr;
+  if ((rc = prdt_mv_stage_G_x(G_full, (long)ni, (long)ni, false, &Gd, nullptr, msg))) return ret(rc, msg);
+  ScopedBuf sub, U, small; // small: [eval n | WY n x (c + d) | UtWY n x (c + d)]
+  const size_t k = c + d;
+  if (sub.reserve(n * n * 8) || U.reserve(n * n * 8) || small.reserve((n + 2 * n * k) * 8))
+    return fail(GEMMA_HIP_ENOMEM, "prdt_kin_mv: cannot allocate 2 x %zu bytes", n * n * 8);
+  if ((rc = prdt_mv_sub_x(Gd, (long)ni, pos.data(), (long)n, sub.as<double>(), nullptr, msg))) return ret(rc, msg);
+  double *ev_d = small.as<double>(), *WY_d = ev_d + n, *UtWY_d = WY_d + n * k;
+  double trace_G = 0.0;
+  if ((rc = gemma_hip_center_d(sub.as<double>(), n, nullptr)) ||
+      (rc = gemma_hip_eigh_d(sub.as<double>(), n, U.as<double>(), ev_d, &trace_G, nullptr)))
+    return rc;
+  // U'W and U'Y in one product (:1785-1786)
+  std::vector<double> WY(n * k), UtWY(n * k), ev(n), UtW(n * c), UtY(n * d);
+  for (size_t a = 0; a < n; ++a) {
+    for (size_t j = 0; j < c; ++j) WY[a * k + j] = W_full[(size_t)pos[a] * c + j];
+    for (size_t j = 0; j < d; ++j) WY[a * k + c + j] = Y_full[(size_t)pos[a] * d + j];
+  }
+  HIPCHK(hipMemcpy(WY_d, WY.data(), n * k * 8, hipMemcpyHostToDevice));
+  if ((rc = gemma_hip_dgemm_d('T', 'N', n, k, n, 1.0, U.as<double>(), n, WY_d, k, 0.0, UtWY_d, k, nullptr))) return rc;
+  HIPCHK(hipMemcpy(UtWY.data(), UtWY_d, n * k * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(ev.data(), ev_d, n * 8, hipMemcpyDeviceToHost));
+  sub.release();
+  U.release();
+  small.release();
+  for (size_t a = 0; a < n; ++a) {
+    for (size_t j = 0; j < c; ++j) UtW[a * c + j] = UtWY[a * k + j];
+    for (size_t j = 0; j < d; ++j) UtY[a * d + j] = UtWY[a * k + c + j];
+  }
+  // CalcMvLmmVgVeBeta (:1828-1830): the REMLE half of the null block
+  gemma_mvlmm_null local;
+  gemma_mvlmm_null *f = fit ? fit : &local;
+  if ((rc = gemma_hip_mvlmm_null(n, c, d, ev.data(), UtW.data(), UtY.data(), l_min, l_max, n_region, opt, f))) return rc;
+  if (m == 0) return GEMMA_HIP_OK;
+  long bad = -1;
+  rc = prdt_mv_apply_x((long)ni, (long)d, nullptr, (long)ni, 2, indicator_pheno, W_full, (long)c, Y_full, f->Vg_remle, f->Ve_remle,
+                       f->B_remle, y_miss, &bad, nullptr, msg);
+  return ret(rc, msg);
+}
+
+// tests and scripts/prdt_mv_probe.py (not in the public header): H_oo's assembled upper triangle, and the factor + solve path on a
+// host or a device matrix
+extern "C" int gemma_hip_dbg_prdt_mv_assemble(size_t ni, size_t d, const double *Gc, const int *indicator_pheno, const double *Vg,
+                                              const double *Ve, double *H, size_t lda) {
+  NEED_INIT();
+  if (ni == 0 || d == 0 || d > (size_t)MV_DMAX || !Gc || !indicator_pheno || !Vg || !Ve || !H)
+    return fail(GEMMA_HIP_EINVAL, "dbg_prdt_mv_assemble: ni = %zu, d = %zu", ni, d);
+  size_t N = 0;
+  for (size_t k = 0; k < ni * d; ++k) N += indicator_pheno[k] != 0;
+  if (lda < N) return fail(GEMMA_HIP_EINVAL, "dbg_prdt_mv_assemble: lda = %zu, %zu observed entries", lda, N);
+  std::string msg;
+  const int rc = prdt_mv_dbg_assemble_x((long)ni, (long)d, Gc, indicator_pheno, Vg, Ve, H, (long)lda, nullptr, msg);
+  return ret(rc, msg);
+}
+
+extern "C" int gemma_hip_dbg_spd_solve(const double *A, size_t n, double *x, long *bad_pivot) {
+  NEED_INIT();
+  if (n == 0 || !A || !x) return fail(GEMMA_HIP_EINVAL, "dbg_spd_solve: n = %zu", n);
+  std::string msg;
+  const int rc = prdt_mv_dbg_solve_x(const_cast<double *>(A), (long)n, (long)n, x, false, bad_pivot, nullptr, msg);
+  return ret(rc, msg);
+}
+
+extern "C" int gemma_hip_dbg_spd_solve_d(double *A_d, size_t n, size_t lda, double *x_d, long *bad_pivot, void *stream) {
+  NEED_INIT();
+  if (n == 0 || lda < n || !A_d || !x_d) return fail(GEMMA_HIP_EINVAL, "dbg_spd_solve: n = %zu, lda = %zu", n, lda);
+  std::string msg;
+  const int rc = prdt_mv_dbg_solve_x(A_d, (long)n, (long)lda, x_d, true, bad_pivot, S(stream), msg);
+  return ret(rc, msg);
+}

@@ -30,6 +30,22 @@ int prdt_end_x(double pheno_mean, int probit, double *y_prdt, std::string &msg);
 bool prdt_active_x();
 size_t prdt_ni_total_x();
 size_t prdt_n_train_x();
+
+// Kinship-only prediction for several phenotypes (prdt_mv.hip.h).  prdt_mv_apply_x: the Kronecker system alone, ind (ni x d, host),
+// W (ni x c), Y (ni x d), Vg / Ve (d x d), B (d x c), y_miss on the host.  g_where: 0 = G (ni x ni, ldg) on the host, 1 = on the
+// device (copied, not changed), 2 = already staged by prdt_mv_stage_G_x (centred in place).  *bad_pivot with GEMMA_HIP_ENOTPD.
+int prdt_mv_apply_x(long ni, long d, const double *G, long ldg, int g_where, const int *ind, const double *W, long c, const double *Y,
+                    const double *Vg, const double *Ve, const double *B, double *y_miss, long *bad_pivot, hipStream_t s, std::string &msg);
+// G (host or device) into the unit's own ni x ni buffer: *Gd
+int prdt_mv_stage_G_x(const double *G, long ni, long ldg, bool device, double **Gd, hipStream_t s, std::string &msg);
+// out_d (n x n, device) = Gd[pos][pos], pos[n] on the host
+int prdt_mv_sub_x(const double *Gd, long ldg, const int *pos, long n, double *out_d, hipStream_t s, std::string &msg);
+void prdt_mv_release_x();
+// tests: the assembled upper triangle of H_oo from a centred Gc (all on the host; H_host N x lda is read, overwritten on its upper
+// triangle and returned), and the factor + solve path on a host matrix (not changed) or on a device matrix (factored in place)
+int prdt_mv_dbg_assemble_x(long ni, long d, const double *Gc_host, const int *ind, const double *Vg, const double *Ve, double *H_host,
+                           long lda, hipStream_t s, std::string &msg);
+int prdt_mv_dbg_solve_x(double *A, long n, long lda, double *x, bool device, long *bad_pivot, hipStream_t s, std::string &msg);
 void prdt_tu_shutdown();
 
 } // namespace gemma_hip

@@ -18,6 +18,8 @@
 #include "dgemm_mfma.hip.h"
 #include "eigh_tu.h"
 #include "geno_mv.hip.h"
+#include "spd_inv.hip.h"
+#include "prdt_mv.hip.h"
 #include "prdt_tu.h"
 
 namespace gemma_hip {
@@ -395,9 +397,193 @@ int prdt_end_x(double pheno_mean, int probit, double *y_prdt, std::string &msg) 
   return GEMMA_HIP_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ kinship-only, several phenotypes
+namespace {
+
+struct PrdtMvState {
+  DevBuf G, H, small; // the centred kinship (ni x ni), H_oo (N x lda), the index lists and the short vectors
+  SpdFactorWork spd;
+} g_mv;
+
+// the lists of an ni x d indicator, entries in i * d + a order
+struct MvLists {
+  std::vector<int> oi, oa, ou, ui, mi, ma;
+  void set(const int *ind, long ni, long d) {
+    for (long i = 0; i < ni; ++i) {
+      bool any = false;
+      for (long a = 0; a < d; ++a) {
+        if (ind[i * d + a] != 0) {
+          if (!any) ui.push_back((int)i);
+          any = true;
+          oi.push_back((int)i);
+          oa.push_back((int)a);
+          ou.push_back((int)ui.size() - 1);
+        } else {
+          mi.push_back((int)i);
+          ma.push_back((int)a);
+        }
+      }
+    }
+  }
+};
+
+PmvSmall mv_small(long d, long c, const double *Vg, const double *Ve, const double *B) {
+  PmvSmall sm;
+  memset(&sm, 0, sizeof sm);
+  sm.d = (int)d;
+  sm.c = (int)c;
+  memcpy(sm.Vg, Vg, d * d * 8);
+  memcpy(sm.Ve, Ve, d * d * 8);
+  if (B) memcpy(sm.B, B, d * c * 8);
+  return sm;
+}
+
+int mv_upload_lists(const MvLists &l, int *&oi, int *&oa, int *&ou, int *&ui, int *&mi, int *&ma, char *&next, hipStream_t s,
+                    std::string &msg) { // into g_mv.small, already reserved; next: the first 16-byte aligned byte behind them
+  const std::vector<int> *v[6] = {&l.oi, &l.oa, &l.ou, &l.ui, &l.mi, &l.ma};
+  int **dst[6] = {&oi, &oa, &ou, &ui, &mi, &ma};
+  char *p = g_mv.small.as<char>();
+  for (int k = 0; k < 6; ++k) {
+    *dst[k] = reinterpret_cast<int *>(p);
+    if (!v[k]->empty()) TU_CHK(hipMemcpyAsync(p, v[k]->data(), v[k]->size() * 4, hipMemcpyHostToDevice, s));
+    p += (v[k]->size() * 4 + 15) & ~(size_t)15;
+  }
+  next = p;
+  return GEMMA_HIP_OK;
+}
+
+size_t mv_lists_bytes(const MvLists &l) {
+  size_t b = 0;
+  for (const std::vector<int> *v : {&l.oi, &l.oa, &l.ou, &l.ui, &l.mi, &l.ma}) b += (v->size() * 4 + 15) & ~(size_t)15;
+  return b;
+}
+
+void mv_launch_assemble(const double *Gc, long ldg, const int *ou, const int *oa, const int *ui, long N, const PmvSmall &sm, double *H,
+                        long lda, hipStream_t s) {
+  const unsigned t = (unsigned)((N + PMV_TILE - 1) / PMV_TILE);
+  prdt_mv_assemble_kernel<<<dim3(t, t), 256, 0, s>>>(Gc, ldg, ou, oa, ui, N, sm, H, lda);
+}
+
+} // namespace
+
+void prdt_mv_release_x() {
+  g_mv.G.release(); g_mv.H.release(); g_mv.small.release();
+  g_mv.spd.release();
+}
+
+int prdt_mv_stage_G_x(const double *G, long ni, long ldg, bool device, double **Gd, hipStream_t s, std::string &msg) {
+  int rc = g_mv.G.reserve((size_t)ni * ni * 8, "prdt_kin_mv", msg);
+  if (rc) return rc;
+  TU_CHK(hipMemcpy2DAsync(g_mv.G.p, ni * 8, G, ldg * 8, ni * 8, ni, device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+  *Gd = g_mv.G.as<double>();
+  return GEMMA_HIP_OK;
+}
+
+int prdt_mv_sub_x(const double *Gd, long ldg, const int *pos, long n, double *out_d, hipStream_t s, std::string &msg) {
+  int rc = g_mv.small.reserve((size_t)n * 4, "prdt_kin_mv", msg);
+  if (rc) return rc;
+  TU_CHK(hipMemcpyAsync(g_mv.small.p, pos, n * 4, hipMemcpyHostToDevice, s));
+  prdt_mv_sub_kernel<<<dim3(nb(n), (unsigned)n), 256, 0, s>>>(Gd, ldg, g_mv.small.as<int>(), n, out_d);
+  TU_CHK(hipGetLastError());
+  TU_CHK(hipStreamSynchronize(s)); // pos and the list buffer may change after the return
+  return GEMMA_HIP_OK;
+}
+
+int prdt_mv_apply_x(long ni, long d, const double *G, long ldg, int g_where, const int *ind, const double *W, long c, const double *Y,
+                    const double *Vg, const double *Ve, const double *B, double *y_miss, long *bad_pivot, hipStream_t s, std::string &msg) {
+  aux_init();
+  MvLists l;
+  l.set(ind, ni, d);
+  const long N = (long)l.oi.size(), M = (long)l.mi.size();
+  if (M == 0) return GEMMA_HIP_OK;
+  int rc;
+  double *Gc = g_mv.G.as<double>();
+  if (g_where != 2 && (rc = prdt_mv_stage_G_x(G, ni, ldg, g_where == 1, &Gc, s, msg))) return rc;
+  if ((rc = gemma_hip_center_d(Gc, (size_t)ni, s))) {
+    msg = gemma_hip_last_error();
+    return rc;
+  }
+  const long lda = (N + 1) & ~1L;
+  // small: [lists | W ni x c | Y ni x d | x N | Z ni x d | GZ ni x d | y_miss M]
+  const size_t doubles = (size_t)ni * (c + 3 * d) + N + M;
+  if ((rc = g_mv.small.reserve(mv_lists_bytes(l) + doubles * 8, "prdt_kin_mv", msg)) ||
+      (rc = g_mv.H.reserve((size_t)std::max<long>(N, 1) * lda * 8, "prdt_kin_mv", msg)))
+    return rc;
+  int *oi, *oa, *ou, *ui, *mi, *ma;
+  char *next;
+  if ((rc = mv_upload_lists(l, oi, oa, ou, ui, mi, ma, next, s, msg))) return rc;
+  double *p = reinterpret_cast<double *>(next);
+  double *Wd = p; p += ni * c;
+  double *Yd = p; p += ni * d;
+  double *x = p; p += N;
+  double *Z = p; p += ni * d;
+  double *GZ = p; p += ni * d;
+  double *ym = p;
+  TU_CHK(hipMemcpyAsync(Wd, W, ni * c * 8, hipMemcpyHostToDevice, s));
+  TU_CHK(hipMemcpyAsync(Yd, Y, ni * d * 8, hipMemcpyHostToDevice, s));
+  TU_CHK(hipMemsetAsync(Z, 0, ni * d * 8, s));
+  const PmvSmall sm = mv_small(d, c, Vg, Ve, B);
+  if (N > 0) {
+    double *H = g_mv.H.as<double>();
+    TU_CHK(hipMemsetAsync(H, 0, (size_t)N * lda * 8, s)); // what lies below the diagonal is scratch of the factor's diagonal tiles
+    mv_launch_assemble(Gc, ni, ou, oa, ui, N, sm, H, lda, s);
+    prdt_mv_resid_kernel<<<nb(N), 256, 0, s>>>(Yd, Wd, oi, oa, N, sm, x);
+    TU_CHK(hipGetLastError());
+    if ((rc = spd_factor_solve_device(H, N, lda, x, nullptr, bad_pivot, g_mv.spd, "prdt_kin_mv: H_oo", s, msg))) return rc;
+    prdt_mv_scatter_kernel<<<nb(N), 256, 0, s>>>(x, oi, oa, N, (int)d, Z);
+    TU_CHK(hipGetLastError());
+  }
+  TU_CHK(launch_dgemm('N', 'N', ni, d, ni, 1.0, Gc, ni, Z, d, 0.0, GZ, d, false, false, s));
+  prdt_mv_epilogue_kernel<<<nb(M), 256, 0, s>>>(GZ, Z, Wd, mi, ma, M, sm, ym);
+  TU_CHK(hipGetLastError());
+  TU_CHK(hipMemcpyAsync(y_miss, ym, M * 8, hipMemcpyDeviceToHost, s));
+  TU_CHK(hipStreamSynchronize(s));
+  return GEMMA_HIP_OK;
+}
+
+// tests: the upper triangle of H_oo alone, written into the caller's N x lda host array (everything else of it is left as it was)
+int prdt_mv_dbg_assemble_x(long ni, long d, const double *Gc_host, const int *ind, const double *Vg, const double *Ve, double *H_host,
+                           long lda, hipStream_t s, std::string &msg) {
+  MvLists l;
+  l.set(ind, ni, d);
+  const long N = (long)l.oi.size();
+  if (N == 0) return GEMMA_HIP_OK;
+  int rc;
+  double *Gc;
+  if ((rc = prdt_mv_stage_G_x(Gc_host, ni, ni, false, &Gc, s, msg)) ||
+      (rc = g_mv.small.reserve(mv_lists_bytes(l), "prdt_kin_mv", msg)) || (rc = g_mv.H.reserve((size_t)N * lda * 8, "prdt_kin_mv", msg)))
+    return rc;
+  int *oi, *oa, *ou, *ui, *mi, *ma;
+  char *next;
+  if ((rc = mv_upload_lists(l, oi, oa, ou, ui, mi, ma, next, s, msg))) return rc;
+  TU_CHK(hipMemcpyAsync(g_mv.H.p, H_host, (size_t)N * lda * 8, hipMemcpyHostToDevice, s));
+  mv_launch_assemble(Gc, ni, ou, oa, ui, N, mv_small(d, 0, Vg, Ve, nullptr), g_mv.H.as<double>(), lda, s);
+  TU_CHK(hipGetLastError());
+  TU_CHK(hipMemcpyAsync(H_host, g_mv.H.p, (size_t)N * lda * 8, hipMemcpyDeviceToHost, s));
+  TU_CHK(hipStreamSynchronize(s));
+  return GEMMA_HIP_OK;
+}
+
+// tests and the probe: A x = r by the factor + solve path.  Device form: A (n x n, lda; upper triangle read, the factor left in
+// place) and x (r in, the solution out) on the device; host form: both on the host, A dense and not changed.
+int prdt_mv_dbg_solve_x(double *A, long n, long lda, double *x, bool device, long *bad_pivot, hipStream_t s, std::string &msg) {
+  aux_init();
+  if (device) return spd_factor_solve_device(A, n, lda, x, nullptr, bad_pivot, g_mv.spd, "spd_solve", s, msg);
+  const long ld = (n + 1) & ~1L;
+  int rc;
+  if ((rc = g_mv.H.reserve((size_t)n * ld * 8, "prdt_kin_mv", msg)) || (rc = g_mv.small.reserve((size_t)n * 8, "prdt_kin_mv", msg))) return rc;
+  TU_CHK(hipMemcpy2DAsync(g_mv.H.p, ld * 8, A, lda * 8, n * 8, n, hipMemcpyHostToDevice, s));
+  TU_CHK(hipMemcpyAsync(g_mv.small.p, x, n * 8, hipMemcpyHostToDevice, s));
+  if ((rc = spd_factor_solve_device(g_mv.H.as<double>(), n, ld, g_mv.small.as<double>(), nullptr, bad_pivot, g_mv.spd, "spd_solve", s, msg)))
+    return rc;
+  TU_CHK(hipMemcpy(x, g_mv.small.p, n * 8, hipMemcpyDeviceToHost));
+  return GEMMA_HIP_OK;
+}
+
 void prdt_tu_shutdown() {
   ridge_finish_x();
   prdt_release();
+  prdt_mv_release_x();
   if (g_aux) gemm_aux_destroy();
   g_aux = false;
 }

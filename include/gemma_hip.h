@@ -547,9 +547,33 @@ int gemma_hip_prdt_end(double pheno_mean, int probit, double *y_prdt);
  * lambda is the REML estimate (CalcLambda 'R'), vg / ve / beta come from CalcLmmVgVeBeta, H = ve I + vg CenterMatrix(G_full) and
  *   y_miss = W_miss beta + H_mo H_oo^-1 (y_obs - W_obs beta)        y_miss[number of zeros of indicator_pheno], in order.
  * H_oo is inverted as a symmetric positive-definite matrix (GEMMA_HIP_ENOTPD where ve = 0 makes it singular; the reference's LU
- * would carry on).  fit3 (may be NULL) = {vg, ve, lambda}.  More than one phenotype (the Kronecker H_full) is not provided. */
+ * would carry on).  fit3 (may be NULL) = {vg, ve, lambda}. */
 int gemma_hip_prdt_kin(size_t ni, const double *G_full, const int *indicator_pheno, const double *W_full, size_t n_cvt,
                        const double *y_full, double l_min, double l_max, size_t n_region, double *y_miss, double *fit3);
+/* The same for d = 2..GEMMA_MV_DMAX phenotypes: the else branch of src/gemma.cpp:1821-1871 with PRDT::MvnormPrdt, without the
+ * (ni d)^2 matrix H_full = G (x) Vg + I (x) Ve.  Entries are ordered i * d + a (individual-major, as KroneckerSym and MvnormPrdt
+ * order them): indicator_pheno (ni x d, 1 = observed), Y_full (ni x d, unobserved entries are not read), y_miss one value per zero
+ * of indicator_pheno in that order.  With Gc = CenterMatrix(G_full), o the observed entries and r = (Y - W B^T)[o]:
+ *   H_oo[(i,a),(j,b)] = Gc_ij Vg_ab + delta_ij Ve_ab  (assembled on the device),  z = H_oo^-1 r  (Cholesky factor and two
+ *   triangular solves, no inverse),  y_miss_ia = (W B^T)_ia + (Gc Z Vg + Z Ve)_ia  with Z = z scattered over ni x d.
+ * _apply: the system alone for given Vg, Ve (d x d, leading dimension d) and B (d x n_cvt, n_cvt <= GEMMA_MV_CMAX): no
+ * eigensolver, no null fit.  _apply_d: G_full on the device (leading dimension ldg, not changed), on `stream`, which is
+ * synchronised; every other argument on the host.
+ * prdt_kin_mv: the whole block -- the kinship of the individuals with every phenotype is taken from G_full, centred and decomposed
+ * on the device, U'W and U'Y, the REMLE fit of gemma_hip_mvlmm_null (opt NULL = the PARAM defaults; n_cvt + 1 <= GEMMA_MV_CMAX),
+ * then _apply with its Vg_remle, Ve_remle, B_remle.  fit (may be NULL) receives that null fit.  d == 1 is handed to
+ * gemma_hip_prdt_kin (fit: Vg_remle[0] = vg, Ve_remle[0] = ve, everything else 0).
+ * GEMMA_HIP_EINVAL: a null pointer, d or n_cvt beyond the caps, no observed entry, no more individuals with every phenotype than
+ * n_cvt + 1 (prdt_kin_mv), y_miss == NULL while something is missing, ni > 65535.  Nothing missing: GEMMA_HIP_OK (prdt_kin_mv
+ * still returns the fit).  GEMMA_HIP_ENOTPD, with the failing pivot in the message, when H_oo is not positive definite. */
+int gemma_hip_prdt_kin_mv_apply(size_t ni, size_t d, const double *G_full, const int *indicator_pheno, const double *W_full,
+                                size_t n_cvt, const double *Y_full, const double *Vg, const double *Ve, const double *B, double *y_miss);
+int gemma_hip_prdt_kin_mv_apply_d(size_t ni, size_t d, const double *G_full_d, size_t ldg, const int *indicator_pheno,
+                                  const double *W_full, size_t n_cvt, const double *Y_full, const double *Vg, const double *Ve,
+                                  const double *B, double *y_miss, void *stream);
+int gemma_hip_prdt_kin_mv(size_t ni, size_t d, const double *G_full, const int *indicator_pheno, const double *W_full, size_t n_cvt,
+                          const double *Y_full, double l_min, double l_max, size_t n_region, const gemma_mvlmm_opt *opt, double *y_miss,
+                          gemma_mvlmm_null *fit);
 
 /* ---- MQS summary-statistic variance components: -gs and -vc 1 -beta (Zhou 2017) ---------------------------------------------- */
 /* PARAM::CalcS (src/param.cpp:1717-1812), called where src/gemma.cpp:1977 (-gs) and :2166 / :2198 (-vc 1 / 2 with -beta) call it.

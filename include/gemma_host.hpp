@@ -1290,6 +1290,82 @@ public:
       if (indicator_pheno[i] == 0) y_full[i] = y_miss[t++];
     return fit;
   }
+  // a_mode 43 for several phenotypes: the whole block of src/gemma.cpp:1732-1897 with the else branch :1821-1871.  indicator_pheno
+  // and indicator_cvt as PARAM holds them (one row per individual of the files); G_full, W_full and Y_full over the individuals
+  // with covariates (ReadFile_kin with indicator_cvt, CopyCvtPhen(W_full, Y_full, 1)), Y_full ni_cvt x n_ph.  The missing entries
+  // of Y_full are filled in; fit (may be NULL) receives Vg, Ve, B of the null model.  The checks of src/param.cpp:1090-1103 on
+  // the indicators throw std::invalid_argument with the reference's messages.  Needs no PRDT object.
+  static void MvnormPrdt(const Matrix *G_full, const std::vector<std::vector<int>> &indicator_pheno, const std::vector<int> &indicator_cvt,
+                         const Matrix *W_full, Matrix *Y_full, gemma_mvlmm_null *fit = nullptr, double l_min = 1e-5, double l_max = 1e5,
+                         size_t n_region = 10, const gemma_mvlmm_opt *opt = nullptr) {
+    std::vector<int> ind;
+    const size_t n_ph = Y_full->size2;
+    const size_t ni_cvt = MvIndicator(indicator_pheno, indicator_cvt, n_ph, ind);
+    if (G_full->tda != ni_cvt || G_full->size1 != ni_cvt || W_full->tda != W_full->size2 || W_full->size1 != ni_cvt ||
+        Y_full->size1 != ni_cvt || Y_full->tda != n_ph)
+      throw std::invalid_argument("PRDT::MvnormPrdt: shapes");
+    std::vector<double> y_miss(ni_cvt * n_ph + 1);
+    enforce_hip(gemma_hip_prdt_kin_mv(ni_cvt, n_ph, G_full->data, ind.data(), W_full->data, W_full->size2, Y_full->data, l_min, l_max,
+                                      n_region, opt, y_miss.data(), fit), "PRDT::MvnormPrdt");
+    size_t t = 0;
+    for (size_t k = 0; k < ni_cvt * n_ph; ++k)
+      if (ind[k] == 0) Y_full->data[k] = y_miss[t++];
+  }
+  // PRDT::MvnormPrdt itself (src/prdt.cpp:448-553) for given Vg, Ve (n_ph x n_ph) and B (n_ph x n_cvt): Y_hat = W_full B' and H are
+  // not formed by the caller
+  static void MvnormPrdt(const Matrix *G_full, const std::vector<std::vector<int>> &indicator_pheno, const std::vector<int> &indicator_cvt,
+                         const Matrix *W_full, const Matrix *Vg, const Matrix *Ve, const Matrix *B, Matrix *Y_full) {
+    std::vector<int> ind;
+    const size_t n_ph = Y_full->size2;
+    const size_t ni_cvt = MvIndicator(indicator_pheno, indicator_cvt, n_ph, ind);
+    if (G_full->tda != ni_cvt || W_full->tda != W_full->size2 || W_full->size1 != ni_cvt || Y_full->size1 != ni_cvt || Y_full->tda != n_ph ||
+        Vg->tda != n_ph || Ve->tda != n_ph || B->tda != W_full->size2 || B->size1 != n_ph)
+      throw std::invalid_argument("PRDT::MvnormPrdt: shapes");
+    std::vector<double> y_miss(ni_cvt * n_ph + 1);
+    enforce_hip(gemma_hip_prdt_kin_mv_apply(ni_cvt, n_ph, G_full->data, ind.data(), W_full->data, W_full->size2, Y_full->data, Vg->data,
+                                            Ve->data, B->data, y_miss.data()), "PRDT::MvnormPrdt");
+    size_t t = 0;
+    for (size_t k = 0; k < ni_cvt * n_ph; ++k)
+      if (ind[k] == 0) Y_full->data[k] = y_miss[t++];
+  }
+  // the ni_cvt x n_ph indicator of the individuals with covariates, after the checks of src/param.cpp:1090-1103
+  static size_t MvIndicator(const std::vector<std::vector<int>> &indicator_pheno, const std::vector<int> &indicator_cvt, size_t n_ph,
+                            std::vector<int> &ind) {
+    ind.clear();
+    size_t ni_cvt = 0, ni_test = 0, np_obs = 0, np_miss = 0;
+    for (size_t i = 0; i < indicator_pheno.size(); ++i) {
+      if (!indicator_cvt.empty() && indicator_cvt[i] == 0) continue;
+      ni_cvt++;
+      bool full = true;
+      for (size_t j = 0; j < indicator_pheno[i].size(); ++j) {
+        if (indicator_pheno[i][j] == 0) np_miss++;
+        else np_obs++;
+        full = full && indicator_pheno[i][j] != 0;
+        ind.push_back(indicator_pheno[i][j] != 0 ? 1 : 0);
+      }
+      if (full) ni_test++;
+    }
+    if (ni_cvt == ni_test) throw std::invalid_argument("error! no individual has missing phenotypes.");
+    if (np_obs + np_miss != ni_cvt * n_ph)
+      throw std::invalid_argument("error! number of phenotypes do not match the summation of missing and observed phenotypes.");
+    return ni_cvt;
+  }
+  // PRDT::WriteFiles(gsl_matrix *), src/prdt.cpp:104-131: one row per individual of the files, NA without covariates, a tab after
+  // every value
+  static void WriteFiles(const std::string &file_str, const std::vector<int> &indicator_cvt, const Matrix *Y_full) {
+    std::ofstream outfile(file_str.c_str(), std::ofstream::out);
+    if (!outfile) throw std::runtime_error("error writing file: " + file_str);
+    size_t ci_test = 0;
+    for (size_t i = 0; i < indicator_cvt.size(); i++) {
+      if (indicator_cvt[i] == 0) {
+        outfile << "NA" << std::endl;
+      } else {
+        for (size_t j = 0; j < Y_full->size2; j++) outfile << Y_full->data[ci_test * Y_full->tda + j] << "\t";
+        outfile << std::endl;
+        ci_test++;
+      }
+    }
+  }
   // PRDT::WriteFiles(gsl_vector *), src/prdt.cpp:76-102 (default stream precision)
   void WriteFiles(const std::string &file_str, const std::vector<double> &y_prdt) const { WriteFiles(file_str, indicator_idv, y_prdt); }
   static void WriteFiles(const std::string &file_str, const std::vector<int> &indicator, const std::vector<double> &y_prdt) {
