@@ -37,6 +37,8 @@ SYMBOLS = [
     "gemma_hip_ci_xtxwz_d", "gemma_hip_ci_release",
     "gemma_hip_lmm_multi_setup", "gemma_hip_lmm_multi_setup_d", "gemma_hip_lmm_multi_setup_kept", "gemma_hip_lmm_multi_batch",
     "gemma_hip_lmm_multi_batch_d",
+    "gemma_hip_lmm_score_panel_setup", "gemma_hip_lmm_score_panel_setup_d", "gemma_hip_lmm_score_panel_setup_kept",
+    "gemma_hip_lmm_score_panel_batch", "gemma_hip_lmm_score_panel_batch_d", "gemma_hip_lmm_score_panel_assoc_d",
 ]
 LMM_MULTI_MAX = 64
 COMM_ID_BYTES = 128
@@ -49,6 +51,11 @@ STAGE_INGEST, STAGE_UTX_GEMM, STAGE_ASSOC, STAGE_KIN_GEMM, STAGE_EIGH, STAGE_UTX
 class SumStat(C.Structure):
     _fields_ = [(k, C.c_double) for k in
                 ("beta", "se", "lambda_remle", "lambda_mle", "p_wald", "p_lrt", "p_score", "logl_H1")]
+
+
+class ScoreRec(C.Structure):
+    """gemma_score_rec: one (phenotype, SNP) pair of the score panel"""
+    _fields_ = [(k, C.c_double) for k in ("beta", "se", "p_score")]
 
 
 class LmmCfg(C.Structure):
@@ -182,6 +189,12 @@ def lib():
     L.gemma_hip_lmm_multi_setup_kept.argtypes = [C.POINTER(LmmCfg), sz, dp, dp, dp, dp]
     L.gemma_hip_lmm_multi_batch.argtypes = [ci, vp, sz, sz, vp]
     L.gemma_hip_lmm_multi_batch_d.argtypes = [ci, vp, sz, sz, vp, vp]
+    L.gemma_hip_lmm_score_panel_setup.argtypes = [C.POINTER(LmmCfg), sz, dp, dp, dp, dp, dp]
+    L.gemma_hip_lmm_score_panel_setup_d.argtypes = [C.POINTER(LmmCfg), sz, dp, dp, dp, dp, dp, vp]
+    L.gemma_hip_lmm_score_panel_setup_kept.argtypes = [C.POINTER(LmmCfg), sz, dp, dp, dp]
+    L.gemma_hip_lmm_score_panel_batch.argtypes = [ci, vp, sz, sz, vp]
+    L.gemma_hip_lmm_score_panel_batch_d.argtypes = [ci, vp, sz, sz, vp, vp]
+    L.gemma_hip_lmm_score_panel_assoc_d.argtypes = [dp, sz, sz, vp, vp]
     L.gemma_hip_dbg_i8_digits.argtypes = [sz, C.POINTER(ci)]
     L.gemma_hip_dbg_last_utx_path.argtypes = [C.POINTER(ci)]
     L.gemma_hip_dbg_last_utx_kernel.argtypes = [C.POINTER(UtxKernelInfo)]

@@ -24,6 +24,7 @@ from . import _lib as L
 SUMSTAT_DTYPE = np.dtype([(k, "f8") for k in
                           ("beta", "se", "lambda_remle", "lambda_mle", "p_wald", "p_lrt", "p_score",
                            "logl_H1")])
+SCORE_DTYPE = np.dtype([(k, "f8") for k in ("beta", "se", "p_score")])  # gemma_score_rec
 LMM_BATCH_SIZE = 20000  # src/lmm.h:33
 K_BATCH_SIZE = 20000  # src/param.h:32
 
@@ -592,6 +593,100 @@ class LMM:
         finally:
             self.finish()
         return self.sumStat
+
+    # -- score panel: -lmm 3 of T phenotypes from one product per block (gemma_hip_lmm_score_panel_*) --
+    def setup_score_panel(self, U, eval_, UtW, UtY, l_mle_null):
+        """Score-panel setup for the T columns of UtY (n x T): a_mode must be 3; l_mle_null holds the T null lambdas.  numpy
+        arrays are uploaded, torch device tensors are used in place (U, eval: borrowed until finish())."""
+        n = U.shape[0]
+        T = UtY.shape[1]
+        nul = np.ascontiguousarray(l_mle_null, dtype=np.float64).ravel()
+        if nul.size != T:
+            raise ValueError("LMM.setup_score_panel: %d null values for %d phenotypes" % (nul.size, T))
+        if _is_torch(U):
+            c = UtW.shape[1] if UtW.dim() == 2 else 1
+            cfg = self._cfg(n, c, False)
+            UtY = UtY.contiguous()
+            self._keep = (U, eval_, UtW, UtY)
+            rc = L.lib().gemma_hip_lmm_score_panel_setup_d(C.byref(cfg), T, _ptr(nul), C.c_void_p(U.data_ptr()),
+                                                           C.c_void_p(eval_.data_ptr()), C.c_void_p(UtW.data_ptr()),
+                                                           C.c_void_p(UtY.data_ptr()), _stream())
+        else:
+            UtW = np.ascontiguousarray(UtW, dtype=np.float64).reshape(n, -1)
+            c = UtW.shape[1]
+            cfg = self._cfg(n, c, False)
+            U_c = _np64(np.ascontiguousarray(U), "U")
+            ev_c = np.ascontiguousarray(eval_, dtype=np.float64)
+            UtY_c = np.ascontiguousarray(UtY, dtype=np.float64)
+            rc = L.lib().gemma_hip_lmm_score_panel_setup(C.byref(cfg), T, _ptr(nul), _ptr(U_c), _ptr(ev_c), _ptr(UtW), _ptr(UtY_c))
+        L.check(rc, "LMM.setup_score_panel")
+        self.ni_test, self.n_cvt, self.n_ph = n, c, T
+        self._active = True
+
+    def batch_score_panel(self, geno, geno_kind, out=None, l=None, ld=None):
+        """One block of SNPs -> (T, l) SCORE_DTYPE records (numpy), or a (T, l, 3) device tensor (torch)."""
+        T = self.n_ph
+        if _is_torch(geno):
+            import torch
+            l = geno.shape[0] if l is None else l
+            ld = _tld(geno) if ld is None else ld
+            if out is None:
+                out = torch.empty((T, l, 3), dtype=torch.float64, device=geno.device)
+            rc = L.lib().gemma_hip_lmm_score_panel_batch_d(geno_kind, C.c_void_p(geno.data_ptr()), l, ld,
+                                                           C.c_void_p(out.data_ptr()), _stream())
+            L.check(rc, "LMM.batch_score_panel")
+            return out
+        if geno_kind == L.GENO_F64_IDV_MAJOR:
+            l = geno.shape[1] if l is None else l
+        else:
+            l = geno.shape[0] if l is None else l
+        ld = (geno.strides[0] // geno.itemsize) if ld is None else ld
+        if out is None:
+            out = np.zeros((T, l), dtype=SCORE_DTYPE)
+        L.check(L.lib().gemma_hip_lmm_score_panel_batch(geno_kind, _ptr(geno), l, ld, _ptr(out)), "LMM.batch_score_panel")
+        return out
+
+    def assoc_score_panel(self, UtX, out=None):
+        """The product alone, on a device-resident SNP-major UtX (torch) -> (T, l, 3) device tensor."""
+        import torch
+        l = UtX.shape[0]
+        if out is None:
+            out = torch.empty((self.n_ph, l, 3), dtype=torch.float64, device=UtX.device)
+        L.check(L.lib().gemma_hip_lmm_score_panel_assoc_d(C.c_void_p(UtX.data_ptr()), l, _tld(UtX),
+                                                          C.c_void_p(out.data_ptr()), _stream()), "LMM.assoc_score_panel")
+        return out
+
+    def AnalyzeScorePanel(self, U, eval_, UtW, UtY, geno, geno_kind=L.GENO_F64_SNP_MAJOR, indicator_idv=None, l_mle_null=None,
+                          batch=LMM_BATCH_SIZE):
+        """`-lmm 3` for every column of UtY (n x T) over ONE pass of the genotypes and one product per block: a (T, p) array of
+        (beta, se, p_score) records (numpy in), or a (T, p, 3) device tensor (torch in; l_mle_null is then required).  Nulls that
+        are not given are fitted per phenotype (CalcLambdaNull)."""
+        if self.a_mode != 3:
+            raise ValueError("LMM.AnalyzeScorePanel: a_mode %d (the score panel is a_mode 3)" % self.a_mode)
+        tor = _is_torch(U)
+        if not tor:
+            UtY = np.ascontiguousarray(UtY, dtype=np.float64).reshape(len(eval_), -1)
+        T = UtY.shape[1]
+        if l_mle_null is None:
+            if tor:
+                raise ValueError("LMM.AnalyzeScorePanel: device inputs need l_mle_null")
+            l_mle_null = [CalcLambdaNull(eval_, UtW, UtY[:, t], self.l_min, self.l_max, self.n_region)["l_mle_null"]
+                          for t in range(T)]
+        self.setup_score_panel(U, eval_, UtW, UtY, l_mle_null)
+        try:
+            if indicator_idv is not None:
+                self.set_indicator(indicator_idv)
+            outs = []
+            for s0 in range(0, geno.shape[0], batch):
+                outs.append(self.batch_score_panel(geno[s0:s0 + batch], geno_kind))
+            if tor:
+                import torch
+                self.scorePanel = torch.cat(outs, dim=1) if outs else torch.empty((T, 0, 3), dtype=torch.float64, device=U.device)
+            else:
+                self.scorePanel = np.concatenate(outs, axis=1) if outs else np.zeros((T, 0), dtype=SCORE_DTYPE)
+        finally:
+            self.finish()
+        return self.scorePanel
 
     def AnalyzeBimbam(self, U, eval_, UtW, Uty, X_snpmajor_nan):
         """src/lmm.cpp:1660-1706 with the file reader factored out: X is SNP-major over the analysed

@@ -379,6 +379,7 @@ extern "C" int gemma_hip_lmm_finish(double *time_UtX_min, double *time_opt_min) 
   g_ctx.gxe_flip.release();
   g_ctx.gxe_ready = false;
   multi_release();
+  score_release();
   g_ctx.U = g_ctx.eval = g_ctx.Uty = nullptr;
   g_ctx.U_even_of = nullptr;
   g_ctx.U_even.release();

@@ -1,0 +1,198 @@
+// Part of gemma_hip.hip (ONE translation unit: the parts share the context g_ctx and the helpers of its anonymous namespace).
+// This part: the score panel (gemma_hip_lmm_score_panel_*): `-lmm 3` of T phenotypes over one U^T x, T in the thousands.
+//
+// The third LMM state beside the single-phenotype and the multi setup.  A setup builds, per phenotype, the c + 2 weight columns of
+// the closed form of CalcRLScore at the phenotype's null lambda (score_setup_kernel, lmm_score_panel.hip.h) -- n (c + 2) doubles
+// per phenotype, no lambda-search tables -- and a block is compute_utx as every batch entry point runs it followed by ONE product
+// kernel with the statistics in its epilogue (score_panel_kernel).
+
+static int score_check(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null) {
+  if (!cfg) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup: null cfg");
+  if (cfg->a_mode != 3)
+    return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup: a_mode %d (the score panel is a_mode 3; the other modes search lambda per SNP: "
+                                  "gemma_hip_lmm_multi_setup)", cfg->a_mode);
+  if (cfg->n_cvt < 1 || cfg->n_cvt > (size_t)SP_CMAX)
+    return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup: n_cvt=%zu covariates (1..%d)", cfg->n_cvt, SP_CMAX);
+  if (T == 0 || T > (size_t)INT_MAX - 64) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup: T=%zu phenotypes", T);
+  if (!l_mle_null) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup: l_mle_null of every phenotype is needed");
+  return GEMMA_HIP_OK;
+}
+static int score_fail(int rc) {
+  score_release();
+  return rc;
+}
+
+// After lmm_common_setup(cfg) with g_ctx.U / g_ctx.eval in place.  UtW_d: n x c, UtY_d: n x T row-major, both on the device;
+// l_mle_null: T values on the host.
+static int score_setup_dev(size_t T, const double *l_mle_null, const double *UtW_d, const double *UtY_d, hipStream_t s) {
+  const size_t n = g_ctx.cfg.n, c = g_ctx.cfg.n_cvt;
+  ScoreGeom g;
+  g.n = (int)n; g.nc = (int)((n + 15) / 16);
+  g.c = (int)c; g.nk = (int)c + 2;
+  g.T = (int)T; g.ng = (int)((T + 15) / 16);
+  const size_t r_bytes = (size_t)g.nc * (size_t)g.ng * (size_t)g.nk * 256 * 8;
+  if (g_ctx.score_R.reserve(r_bytes))
+    return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_setup: the weight matrix of %zu phenotypes does not fit (%zu bytes)", T, r_bytes);
+  if (g_ctx.score_Yt.reserve(T * n * 8))
+    return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_setup: U^T Y does not fit beside the weight matrix (%zu bytes)", T * n * 8);
+  if (g_ctx.UtWt.reserve(c * n * 8) || g_ctx.score_Pyy.reserve(T * 8) || g_ctx.score_lam.reserve(T * 8) || g_ctx.score_bad.reserve(4))
+    return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_setup: per-phenotype constants (%zu bytes)", c * n * 8 + 2 * T * 8 + 4);
+  g_ctx.score_T = T; // from here on a failure leaves a score state that lmm_common_setup / the caller's score_release takes down
+  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((c + 31) / 32), (unsigned)((n + 31) / 32)), dim3(32, 8), 0, s, UtW_d, (long)n,
+                     (long)c, (long)c, g_ctx.UtWt.as<double>(), (long)n);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((T + 31) / 32), (unsigned)((n + 31) / 32)), dim3(32, 8), 0, s, UtY_d, (long)n,
+                     (long)T, (long)T, g_ctx.score_Yt.as<double>(), (long)n);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemsetAsync(g_ctx.score_R.p, 0, r_bytes, s));
+  HIPCHK(hipMemsetAsync(g_ctx.score_bad.p, 0x7f, 4, s)); // above every phenotype index
+  HIPCHK(hipMemcpyAsync(g_ctx.score_lam.p, l_mle_null, T * 8, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(score_setup_kernel, dim3((unsigned)T), dim3(256), 0, s, g, g_ctx.eval, g_ctx.UtWt.as<double>(),
+                     g_ctx.score_Yt.as<double>(), g_ctx.score_lam.as<double>(), g_ctx.score_R.as<double>(),
+                     g_ctx.score_Pyy.as<double>(), g_ctx.score_bad.as<int>());
+  HIPCHK(hipGetLastError());
+  int bad = 0;
+  HIPCHK(hipMemcpyAsync(&bad, g_ctx.score_bad.p, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s)); // l_mle_null and `bad` are the caller's / a local
+  g_ctx.score_Yt.release();
+  if (bad >= 0 && (size_t)bad < T)
+    return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup: phenotype %d: UtW^T H UtW at l_mle_null = %g is not positive definite "
+                                  "(collinear covariates or a non-finite lambda)", bad, l_mle_null[bad]);
+  g_ctx.score_geom = g;
+  return GEMMA_HIP_OK;
+}
+
+extern "C" int gemma_hip_lmm_score_panel_setup_d(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null, const double *U_d,
+                                                 const double *eval_d, const double *UtW_d, const double *UtY_d, void *stream) {
+  NEED_INIT();
+  int rc = score_check(cfg, T, l_mle_null); // the shape first: T = 0 has no U^T Y to point to
+  if (rc) return rc;
+  if (!U_d || !eval_d || !UtW_d || !UtY_d) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup: null pointer");
+  if ((rc = lmm_common_setup(cfg))) return rc;
+  g_ctx.lmm_active = false; // a failed setup leaves no state behind
+  g_ctx.U = U_d;
+  g_ctx.U_even_of = nullptr;
+  g_ctx.eval = eval_d;
+  if ((rc = score_setup_dev(T, l_mle_null, UtW_d, UtY_d, S(stream)))) return score_fail(rc);
+  g_ctx.lmm_active = true;
+  return GEMMA_HIP_OK;
+}
+
+extern "C" int gemma_hip_lmm_score_panel_setup(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null, const double *U,
+                                               const double *eval, const double *UtW, const double *UtY) {
+  NEED_INIT();
+  int rc = score_check(cfg, T, l_mle_null); // the shape first: T = 0 has no U^T Y to point to
+  if (rc) return rc;
+  if (!U || !eval || !UtW || !UtY) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup: null pointer");
+  if ((rc = lmm_common_setup(cfg))) return rc;
+  g_ctx.lmm_active = false;
+  const size_t n = cfg->n, c = cfg->n_cvt;
+  if (g_ctx.own_U.reserve(n * n * 8) || g_ctx.own_eval.reserve(n * 8) || g_ctx.own_Uty.reserve(n * T * 8) ||
+      g_ctx.own_UtW.reserve(n * c * 8))
+    return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_setup: cannot allocate U and U^T Y (%zu bytes)", n * n * 8 + n * T * 8);
+  HIPCHK(hipMemcpy(g_ctx.own_U.p, U, n * n * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(g_ctx.own_eval.p, eval, n * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(g_ctx.own_Uty.p, UtY, n * T * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(g_ctx.own_UtW.p, UtW, n * c * 8, hipMemcpyHostToDevice));
+  g_ctx.U = g_ctx.own_U.as<double>();
+  g_ctx.U_even_of = nullptr;
+  g_ctx.eval = g_ctx.own_eval.as<double>();
+  if ((rc = score_setup_dev(T, l_mle_null, g_ctx.own_UtW.as<double>(), g_ctx.own_Uty.as<double>(), 0))) return score_fail(rc);
+  g_ctx.own_Uty.release(); // read by the setup kernel only
+  g_ctx.lmm_active = true;
+  return GEMMA_HIP_OK;
+}
+
+extern "C" int gemma_hip_lmm_score_panel_setup_kept(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null, const double *UtW,
+                                                    const double *UtY) {
+  NEED_INIT();
+  if (!g_ctx.kept_n) return fail(GEMMA_HIP_ESTATE, "lmm_score_panel_setup_kept: no kept U");
+  int rc = score_check(cfg, T, l_mle_null); // the shape first: T = 0 has no U^T Y to point to
+  if (rc) return rc;
+  if (!UtW || !UtY) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup_kept: null pointer");
+  if (cfg->n != g_ctx.kept_n)
+    return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup_kept: cfg.n=%zu, kept U is %zu", cfg->n, g_ctx.kept_n);
+  if ((rc = lmm_common_setup(cfg))) return rc;
+  g_ctx.lmm_active = false;
+  const size_t n = cfg->n, c = cfg->n_cvt;
+  if (g_ctx.own_Uty.reserve(n * T * 8) || g_ctx.own_UtW.reserve(n * c * 8))
+    return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_setup_kept: cannot allocate U^T Y (%zu bytes)", n * T * 8);
+  HIPCHK(hipMemcpy(g_ctx.own_Uty.p, UtY, n * T * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(g_ctx.own_UtW.p, UtW, n * c * 8, hipMemcpyHostToDevice));
+  g_ctx.U = kept_U();
+  g_ctx.U_even_of = nullptr;
+  g_ctx.eval = kept_eval();
+  if ((rc = score_setup_dev(T, l_mle_null, g_ctx.own_UtW.as<double>(), g_ctx.own_Uty.as<double>(), 0))) return score_fail(rc);
+  g_ctx.own_Uty.release();
+  g_ctx.lmm_active = true;
+  return GEMMA_HIP_OK;
+}
+
+// the product + statistics of the l rows of UtX -> out_d[t * l + s]
+static int launch_score_panel(const double *UtX, size_t l, size_t ld, gemma_score_rec *out_d, hipStream_t s) {
+  const ScoreGeom &g = g_ctx.score_geom;
+  ScoreArgs a;
+  a.UtX = UtX; a.ld = (long)ld; a.l = (long)l; a.g = g;
+  a.Rp = g_ctx.score_R.as<double>();
+  a.Pyy = g_ctx.score_Pyy.as<double>();
+  a.out = reinterpret_cast<ScoreRec *>(out_d);
+  a.lnbeta_half_df = g_ctx.assoc_proto.lnbeta_half_df;
+  const size_t npt = ((size_t)g.ng + 2 * SP_PG - 1) / (2 * SP_PG), nst = (l + 32 * SP_RG - 1) / (32 * SP_RG);
+  if (npt * nst > 0x7fffffffUL) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_batch: %zu x %zu tiles in one block", nst, npt);
+  ProfScope ps(GEMMA_STAGE_ASSOC, s);
+  const bool al = (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(UtX) & 15) == 0; // 16-byte loads of the row fragments
+  if (al) hipLaunchKernelGGL(score_panel_kernel<true>, dim3((unsigned)(npt * nst)), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(score_panel_kernel<false>, dim3((unsigned)(npt * nst)), dim3(256), 0, s, a);
+  HIPCHK(hipGetLastError());
+  return GEMMA_HIP_OK;
+}
+
+#define NEED_SCORE(who)                                                                                                        \
+  do {                                                                                                                         \
+    if (!g_ctx.lmm_active || !g_ctx.score_T) return fail(GEMMA_HIP_ESTATE, who " before gemma_hip_lmm_score_panel_setup");      \
+  } while (0)
+
+extern "C" int gemma_hip_lmm_score_panel_assoc_d(const double *UtX_d, size_t l, size_t ld_utx, gemma_score_rec *out_d, void *stream) {
+  NEED_INIT();
+  NEED_SCORE("lmm_score_panel_assoc");
+  if (l == 0) return GEMMA_HIP_OK;
+  if (!UtX_d || !out_d || ld_utx < g_ctx.cfg.n) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_assoc: bad UtX/ld");
+  {
+    int rcf = xp_flush_fwd(S(stream));
+    if (rcf) return rcf;
+  }
+  return launch_score_panel(UtX_d, l, ld_utx, out_d, S(stream));
+}
+
+extern "C" int gemma_hip_lmm_score_panel_batch_d(int kind, const void *geno, size_t l, size_t ld, gemma_score_rec *out_d, void *stream) {
+  NEED_INIT();
+  NEED_SCORE("lmm_score_panel_batch");
+  if (l == 0) return GEMMA_HIP_OK;
+  int rc = check_batch_args("lmm_score_panel_batch", kind, geno, l, ld, out_d);
+  if (rc) return rc;
+  hipStream_t s = S(stream);
+  double *UtX;
+  size_t ldx;
+  if ((rc = compute_utx(kind, geno, l, ld, -1, &UtX, &ldx, s))) return rc;
+  return launch_score_panel(UtX, l, ldx, out_d, s);
+}
+
+extern "C" int gemma_hip_lmm_score_panel_batch(int kind, const void *geno, size_t l, size_t ld, gemma_score_rec *out) {
+  NEED_INIT();
+  NEED_SCORE("lmm_score_panel_batch");
+  if (l == 0) return GEMMA_HIP_OK;
+  const size_t n = g_ctx.cfg.n, T = g_ctx.score_T;
+  const size_t per_row = (kind == GEMMA_GENO_PLINK_2BIT && g_ctx.have_map) ? g_ctx.ni_total : n;
+  const size_t need = min_ld_for(kind, per_row, l);
+  if (need == (size_t)-1) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_batch: unknown geno_kind %d", kind);
+  if (!geno || !out || ld < need) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_batch: ld=%zu < %zu", ld, need);
+  const size_t rows = (kind == GEMMA_GENO_F64_IDV_MAJOR) ? n : l;
+  const size_t esz = (kind == GEMMA_GENO_PLINK_2BIT) ? 1 : 8;
+  if (g_ctx.stage_in.reserve(rows * ld * esz) || g_ctx.stage_out.reserve(T * l * sizeof(gemma_score_rec)))
+    return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_batch: staging %zu bytes", rows * ld * esz + T * l * sizeof(gemma_score_rec));
+  HIPCHK(hipMemcpy2D(g_ctx.stage_in.p, ld * esz, geno, ld * esz, need * esz, rows, hipMemcpyHostToDevice));
+  int rc = gemma_hip_lmm_score_panel_batch_d(kind, g_ctx.stage_in.p, l, ld, g_ctx.stage_out.as<gemma_score_rec>(), nullptr);
+  if (rc) return rc;
+  HIPCHK(hipMemcpy(out, g_ctx.stage_out.p, T * l * sizeof(gemma_score_rec), hipMemcpyDeviceToHost));
+  return GEMMA_HIP_OK;
+}

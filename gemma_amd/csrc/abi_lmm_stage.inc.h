@@ -24,11 +24,18 @@ static void multi_release() {
   g_ctx.multi_T = 0;
   g_ctx.multi_G = 0;
 }
+static void score_release() {
+  g_ctx.score_R.release(); g_ctx.score_Pyy.release(); g_ctx.score_Yt.release(); g_ctx.score_lam.release(); g_ctx.score_bad.release();
+  g_ctx.score_T = 0;
+}
 // the single-phenotype entry points after a multi setup: the live slot is nobody's
 #define NEED_SINGLE(who)                                                                                                  \
   do {                                                                                                                    \
     if (g_ctx.multi_T)                                                                                                    \
       return fail(GEMMA_HIP_ESTATE, who ": the setup holds %zu phenotypes (gemma_hip_lmm_multi_batch)", g_ctx.multi_T);   \
+    if (g_ctx.score_T)                                                                                                    \
+      return fail(GEMMA_HIP_ESTATE, who ": the setup is a score panel of %zu phenotypes (gemma_hip_lmm_score_panel_batch)", \
+                  g_ctx.score_T);                                                                                         \
   } while (0)
 
 static int lmm_common_setup(const gemma_lmm_cfg *cfg) {
@@ -44,6 +51,7 @@ static int lmm_common_setup(const gemma_lmm_cfg *cfg) {
   if (cfg->n > 0x7fffffffUL) return fail(GEMMA_HIP_EINVAL, "lmm_setup: n too large");
   g_ctx.cfg = *cfg;
   if (g_ctx.multi_T) multi_release(); // a multi setup that was not finished: its slots go with it
+  if (g_ctx.score_T) score_release();
   {
     // the eigensolver's workspace pool (gemma_hip_eigh_reserve / GEMMA_HIP_EIGH_CACHE): a pool that holds more than a quarter of
     // the device would stand in the way of this setup's own buffers (n = 50 000: 100+ GB idle beside 70 GB of digit planes)

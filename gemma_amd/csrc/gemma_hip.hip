@@ -23,6 +23,7 @@
 #include "lm_assoc.hip.h"
 #include "lmm_assoc.hip.h"
 #include "lmm_grid.hip.h"
+#include "lmm_score_panel.hip.h"
 #include "i8gemm.hip.h"
 #include "i8gemm_sparse.hip.h"
 #include "i8gemm_sparse2.hip.h"
@@ -241,6 +242,10 @@ struct Ctx {
   DevBuf multi_Yt;                 // U^T Y transposed (T x n): slot t's Uty is row t
   DevBuf multi_R, multi_T_buf;     // shared table: a group's weight matrix (one per group, back to back) and its G tables
   int multi_G = 0;                 // phenotypes per pass of the shared table product (0: no shared table for this setup)
+  // score panel (gemma_hip_lmm_score_panel_setup): -lmm 3 of score_T phenotypes from one product per block (lmm_score_panel.hip.h)
+  size_t score_T = 0;              // 0: no score-panel setup
+  ScoreGeom score_geom;
+  DevBuf score_R, score_Pyy, score_Yt, score_lam, score_bad; // weight matrix, P_yy and lambda per phenotype; U^T Y transposed (setup only)
 
   // linear model (-lm) state
   bool lm_active = false;
@@ -420,6 +425,8 @@ extern "C" void gemma_hip_shutdown(void) {
   g_ctx.slots.clear();
   g_ctx.multi_Yt.release(); g_ctx.multi_R.release(); g_ctx.multi_T_buf.release();
   g_ctx.multi_T = 0;
+  g_ctx.score_R.release(); g_ctx.score_Pyy.release(); g_ctx.score_Yt.release(); g_ctx.score_lam.release(); g_ctx.score_bad.release();
+  g_ctx.score_T = 0;
   g_ctx.U_even_of = nullptr;
   pipe_release(); // pinned slots, copy stream and events of the pipelined host-block path
   xp_release();
@@ -551,6 +558,7 @@ extern "C" int gemma_hip_dgemm(char ta, char tb, size_t M, size_t N, size_t K, d
 #include "abi_gxe_lm.inc.h"
 #include "abi_kept_comm.inc.h"
 #include "abi_lmm_multi.inc.h"
+#include "abi_lmm_score_panel.inc.h"
 #include "abi_vc.inc.h"
 #include "abi_prdt.inc.h"
 #include "abi_mqs.inc.h"

@@ -268,6 +268,39 @@ int gemma_hip_lmm_multi_setup_kept(const gemma_lmm_cfg *cfg, size_t T, const dou
 int gemma_hip_lmm_multi_batch(int geno_kind, const void *geno, size_t l, size_t ld, gemma_sumstat *out);
 int gemma_hip_lmm_multi_batch_d(int geno_kind, const void *geno_d, size_t l, size_t ld, gemma_sumstat *out_d, void *stream);
 
+/* ---- score panel: `-lmm 3` of T phenotypes over one U^T x, T in the thousands -------------------------------- */
+/* The first pass over an omics panel (expression, protein, metabolite levels on the same individuals, kinship and covariates) is
+ * the score test at each phenotype's null lambda: LMM::CalcRLScore (src/lmm.cpp:1170-1211) at l_mle_null, no lambda search per
+ * SNP.  At a fixed lambda the statistic is a closed form of c + 2 weighted sums over the individuals per (SNP, phenotype) pair, and
+ * for all pairs of a block those sums are ONE product of [x.x | x] (the block's U^T x) against an n x T (c + 2) weight matrix:
+ * a block costs ingest + U^T x once and one matrix kernel with the statistics in its epilogue.  The reference has no such mode
+ * (it runs `-lmm 3 -n t` once per trait); the records are the ones those runs print.
+ * cfg->a_mode must be 3 (the other modes search lambda per SNP: gemma_hip_lmm_multi_*) and cfg->n_cvt 1..16, else GEMMA_HIP_EINVAL;
+ * cfg's own two null fields are ignored.  l_mle_null: T values on the host, UtY: n x T row-major.  T >= 1 with no fixed upper cap:
+ * a setup keeps 8 n (c + 2) bytes per phenotype (rounded up to groups of 16), and buffers that do not fit return GEMMA_HIP_ENOMEM
+ * with the byte count in the message.  A phenotype whose UtW^T diag(h) UtW is not positive definite (collinear covariates, a
+ * non-finite lambda) fails the setup with GEMMA_HIP_EINVAL and a message naming it.
+ * gemma_hip_lmm_set_indicator and gemma_hip_lmm_finish serve this form too; every single-phenotype or multi batch entry point after a
+ * score-panel setup, and a score-panel batch after a single-phenotype or multi setup, return GEMMA_HIP_ESTATE.
+ * Rows that are monomorphic or all-missing after imputation get what the formulas give on a P_xx of rounding noise. */
+typedef struct {
+  double beta, se, p_score;
+} gemma_score_rec;
+int gemma_hip_lmm_score_panel_setup(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null,
+                                    const double *U, const double *eval, const double *UtW, const double *UtY);
+/* device pointers; U_d and eval_d are borrowed until gemma_hip_lmm_finish, UtW_d and UtY_d are read before the call returns */
+int gemma_hip_lmm_score_panel_setup_d(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null,
+                                      const double *U_d, const double *eval_d, const double *UtW_d, const double *UtY_d, void *stream);
+/* on the kept U (gemma_hip_eigh_kept_K / gemma_hip_eigh_keep); UtW, UtY: host */
+int gemma_hip_lmm_score_panel_setup_kept(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null,
+                                         const double *UtW, const double *UtY);
+/* one block: ingest + U^T x as gemma_hip_lmm_batch runs them (same genotype kinds, indicator mapping and mean imputation), then the
+ * product.  out: T x l records, phenotype-major (out[t * l + s]). */
+int gemma_hip_lmm_score_panel_batch(int geno_kind, const void *geno, size_t l, size_t ld, gemma_score_rec *out);
+int gemma_hip_lmm_score_panel_batch_d(int geno_kind, const void *geno_d, size_t l, size_t ld, gemma_score_rec *out_d, void *stream);
+/* the product alone, on a caller-made U^T x (l x n SNP-major, leading dimension ld_utx >= n) */
+int gemma_hip_lmm_score_panel_assoc_d(const double *UtX_d, size_t l, size_t ld_utx, gemma_score_rec *out_d, void *stream);
+
 /* ---- multivariate LMM (-lmm 1..4 -n a b c ...) ------------------------------------ */
 /* MVLMM::AnalyzeBimbam / AnalyzePlink, src/mvlmm.cpp:2972-3416 / :3418-3899, and with opt->gxe the interaction test of
  * AnalyzeBimbamGXE / AnalyzePlinkGXE (:3970-4414 / :4416-4870).  d phenotypes (1..GEMMA_MV_DMAX), n_cvt covariates with

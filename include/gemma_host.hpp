@@ -780,6 +780,49 @@ public:
     file_out = keep_out;
   }
 
+  // ---- score panel: `-lmm 3` of T phenotypes, one product per block (gemma_hip_lmm_score_panel_*) ----
+  // a_mode must be 3; UtY: ni_test x T, l_mle_null_multi: the T null lambdas.  scorePanel[t][s] = (beta, se, p_score) of phenotype t
+  // and the s-th analysed SNP -- what `-lmm 3 -n t` prints.  T in the thousands: a block's records are T x l x 24 bytes on the host.
+  std::vector<std::vector<gemma_score_rec>> scorePanel;
+
+  void AnalyzePlinkScorePanel(const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY) {
+    const std::string file_bed = file_bfile + ".bed";
+    std::ifstream infile(file_bed.c_str(), std::ios::binary);
+    if (!infile) throw std::runtime_error("error reading genotype (.bed) file");
+    const size_t T = setup_score_panel(U, eval, UtW, UtY);
+    enforce_hip(gemma_hip_lmm_set_indicator(indicator_idv.data(), indicator_idv.size()), "AnalyzePlinkScorePanel");
+    const size_t n_bit = (ni_total + 3) / 4;
+    const size_t B = io_block_rows(LMM_BATCH_SIZE);
+    std::vector<gemma_score_rec> out(T * B);
+    size_t t_next = 0;
+    const std::vector<int> keep = analysed_snps();
+    BlockPrefetch pf(B * n_bit, [&](void *slot, int) {
+      return read_bed_rows(infile, keep, t_next, n_bit, static_cast<unsigned char *>(slot), B);
+    });
+    for (;;) {
+      void *slot = nullptr;
+      const size_t l = pf.next(slot);
+      if (l == (size_t)-1) throw std::runtime_error("error reading genotype (.bed) file (truncated)");
+      if (l == 0) break;
+      batch_compute_score_panel(GEMMA_GENO_PLINK_2BIT, slot, l, n_bit, out);
+    }
+    finish();
+  }
+
+  void AnalyzeFeedScorePanel(const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY, RowFeeder &feed,
+                             size_t max_rows, size_t ld) {
+    const size_t T = setup_score_panel(U, eval, UtW, UtY);
+    std::vector<gemma_score_rec> out(T * max_rows);
+    for (;;) {
+      const double *X = nullptr;
+      const size_t l = feed(X);
+      if (l == 0) break;
+      if (l > max_rows) throw HipError(GEMMA_HIP_EINVAL, "AnalyzeFeedScorePanel: block larger than max_rows");
+      batch_compute_score_panel(GEMMA_GENO_F64_SNP_MAJOR, X, l, ld, out);
+    }
+    finish();
+  }
+
   // WriteFiles, src/lmm.cpp:101-225
   void WriteFiles() {
     const std::string file_str = path_out + "/" + file_out + ".assoc.txt";
@@ -868,6 +911,30 @@ private:
         SUMSTAT s = {o.beta, o.se, o.lambda_remle, o.lambda_mle, o.p_wald, o.p_lrt, o.p_score, o.logl_H1};
         sumStatMulti[t].push_back(s);
       }
+  }
+  size_t setup_score_panel(const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY) {
+    if ((!kept_U && U->tda != U->size2) || UtW->tda != UtW->size2 || eval->stride != 1 || UtY->tda != UtY->size2)
+      throw HipError(GEMMA_HIP_EINVAL, "LMM: contiguous U/UtW/eval/UtY required");
+    if (shard_world > 1) throw HipError(GEMMA_HIP_EINVAL, "LMM: the score panel is not sharded over ranks");
+    const size_t T = UtY->size2;
+    if (l_mle_null_multi.size() != T) throw HipError(GEMMA_HIP_EINVAL, "LMM: l_mle_null_multi needs one value per phenotype");
+    ni_test = UtY->size1;
+    n_cvt = UtW->size2;
+    gemma_lmm_cfg cfg;
+    cfg.a_mode = a_mode; cfg.n = ni_test; cfg.n_cvt = n_cvt; cfg.l_min = l_min; cfg.l_max = l_max;
+    cfg.n_region = n_region; cfg.l_mle_null = 0.0; cfg.logl_mle_H0 = 0.0; cfg.plink_nan_rule = 0;
+    if (kept_U)
+      enforce_hip(gemma_hip_lmm_score_panel_setup_kept(&cfg, T, l_mle_null_multi.data(), UtW->data, UtY->data), "LMM::AnalyzeScorePanel");
+    else
+      enforce_hip(gemma_hip_lmm_score_panel_setup(&cfg, T, l_mle_null_multi.data(), U->data, eval->data, UtW->data, UtY->data),
+                  "LMM::AnalyzeScorePanel");
+    scorePanel.assign(T, std::vector<gemma_score_rec>());
+    return T;
+  }
+  void batch_compute_score_panel(int kind, const void *geno, size_t l, size_t ld, std::vector<gemma_score_rec> &out) {
+    if (l == 0) return;
+    enforce_hip(gemma_hip_lmm_score_panel_batch(kind, geno, l, ld, out.data()), "batch_compute (score panel)");
+    for (size_t t = 0; t < scorePanel.size(); ++t) scorePanel[t].insert(scorePanel[t].end(), out.begin() + t * l, out.begin() + (t + 1) * l);
   }
   // batch_compute, src/lmm.cpp:1513-1564
   void batch_compute(int kind, const void *geno, size_t l, size_t ld, std::vector<gemma_sumstat> &out) {
