@@ -39,6 +39,7 @@ SYMBOLS = [
     "gemma_hip_lmm_multi_batch_d",
     "gemma_hip_lmm_score_panel_setup", "gemma_hip_lmm_score_panel_setup_d", "gemma_hip_lmm_score_panel_setup_kept",
     "gemma_hip_lmm_score_panel_batch", "gemma_hip_lmm_score_panel_batch_d", "gemma_hip_lmm_score_panel_assoc_d",
+    "gemma_hip_lmm_score_panel_hits_batch", "gemma_hip_lmm_score_panel_hits_batch_d", "gemma_hip_lmm_score_panel_hits_assoc_d",
 ]
 LMM_MULTI_MAX = 64
 COMM_ID_BYTES = 128
@@ -56,6 +57,16 @@ class SumStat(C.Structure):
 class ScoreRec(C.Structure):
     """gemma_score_rec: one (phenotype, SNP) pair of the score panel"""
     _fields_ = [(k, C.c_double) for k in ("beta", "se", "p_score")]
+
+
+class ScoreHit(C.Structure):
+    """gemma_score_hit: a pair of the score panel with p_score <= p_max; snp is the row inside the block"""
+    _fields_ = [("snp", C.c_uint32), ("pheno", C.c_uint32), ("beta", C.c_double), ("se", C.c_double), ("p_score", C.c_double)]
+
+
+class ScoreBest(C.Structure):
+    """gemma_score_best: the best pair of one phenotype over a block; snp -1 and NaN fields: none"""
+    _fields_ = [("beta", C.c_double), ("se", C.c_double), ("p_score", C.c_double), ("snp", C.c_int64)]
 
 
 class LmmCfg(C.Structure):
@@ -195,6 +206,9 @@ def lib():
     L.gemma_hip_lmm_score_panel_batch.argtypes = [ci, vp, sz, sz, vp]
     L.gemma_hip_lmm_score_panel_batch_d.argtypes = [ci, vp, sz, sz, vp, vp]
     L.gemma_hip_lmm_score_panel_assoc_d.argtypes = [dp, sz, sz, vp, vp]
+    L.gemma_hip_lmm_score_panel_hits_batch.argtypes = [ci, vp, sz, sz, C.c_double, vp, sz, vp, vp]
+    L.gemma_hip_lmm_score_panel_hits_batch_d.argtypes = [ci, vp, sz, sz, C.c_double, vp, sz, vp, vp, vp]
+    L.gemma_hip_lmm_score_panel_hits_assoc_d.argtypes = [dp, sz, sz, C.c_double, vp, sz, vp, vp, vp]
     L.gemma_hip_dbg_i8_digits.argtypes = [sz, C.POINTER(ci)]
     L.gemma_hip_dbg_last_utx_path.argtypes = [C.POINTER(ci)]
     L.gemma_hip_dbg_last_utx_kernel.argtypes = [C.POINTER(UtxKernelInfo)]

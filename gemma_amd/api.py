@@ -15,6 +15,7 @@ Arrays may be numpy arrays (host entry points; the library stages through HBM) o
 tensors (device entry points on torch's current stream: torch is only the allocator/stream here).
 All compute happens in gemma_amd/libgemma_hip.so; nothing in this module has a CPU fallback.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -25,6 +26,8 @@ SUMSTAT_DTYPE = np.dtype([(k, "f8") for k in
                           ("beta", "se", "lambda_remle", "lambda_mle", "p_wald", "p_lrt", "p_score",
                            "logl_H1")])
 SCORE_DTYPE = np.dtype([(k, "f8") for k in ("beta", "se", "p_score")])  # gemma_score_rec
+SCORE_HIT_DTYPE = np.dtype([("snp", "u4"), ("pheno", "u4"), ("beta", "f8"), ("se", "f8"), ("p_score", "f8")])  # gemma_score_hit
+SCORE_BEST_DTYPE = np.dtype([("beta", "f8"), ("se", "f8"), ("p_score", "f8"), ("snp", "i8")])  # gemma_score_best
 LMM_BATCH_SIZE = 20000  # src/lmm.h:33
 K_BATCH_SIZE = 20000  # src/param.h:32
 
@@ -371,6 +374,28 @@ def CalcLambdaNull(eval_, UtW, Uty, l_min=1e-5, l_max=1e5, n_region=10, trace_G=
 
 
 # ----------------------------------------------------------------------------- B4
+ScoreHitsDev = collections.namedtuple("ScoreHitsDev", "snp pheno stats")  # device tensors: int64 (m,), int64 (m,), float64 (m, 3)
+ScoreBestDev = collections.namedtuple("ScoreBestDev", "stats snp")       # device tensors: float64 (T, 3), int64 (T,)
+
+
+def reduce_score_best(blocks, T):
+    """The best pair per phenotype over several blocks: blocks is a sequence of (offset, (T,) SCORE_BEST_DTYPE array with snp inside
+    the block).  The smallest p_score wins, the smaller snp (offset + row) among equal p_score; a NaN p_score or snp -1 never."""
+    out = np.zeros(T, dtype=SCORE_BEST_DTYPE)
+    for k in ("beta", "se", "p_score"):
+        out[k] = np.nan
+    out["snp"] = -1
+    for s0, b in blocks:
+        snp = np.where(b["snp"] >= 0, b["snp"] + s0, -1)
+        p, q = b["p_score"], out["p_score"]
+        with np.errstate(invalid="ignore"):
+            take = (snp >= 0) & ~np.isnan(p) & ((out["snp"] < 0) | (p < q) | ((p == q) & (snp < out["snp"])))
+        new = b[take].copy()
+        new["snp"] = snp[take]
+        out[take] = new
+    return out
+
+
 class LMM:
     """Mirror of class LMM (src/lmm.h:49-125): the fields CopyFromParam fills (src/lmm.cpp:56-90)
     and the Analyze* drivers.  sumStat is a numpy record array with SUMSTAT's fields."""
@@ -687,6 +712,123 @@ class LMM:
         finally:
             self.finish()
         return self.scorePanel
+
+    # -- the hits form of the score panel: pairs with p_score <= p_max and the best pair per phenotype --
+    def _hits_cap(self, l, p_max, cap):
+        if cap is not None:
+            return int(cap)
+        pairs = self.n_ph * l
+        return int(min(pairs, max(4096, 2 * p_max * pairs + 1024)))
+
+    def _hits_dev(self, call, l, p_max, cap, device):
+        """the torch side of a hits call: call(raw, cap, cnt, best) -> rc; repeats once with a sufficient list"""
+        import torch
+        T = self.n_ph
+        cap = self._hits_cap(l, p_max, cap)
+        cnt = torch.zeros(1, dtype=torch.int64, device=device)
+        best = torch.empty((T, 4), dtype=torch.int64, device=device)
+        while True:
+            raw = torch.empty((max(cap, 1), 4), dtype=torch.int64, device=device)
+            L.check(call(C.c_void_p(raw.data_ptr()) if cap else None, cap, C.c_void_p(cnt.data_ptr()), C.c_void_p(best.data_ptr())),
+                    "LMM.score_panel_hits")
+            n = int(cnt.item())
+            if n <= cap:
+                break
+            cap = n
+        raw = raw[:n]
+        key = raw[:, 0]  # snp in the low, pheno in the high 32 bits
+        snp, pheno = key & 0xffffffff, (key >> 32) & 0xffffffff
+        order = torch.argsort((pheno << 32) | snp)
+        hits = ScoreHitsDev(snp[order], pheno[order], raw[:, 1:].contiguous().view(torch.float64)[order])
+        return hits, ScoreBestDev(best[:, :3].contiguous().view(torch.float64), best[:, 3].clone())
+
+    def batch_score_panel_hits(self, geno, geno_kind, p_max, cap=None):
+        """One block of SNPs -> (hits, best).  numpy in: hits is a SCORE_HIT_DTYPE array of every pair with p_score <= p_max, sorted
+        by (pheno, snp), snp the row inside the block; best a (T,) SCORE_BEST_DTYPE array (snp -1, NaN: no pair).  torch in:
+        ScoreHitsDev(snp, pheno, stats (m, 3)) and ScoreBestDev(stats (T, 3), snp) of device tensors, sorted the same way.  cap: the
+        size of the first list; a block with more hits is run again with a list that holds them."""
+        T = self.n_ph
+        p_max = float(p_max)
+        if _is_torch(geno):
+            l, ld = geno.shape[0], _tld(geno)
+            gp, st = C.c_void_p(geno.data_ptr()), _stream()
+            return self._hits_dev(lambda raw, cap_, cnt, best: L.lib().gemma_hip_lmm_score_panel_hits_batch_d(
+                geno_kind, gp, l, ld, p_max, raw, cap_, cnt, best, st), l, p_max, cap, geno.device)
+        l = geno.shape[1] if geno_kind == L.GENO_F64_IDV_MAJOR else geno.shape[0]
+        ld = geno.strides[0] // geno.itemsize
+        cap = self._hits_cap(l, p_max, cap)
+        best = np.zeros(T, dtype=SCORE_BEST_DTYPE)
+        cnt = C.c_ulonglong(0)
+        while True:
+            hits = np.zeros(cap, dtype=SCORE_HIT_DTYPE)
+            L.check(L.lib().gemma_hip_lmm_score_panel_hits_batch(geno_kind, _ptr(geno), l, ld, p_max, _ptr(hits) if cap else None, cap,
+                                                                 C.cast(C.byref(cnt), C.c_void_p), _ptr(best)), "LMM.batch_score_panel_hits")
+            if cnt.value <= cap:
+                return hits[:cnt.value], best
+            cap = int(cnt.value)
+
+    def assoc_score_panel_hits(self, UtX, p_max, cap=None):
+        """The hits form of the product alone, on a device-resident SNP-major UtX (torch): as batch_score_panel_hits for torch."""
+        l, ld, p_max = UtX.shape[0], _tld(UtX), float(p_max)
+        xp, st = C.c_void_p(UtX.data_ptr()), _stream()
+        return self._hits_dev(lambda raw, cap_, cnt, best: L.lib().gemma_hip_lmm_score_panel_hits_assoc_d(
+            xp, l, ld, p_max, raw, cap_, cnt, best, st), l, p_max, cap, UtX.device)
+
+    def AnalyzeScorePanelHits(self, U, eval_, UtW, UtY, geno, geno_kind=L.GENO_F64_SNP_MAJOR, p_max=1e-5, indicator_idv=None,
+                              l_mle_null=None, batch=LMM_BATCH_SIZE):
+        """AnalyzeScorePanel without the (T, p) records: one pass over the genotypes -> (hits, best) as batch_score_panel_hits gives
+        them, with snp the index over the whole scan (block offset + row); best is reduced over the blocks (the smallest p_score,
+        the smaller snp among equals, NaN never).  Nulls are fitted as AnalyzeScorePanel fits them."""
+        if self.a_mode != 3:
+            raise ValueError("LMM.AnalyzeScorePanelHits: a_mode %d (the score panel is a_mode 3)" % self.a_mode)
+        tor = _is_torch(U)
+        if not tor:
+            UtY = np.ascontiguousarray(UtY, dtype=np.float64).reshape(len(eval_), -1)
+        T = UtY.shape[1]
+        if l_mle_null is None:
+            if tor:
+                raise ValueError("LMM.AnalyzeScorePanelHits: device inputs need l_mle_null")
+            l_mle_null = [CalcLambdaNull(eval_, UtW, UtY[:, t], self.l_min, self.l_max, self.n_region)["l_mle_null"]
+                          for t in range(T)]
+        self.setup_score_panel(U, eval_, UtW, UtY, l_mle_null)
+        try:
+            if indicator_idv is not None:
+                self.set_indicator(indicator_idv)
+            parts, bests = [], []
+            for s0 in range(0, geno.shape[0], batch):
+                h, b = self.batch_score_panel_hits(geno[s0:s0 + batch], geno_kind, p_max)
+                parts.append((s0, h))
+                bests.append((s0, b))
+        finally:
+            self.finish()
+        if tor:
+            import torch
+            dev = U.device
+            if parts:
+                hits = ScoreHitsDev(torch.cat([h.snp + s0 for s0, h in parts]), torch.cat([h.pheno for _, h in parts]),
+                                    torch.cat([h.stats for _, h in parts]))
+                order = torch.argsort((hits.pheno << 32) | hits.snp)
+                hits = ScoreHitsDev(hits.snp[order], hits.pheno[order], hits.stats[order])
+            else:
+                hits = ScoreHitsDev(torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+                                    torch.empty((0, 3), dtype=torch.float64, device=dev))
+            stats = torch.full((T, 3), float("nan"), dtype=torch.float64, device=dev)
+            snp = torch.full((T,), -1, dtype=torch.int64, device=dev)
+            for s0, b in bests:
+                bs = torch.where(b.snp >= 0, b.snp + s0, b.snp)
+                p, q = b.stats[:, 2], stats[:, 2]
+                take = (bs >= 0) & ~torch.isnan(p) & ((snp < 0) | (p < q) | ((p == q) & (bs < snp)))
+                stats = torch.where(take[:, None], b.stats, stats)
+                snp = torch.where(take, bs, snp)
+            best = ScoreBestDev(stats, snp)
+        else:
+            hits = np.concatenate([h for _, h in parts]) if parts else np.zeros(0, dtype=SCORE_HIT_DTYPE)
+            off = np.concatenate([np.full(len(h), s0, dtype=np.uint32) for s0, h in parts]) if parts else np.zeros(0, dtype=np.uint32)
+            hits["snp"] += off
+            hits = hits[np.lexsort((hits["snp"], hits["pheno"]))]
+            best = reduce_score_best(bests, T)
+        self.scoreHits, self.scoreBest = hits, best
+        return hits, best
 
     def AnalyzeBimbam(self, U, eval_, UtW, Uty, X_snpmajor_nan):
         """src/lmm.cpp:1660-1706 with the file reader factored out: X is SNP-major over the analysed

@@ -37,6 +37,7 @@ static int score_setup_dev(size_t T, const double *l_mle_null, const double *UtW
     return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_setup: U^T Y does not fit beside the weight matrix (%zu bytes)", T * n * 8);
   if (g_ctx.UtWt.reserve(c * n * 8) || g_ctx.score_Pyy.reserve(T * 8) || g_ctx.score_lam.reserve(T * 8) || g_ctx.score_bad.reserve(4))
     return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_setup: per-phenotype constants (%zu bytes)", c * n * 8 + 2 * T * 8 + 4);
+  g_ctx.score_fthr_p = -1.0; // the hits form's threshold belongs to a setup's df
   g_ctx.score_T = T; // from here on a failure leaves a score state that lmm_common_setup / the caller's score_release takes down
   hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((c + 31) / 32), (unsigned)((n + 31) / 32)), dim3(32, 8), 0, s, UtW_d, (long)n,
                      (long)c, (long)c, g_ctx.UtWt.as<double>(), (long)n);
@@ -194,5 +195,139 @@ extern "C" int gemma_hip_lmm_score_panel_batch(int kind, const void *geno, size_
   int rc = gemma_hip_lmm_score_panel_batch_d(kind, g_ctx.stage_in.p, l, ld, g_ctx.stage_out.as<gemma_score_rec>(), nullptr);
   if (rc) return rc;
   HIPCHK(hipMemcpy(out, g_ctx.stage_out.p, T * l * sizeof(gemma_score_rec), hipMemcpyDeviceToHost));
+  return GEMMA_HIP_OK;
+}
+
+// ---- the hits form: pairs with p_score <= p_max, the best pair per phenotype (lmm_score_panel.hip.h) ----
+static int score_hits_check(const char *who, size_t l, double p_max, const void *hits, size_t cap, const void *n_hits) {
+  if (!(p_max >= 0.0 && p_max <= 1.0)) return fail(GEMMA_HIP_EINVAL, "%s: p_max=%g is not in [0, 1]", who, p_max);
+  if (!n_hits) return fail(GEMMA_HIP_EINVAL, "%s: n_hits is needed", who);
+  if (!hits && cap) return fail(GEMMA_HIP_EINVAL, "%s: a null list of %zu entries (count only: cap = 0)", who, cap);
+  if (l > 0xffffffffUL) return fail(GEMMA_HIP_EINVAL, "%s: l=%zu rows (snp is 32 bits)", who, l);
+  return GEMMA_HIP_OK;
+}
+
+// the block's counter to zero and, for l == 0, the best of an empty block
+static int score_hits_empty(unsigned long long *n_hits_d, gemma_score_best *best_d, hipStream_t s) {
+  HIPCHK(hipMemsetAsync(n_hits_d, 0, sizeof(unsigned long long), s));
+  if (best_d) {
+    const ScoreGeom &g = g_ctx.score_geom;
+    hipLaunchKernelGGL(score_best_kernel, dim3((unsigned)((g.T + 255) / 256)), dim3(256), 0, s, g, 0L, (const ScoreCell *)nullptr,
+                       g_ctx.score_Pyy.as<double>(), g_ctx.assoc_proto.lnbeta_half_df, reinterpret_cast<ScoreBest *>(best_d));
+    HIPCHK(hipGetLastError());
+  }
+  return GEMMA_HIP_OK;
+}
+
+static int launch_score_hits(const double *UtX, size_t l, size_t ld, double p_max, gemma_score_hit *hits_d, size_t cap,
+                             unsigned long long *n_hits_d, gemma_score_best *best_d, hipStream_t s) {
+  const ScoreGeom &g = g_ctx.score_geom;
+  const size_t npt = ((size_t)g.ng + 2 * SP_PG - 1) / (2 * SP_PG), nst = (l + 32 * SP_RG - 1) / (32 * SP_RG);
+  if (npt * nst > 0x7fffffffUL) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_hits: %zu x %zu tiles in one block", nst, npt);
+  const size_t ntile = (l + 31) / 32;
+  if (g_ctx.score_fthr.reserve(8)) return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_hits: 8 bytes");
+  if (best_d && g_ctx.score_cells.reserve(ntile * (size_t)g.T * sizeof(ScoreCell)))
+    return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_hits: the per-wave best of %zu row tiles x %d phenotypes (%zu bytes)", ntile, g.T,
+                ntile * (size_t)g.T * sizeof(ScoreCell));
+  const double lnb = g_ctx.assoc_proto.lnbeta_half_df;
+  if (g_ctx.score_fthr_p != p_max || g_ctx.score_fthr_s != s) { // once per (setup, p_max, stream)
+    hipLaunchKernelGGL(score_fcrit_kernel, dim3(1), dim3(64), 0, s, p_max, (double)(g.n - g.c - 1), lnb, g_ctx.score_fthr.as<double>());
+    HIPCHK(hipGetLastError());
+    g_ctx.score_fthr_p = p_max;
+    g_ctx.score_fthr_s = s;
+  }
+  HIPCHK(hipMemsetAsync(n_hits_d, 0, sizeof(unsigned long long), s));
+  ScoreArgs a;
+  a.UtX = UtX; a.ld = (long)ld; a.l = (long)l; a.g = g;
+  a.Rp = g_ctx.score_R.as<double>();
+  a.Pyy = g_ctx.score_Pyy.as<double>();
+  a.out = nullptr;
+  a.lnbeta_half_df = lnb;
+  a.p_max = p_max;
+  a.f_thr = g_ctx.score_fthr.as<double>();
+  a.hits = reinterpret_cast<ScoreHit *>(hits_d);
+  a.cap = cap;
+  a.n_hits = n_hits_d;
+  a.cells = best_d ? g_ctx.score_cells.as<ScoreCell>() : nullptr;
+  ProfScope ps(GEMMA_STAGE_ASSOC, s);
+  const bool al = (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(UtX) & 15) == 0;
+  if (al) hipLaunchKernelGGL((score_panel_kernel<true, true>), dim3((unsigned)(npt * nst)), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((score_panel_kernel<false, true>), dim3((unsigned)(npt * nst)), dim3(256), 0, s, a);
+  HIPCHK(hipGetLastError());
+  if (best_d) {
+    hipLaunchKernelGGL(score_best_kernel, dim3((unsigned)((g.T + 255) / 256)), dim3(256), 0, s, g, (long)ntile,
+                       (const ScoreCell *)g_ctx.score_cells.as<ScoreCell>(), g_ctx.score_Pyy.as<double>(), lnb,
+                       reinterpret_cast<ScoreBest *>(best_d));
+    HIPCHK(hipGetLastError());
+  }
+  return GEMMA_HIP_OK;
+}
+
+extern "C" int gemma_hip_lmm_score_panel_hits_assoc_d(const double *UtX_d, size_t l, size_t ld_utx, double p_max,
+                                                      gemma_score_hit *hits_d, size_t cap, unsigned long long *n_hits_d,
+                                                      gemma_score_best *best_d, void *stream) {
+  NEED_INIT();
+  NEED_SCORE("lmm_score_panel_hits_assoc");
+  int rc = score_hits_check("lmm_score_panel_hits_assoc", l, p_max, hits_d, cap, n_hits_d);
+  if (rc) return rc;
+  if (l == 0) return score_hits_empty(n_hits_d, best_d, S(stream));
+  if (!UtX_d || ld_utx < g_ctx.cfg.n) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_hits_assoc: bad UtX/ld");
+  if ((rc = xp_flush_fwd(S(stream)))) return rc;
+  return launch_score_hits(UtX_d, l, ld_utx, p_max, hits_d, cap, n_hits_d, best_d, S(stream));
+}
+
+extern "C" int gemma_hip_lmm_score_panel_hits_batch_d(int kind, const void *geno, size_t l, size_t ld, double p_max,
+                                                      gemma_score_hit *hits_d, size_t cap, unsigned long long *n_hits_d,
+                                                      gemma_score_best *best_d, void *stream) {
+  NEED_INIT();
+  NEED_SCORE("lmm_score_panel_hits_batch");
+  int rc = score_hits_check("lmm_score_panel_hits_batch", l, p_max, hits_d, cap, n_hits_d);
+  if (rc) return rc;
+  hipStream_t s = S(stream);
+  if (l == 0) return score_hits_empty(n_hits_d, best_d, s);
+  if ((rc = check_batch_args("lmm_score_panel_hits_batch", kind, geno, l, ld, n_hits_d))) return rc;
+  double *UtX;
+  size_t ldx;
+  if ((rc = compute_utx(kind, geno, l, ld, -1, &UtX, &ldx, s))) return rc;
+  return launch_score_hits(UtX, l, ldx, p_max, hits_d, cap, n_hits_d, best_d, s);
+}
+
+extern "C" int gemma_hip_lmm_score_panel_hits_batch(int kind, const void *geno, size_t l, size_t ld, double p_max,
+                                                    gemma_score_hit *hits, size_t cap, unsigned long long *n_hits,
+                                                    gemma_score_best *best) {
+  NEED_INIT();
+  NEED_SCORE("lmm_score_panel_hits_batch");
+  int rc = score_hits_check("lmm_score_panel_hits_batch", l, p_max, hits, cap, n_hits);
+  if (rc) return rc;
+  const size_t n = g_ctx.cfg.n, T = g_ctx.score_T;
+  if (g_ctx.score_cnt.reserve(8) || (best && g_ctx.score_best.reserve(T * sizeof(gemma_score_best))) ||
+      (cap && g_ctx.score_hits.reserve(cap * sizeof(gemma_score_hit))))
+    return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_hits_batch: a list of %zu hits (%zu bytes)", cap, cap * sizeof(gemma_score_hit));
+  gemma_score_hit *hits_d = cap ? g_ctx.score_hits.as<gemma_score_hit>() : nullptr;
+  gemma_score_best *best_d = best ? g_ctx.score_best.as<gemma_score_best>() : nullptr;
+  if (l == 0) {
+    if ((rc = score_hits_empty(g_ctx.score_cnt.as<unsigned long long>(), best_d, nullptr))) return rc;
+  } else {
+    const size_t per_row = (kind == GEMMA_GENO_PLINK_2BIT && g_ctx.have_map) ? g_ctx.ni_total : n;
+    const size_t need = min_ld_for(kind, per_row, l);
+    if (need == (size_t)-1) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_hits_batch: unknown geno_kind %d", kind);
+    if (!geno || ld < need) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_hits_batch: ld=%zu < %zu", ld, need);
+    const size_t rows = (kind == GEMMA_GENO_F64_IDV_MAJOR) ? n : l;
+    const size_t esz = (kind == GEMMA_GENO_PLINK_2BIT) ? 1 : 8;
+    if (g_ctx.stage_in.reserve(rows * ld * esz)) return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_hits_batch: staging %zu bytes", rows * ld * esz);
+    HIPCHK(hipMemcpy2D(g_ctx.stage_in.p, ld * esz, geno, ld * esz, need * esz, rows, hipMemcpyHostToDevice));
+    rc = gemma_hip_lmm_score_panel_hits_batch_d(kind, g_ctx.stage_in.p, l, ld, p_max, hits_d, cap, g_ctx.score_cnt.as<unsigned long long>(),
+                                                best_d, nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(hipMemcpy(n_hits, g_ctx.score_cnt.p, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  const size_t kept = *n_hits < cap ? (size_t)*n_hits : cap;
+  if (kept) {
+    HIPCHK(hipMemcpy(hits, hits_d, kept * sizeof(gemma_score_hit), hipMemcpyDeviceToHost));
+    std::sort(hits, hits + kept, [](const gemma_score_hit &x, const gemma_score_hit &y) {
+      return x.pheno != y.pheno ? x.pheno < y.pheno : x.snp < y.snp;
+    });
+  }
+  if (best) HIPCHK(hipMemcpy(best, best_d, T * sizeof(gemma_score_best), hipMemcpyDeviceToHost));
   return GEMMA_HIP_OK;
 }

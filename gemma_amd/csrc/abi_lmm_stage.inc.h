@@ -26,6 +26,8 @@ static void multi_release() {
 }
 static void score_release() {
   g_ctx.score_R.release(); g_ctx.score_Pyy.release(); g_ctx.score_Yt.release(); g_ctx.score_lam.release(); g_ctx.score_bad.release();
+  g_ctx.score_fthr.release(); g_ctx.score_cells.release(); g_ctx.score_hits.release(); g_ctx.score_cnt.release(); g_ctx.score_best.release();
+  g_ctx.score_fthr_p = -1.0;
   g_ctx.score_T = 0;
 }
 // the single-phenotype entry points after a multi setup: the live slot is nobody's

@@ -246,6 +246,11 @@ struct Ctx {
   size_t score_T = 0;              // 0: no score-panel setup
   ScoreGeom score_geom;
   DevBuf score_R, score_Pyy, score_Yt, score_lam, score_bad; // weight matrix, P_yy and lambda per phenotype; U^T Y transposed (setup only)
+  // the hits form: the pre-filter's threshold on F (one double, valid for score_fthr_p of this setup), the per-wave best cells,
+  // and the host form's device-side list, counter and best
+  DevBuf score_fthr, score_cells, score_hits, score_cnt, score_best;
+  double score_fthr_p = -1.0;      // p_max the threshold was made for (-1: none)
+  hipStream_t score_fthr_s = nullptr; // ... and the stream it was made on (another stream makes its own: no order between the two)
 
   // linear model (-lm) state
   bool lm_active = false;
@@ -426,6 +431,8 @@ extern "C" void gemma_hip_shutdown(void) {
   g_ctx.multi_Yt.release(); g_ctx.multi_R.release(); g_ctx.multi_T_buf.release();
   g_ctx.multi_T = 0;
   g_ctx.score_R.release(); g_ctx.score_Pyy.release(); g_ctx.score_Yt.release(); g_ctx.score_lam.release(); g_ctx.score_bad.release();
+  g_ctx.score_fthr.release(); g_ctx.score_cells.release(); g_ctx.score_hits.release(); g_ctx.score_cnt.release(); g_ctx.score_best.release();
+  g_ctx.score_fthr_p = -1.0;
   g_ctx.score_T = 0;
   g_ctx.U_even_of = nullptr;
   pipe_release(); // pinned slots, copy stream and events of the pipelined host-block path

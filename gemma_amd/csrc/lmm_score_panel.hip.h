@@ -13,6 +13,9 @@
 // i.e. a 16-wide column block holds 16 phenotypes of ONE kind: lane (col, kq) of a wave holds, in every one of the c + 2
 // accumulator blocks of a (row group, phenotype group) pair, the same (SNP, phenotype) positions -- the epilogue is per lane.
 // Zero beyond n and beyond T.
+//
+// Two output forms of the one product: the records form (T x l records of beta, se, p_score) and the hits form (the pairs with
+// p_score <= p_max in a caller-sized list, and the best pair of every phenotype) -- see SP_PXX_FLOOR / SP_FCRIT_MARGIN below.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cfloat>
@@ -25,6 +28,19 @@ namespace gemma_hip {
 struct ScoreRec {
   double beta, se, p_score;
 };
+struct ScoreHit { // gemma_score_hit
+  unsigned int snp, pheno;
+  double beta, se, p_score;
+};
+struct ScoreBest { // gemma_score_best
+  double beta, se, p_score;
+  long long snp;
+};
+// a wave's best pair of one phenotype over its 32 rows: the largest finite F, the smallest row among equals (row -1: none)
+struct ScoreCell {
+  double F, P_xx, P_xy;
+  long long row;
+};
 
 constexpr int SP_CMAX = 16; // covariates
 constexpr int SP_KP = 4;    // kinds per K pass: SP_RG * SP_PG * SP_KP accumulator blocks of 4 doubles = 128 registers of a wave's 256
@@ -34,6 +50,32 @@ constexpr int SP_NPOS = SP_RG * SP_PG * 4; // (SNP, phenotype) pairs per lane
 // a pivot of the Cholesky factor of S_ww below this fraction of its diagonal element: not positive definite.  Two equal covariate
 // columns leave a pivot of a few ulp of either sign; statistics of a Gram matrix this close to singular would be rounding noise.
 constexpr double SP_PIVOT_MIN = 1e-12;
+
+// ---- the hits form (gemma_hip_lmm_score_panel_hits_*): pairs with p_score <= p_max and the best pair of every phenotype ----
+// Degenerate pairs.  A row that is collinear with the covariates (monomorphic: a multiple of the intercept) has a P_xx that is
+// the rounding of sum h x^2 - sum_a (sum h x w~_a)^2, 1e-16 to 1e-13 of sum h x^2 and of either sign, and statistics that are
+// noise (p_score near 1, NaN, or 0 where the difference happens to vanish).  The records form prints them as they come; a hits
+// list must not carry them to its top, so a pair with P_xx < SP_PXX_FLOOR * sum h x^2 (or a NaN there: an all-missing row) is
+// neither a hit nor a best.  1e-8 is 1 - R^2 of x on the covariates: 1e5 above the noise, and the floor under which the tests of
+// the records form leave a pair out of their comparison.  sum h x^2 is kept as a float per position (the test needs one digit).
+constexpr double SP_PXX_FLOOR = 1e-8;
+// The pre-filter.  p = Q(F; 1, df) decreases in F, so a pair can be a hit only at F >= F*(p_max).  score_fcrit_kernel brackets
+// F* by bisection on fdist_Q1_dev itself and hands out its LOWER end `lo`, with computed Q^(lo) > p_max, times 1 - SP_FCRIT_MARGIN.
+// Derivation of the margin.  Write Q^ = Q (1 + e), |e| <= eps, for the computed function.  Its rounding: on the branch
+// F < about 3 the value is 1 - I with p >= 0.08, error <= 1e-14 of p; elsewhere p = exp(ln_pre) cf / b is formed without a
+// cancellation, |ln_pre| <= 745 before p underflows, so exp carries <= 745 x a few ulp = 5e-13 and the continued fraction (it
+// stops at |delta - 1| < 2 ulp within 512 steps) <= 2e-13: eps = 1e-12.  Suppose a pair has Q^(F) <= p_max and F < lo (1 - m).
+// With s = -d ln Q / d ln F (the elasticity; s >= 0.3 for every df >= 1 once Q <= 1/2: df = 1 has 0.318 at Q = 1/2 rising to
+// 1/2, df = infinity 0.43 rising without bound), Q(F) >= Q(lo) (1 - m)^-s >= Q(lo) (1 + s m), hence
+//     Q^(F) >= Q^(lo) (1 + s m) (1 - eps) / (1 + eps) > p_max (1 + s m) (1 - 2 eps) >= p_max   once   m >= 2 eps / s = 6.7e-12,
+// a contradiction.  SP_FCRIT_MARGIN = 1e-9 is 150 times that; it lets through a further 1e-9 s p_max of the pairs, which the
+// decision on the computed p_score then rejects.  Two ends are cut off: p_max >= SP_FCRIT_PMAX = 1/2, where s falls to 0 with F
+// (no pre-filter: the threshold is -inf, every second pair would pass anyway), and p_max < SP_FCRIT_PMIN = 1e-280, where
+// p_score is close to the subnormals and eps no longer holds (the threshold of 1e-280 is used: a superset).  A NaN from the
+// function ends the bisection where it stands: `lo` only ever moves to a point with Q^ > p_max.
+constexpr double SP_FCRIT_MARGIN = 1e-9;
+constexpr double SP_FCRIT_PMAX = 0.5;
+constexpr double SP_FCRIT_PMIN = 1e-280;
 
 struct ScoreGeom {
   int n, nc; // individuals, 16-k chunks
@@ -185,14 +227,65 @@ struct ScoreArgs {
   const double *Pyy;
   ScoreRec *out; // out[t * l + s]
   double lnbeta_half_df;
+  // the hits form only
+  double p_max;
+  const double *f_thr;          // the pre-filter's threshold on F (score_fcrit_kernel)
+  ScoreHit *hits;               // cap entries
+  unsigned long long cap;
+  unsigned long long *n_hits;   // counts every hit, stored or not
+  ScoreCell *cells;             // [ceil(l / 32)][T], nullptr: no best wanted
 };
+
+// The epilogue arithmetic of CalcRLScore, shared by the records form, the hits form and score_best_kernel: the same operations
+// in the same order, so a hit and a best carry the bits of the record of their pair.
+__device__ __forceinline__ double score_F(double nd, double P_xx, double P_xy, double P_yy) {
+  return nd * P_xy * P_xy / (P_yy * P_xx);
+}
+__device__ __forceinline__ ScoreRec score_stats(double nd, double df, double lnbeta_half_df, double P_xx, double P_xy, double P_yy) {
+  ScoreRec o;
+  o.beta = P_xy / P_xx;
+  const double Px_yy = P_yy - P_xy * P_xy / P_xx;
+  const double tau = df / Px_yy;
+  o.se = safe_sqrt_dev(1.0 / (tau * P_xx));
+  o.p_score = fdist_Q1_dev(score_F(nd, P_xx, P_xy, P_yy), df, lnbeta_half_df);
+  return o;
+}
+// (F, row) of b before (F, row) of a: larger F, the smaller row among equals
+__device__ __forceinline__ bool score_better(double Fb, long long rb, double Fa, long long ra) {
+  return Fb > Fa || (Fb == Fa && rb < ra);
+}
+
+// One thread: the pre-filter's threshold of (p_max, df), see SP_FCRIT_MARGIN.
+__global__ void score_fcrit_kernel(double p_max, double df, double lnbeta_half_df, double *__restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (!(p_max < SP_FCRIT_PMAX)) {
+    *out = -INFINITY;
+    return;
+  }
+  const double pe = p_max > SP_FCRIT_PMIN ? p_max : SP_FCRIT_PMIN;
+  double lo = 0.0, hi = 1.0; // Q^(0) = 1 > pe
+  for (;;) {
+    const double q = fdist_Q1_dev(hi, df, lnbeta_half_df);
+    if (q > pe && hi < 1e300) { lo = hi; hi *= 2.0; }
+    else break;
+  }
+  for (int it = 0; it < 64; ++it) {
+    const double mid = 0.5 * (lo + hi);
+    const double q = fdist_Q1_dev(mid, df, lnbeta_half_df);
+    if (q > pe) lo = mid;
+    else if (q <= pe) hi = mid;
+    else break;
+  }
+  *out = lo * (1.0 - SP_FCRIT_MARGIN);
+}
 
 // One K pass of a wave: NK kinds (FIRST: kind 0 is h against x^2 -- the fragment squared in registers --, kind 1 h . r; the rest
 // and every kind of a later pass: h . w~_a) for SP_RG row groups x SP_PG phenotype groups.  rp[q]: the lane's operand of chunk 0,
 // phenotype group q, first kind of the pass.  pxx / pxy: the running P_xx and P_xy of the lane's positions.
-template <int NK, bool FIRST, bool AL>
+// HITS (first pass): sx takes sum h x^2 of the positions as floats (SP_PXX_FLOOR).
+template <int NK, bool FIRST, bool AL, bool HITS = false>
 __device__ __forceinline__ void score_pass(const ScoreArgs &a, const double *const (&xr)[SP_RG], const double *const (&rp)[SP_PG],
-                                           int kq, double (&pxx)[SP_NPOS], double (&pxy)[SP_NPOS]) {
+                                           int kq, double (&pxx)[SP_NPOS], double (&pxy)[SP_NPOS], float *sx = nullptr) {
   f64x4 acc[SP_RG][SP_PG][NK];
 #pragma unroll
   for (int g = 0; g < SP_RG; ++g)
@@ -266,6 +359,7 @@ __device__ __forceinline__ void score_pass(const ScoreArgs &a, const double *con
         if (FIRST) {
           pxx[e] = acc[g][q][0][r];
           pxy[e] = acc[g][q][1][r];
+          if (HITS) sx[e] = (float)acc[g][q][0][r];
         }
 #pragma unroll
         for (int k = FIRST ? 2 : 0; k < NK; ++k) pxx[e] -= acc[g][q][k][r] * acc[g][q][k][r];
@@ -275,7 +369,11 @@ __device__ __forceinline__ void score_pass(const ScoreArgs &a, const double *con
 // grid: ceil(ng / (2 SP_PG)) phenotype tiles (fastest: the workgroups that share SNP rows run together) x ceil(l / (32 SP_RG)) SNP
 // tiles, linear in blockIdx.x; 4 waves = 2 (rows) x 2 (phenotype groups).  c + 2 <= SP_KP kinds: one pass over K; more: further
 // passes of up to SP_KP kinds h . w~_a each, P_xx and P_xy kept in registers.
-template <bool AL>
+// HITS: the same K passes, then instead of the T x l records the pairs with p_score <= p_max appended to a.hits (one slot claim
+// per wave and step: ballot, one atomicAdd of the wave's count, the lanes' ranks in the ballot) and the wave's best pair of each
+// of its phenotypes written to its own cell of a.cells (no atomics: score_best_kernel reduces the cells in a fixed order).  The
+// F tail runs only where F passes the pre-filter.
+template <bool AL, bool HITS = false>
 __global__ __launch_bounds__(256, 2) void score_panel_kernel(ScoreArgs a) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -301,9 +399,10 @@ __global__ __launch_bounds__(256, 2) void score_panel_kernel(ScoreArgs a) {
     rp[q] = a.Rp + (long)grp[q] * a.g.nk * 256 + lane * 4;
   }
   double pxx[SP_NPOS], pxy[SP_NPOS];
+  float sx[SP_NPOS]; // the hits form only (never written or read by the records form)
   const int nk = a.g.nk;
-  if (nk == 3) score_pass<3, true, AL>(a, xr, rp, kq, pxx, pxy);
-  else score_pass<4, true, AL>(a, xr, rp, kq, pxx, pxy);
+  if (nk == 3) score_pass<3, true, AL, HITS>(a, xr, rp, kq, pxx, pxy, sx);
+  else score_pass<4, true, AL, HITS>(a, xr, rp, kq, pxx, pxy, sx);
   for (int k0 = SP_KP; k0 < nk; k0 += SP_KP) {
     const double *rq[SP_PG];
 #pragma unroll
@@ -316,25 +415,105 @@ __global__ __launch_bounds__(256, 2) void score_panel_kernel(ScoreArgs a) {
   }
   // CalcRLScore from (P_xx, P_xy, P_yy), one position at a time (the F tail is long: not unrolled SP_NPOS times)
   const double nd = (double)a.g.n, df = (double)(a.g.n - a.g.c - 1);
+  if (!HITS) {
 #pragma unroll 1
-  for (int e = 0; e < SP_NPOS; ++e) {
+    for (int e = 0; e < SP_NPOS; ++e) {
+      double P_xx = 0.0, P_xy = 0.0;
+#pragma unroll
+      for (int k = 0; k < SP_NPOS; ++k)
+        if (k == e) { P_xx = pxx[k]; P_xy = pxy[k]; }
+      const int g = e / (SP_PG * 4), q = (e >> 2) % SP_PG, r = e & 3;
+      const long row = s0 + g * 16 + kq + 4 * r;
+      const int t = (g0 + q) * 16 + i;
+      if (row >= a.l || t >= a.g.T) continue;
+      a.out[(long)t * a.l + row] = score_stats(nd, df, a.lnbeta_half_df, P_xx, P_xy, a.Pyy[t]);
+    }
+    return;
+  }
+  const double f_thr = *a.f_thr;
+  double bF[SP_PG], bxx[SP_PG], bxy[SP_PG];
+  long long brow[SP_PG];
+#pragma unroll
+  for (int q = 0; q < SP_PG; ++q) { bF[q] = -INFINITY; bxx[q] = 0.0; bxy[q] = 0.0; brow[q] = -1; }
+#pragma unroll 1
+  for (int e = 0; e < SP_NPOS; ++e) { // e is wave-uniform: every lane reaches the ballot
     double P_xx = 0.0, P_xy = 0.0;
+    float shx2 = 0.0f;
 #pragma unroll
     for (int k = 0; k < SP_NPOS; ++k)
-      if (k == e) { P_xx = pxx[k]; P_xy = pxy[k]; }
+      if (k == e) { P_xx = pxx[k]; P_xy = pxy[k]; shx2 = sx[k]; }
     const int g = e / (SP_PG * 4), q = (e >> 2) % SP_PG, r = e & 3;
     const long row = s0 + g * 16 + kq + 4 * r;
     const int t = (g0 + q) * 16 + i;
-    if (row >= a.l || t >= a.g.T) continue;
-    const double P_yy = a.Pyy[t];
+    const bool inside = row < a.l && t < a.g.T;
+    const double P_yy = inside ? a.Pyy[t] : NAN;
+    const double F = score_F(nd, P_xx, P_xy, P_yy);
+    const bool sound = inside && P_xx >= SP_PXX_FLOOR * (double)shx2; // false on NaN
+    if (sound && F <= DBL_MAX) { // finite (NaN compares false)
+#pragma unroll
+      for (int qq = 0; qq < SP_PG; ++qq)
+        if (qq == q && (brow[qq] < 0 || score_better(F, row, bF[qq], brow[qq]))) { bF[qq] = F; bxx[qq] = P_xx; bxy[qq] = P_xy; brow[qq] = row; }
+    }
+    bool hit = false;
     ScoreRec o;
-    o.beta = P_xy / P_xx;
-    const double Px_yy = P_yy - P_xy * P_xy / P_xx;
-    const double tau = df / Px_yy;
-    o.se = safe_sqrt_dev(1.0 / (tau * P_xx));
-    o.p_score = fdist_Q1_dev(nd * P_xy * P_xy / (P_yy * P_xx), df, a.lnbeta_half_df);
-    a.out[(long)t * a.l + row] = o;
+    if (sound && F >= f_thr) {
+      o = score_stats(nd, df, a.lnbeta_half_df, P_xx, P_xy, P_yy);
+      hit = o.p_score <= a.p_max;
+    }
+    const unsigned long long m = __ballot(hit);
+    if (m != 0) {
+      unsigned long long base = 0;
+      const int leader = __ffsll((long long)m) - 1;
+      if (lane == leader) base = atomicAdd(a.n_hits, (unsigned long long)__popcll(m));
+      base = __shfl(base, leader);
+      const unsigned long long slot = base + (unsigned long long)__popcll(m & ((1ULL << lane) - 1ULL));
+      if (hit && slot < a.cap) {
+        ScoreHit h;
+        h.snp = (unsigned int)row; h.pheno = (unsigned int)t;
+        h.beta = o.beta; h.se = o.se; h.p_score = o.p_score;
+        a.hits[slot] = h;
+      }
+    }
   }
+  if (a.cells == nullptr) return;
+  // the lanes (i, kq = 0 .. 3) hold the four row quarters of phenotype column i
+#pragma unroll
+  for (int q = 0; q < SP_PG; ++q) {
+#pragma unroll
+    for (int off = 16; off <= 32; off <<= 1) {
+      const double oF = __shfl_xor(bF[q], off), oxx = __shfl_xor(bxx[q], off), oxy = __shfl_xor(bxy[q], off);
+      const long long orow = __shfl_xor(brow[q], off);
+      if (orow >= 0 && (brow[q] < 0 || score_better(oF, orow, bF[q], brow[q]))) { bF[q] = oF; bxx[q] = oxx; bxy[q] = oxy; brow[q] = orow; }
+    }
+    const int t = (g0 + q) * 16 + i;
+    if (kq == 0 && t < a.g.T) {
+      ScoreCell c;
+      c.F = bF[q]; c.P_xx = bxx[q]; c.P_xy = bxy[q]; c.row = brow[q];
+      a.cells[(s0 / 32) * (long)a.g.T + t] = c;
+    }
+  }
+}
+
+// One thread per phenotype: the best of its cells over the row tiles in ascending order (a later tile wins only with a larger F:
+// ties stay with the smallest row), then the statistics of that one pair.  No pair: snp -1, NaN.
+__global__ __launch_bounds__(256) void score_best_kernel(ScoreGeom g, long ntile, const ScoreCell *__restrict__ cells,
+                                                        const double *__restrict__ Pyy, double lnbeta_half_df,
+                                                        ScoreBest *__restrict__ best) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= g.T) return;
+  ScoreCell b;
+  b.F = -INFINITY; b.P_xx = 0.0; b.P_xy = 0.0; b.row = -1;
+  for (long k = 0; k < ntile; ++k) {
+    const ScoreCell c = cells[k * (long)g.T + t];
+    if (c.row >= 0 && (b.row < 0 || score_better(c.F, c.row, b.F, b.row))) b = c;
+  }
+  ScoreBest o;
+  o.beta = NAN; o.se = NAN; o.p_score = NAN; o.snp = -1;
+  if (b.row >= 0) {
+    const ScoreRec r = score_stats((double)g.n, (double)(g.n - g.c - 1), lnbeta_half_df, b.P_xx, b.P_xy, Pyy[t]);
+    o.beta = r.beta; o.se = r.se; o.p_score = r.p_score; o.snp = b.row;
+  }
+  best[t] = o;
 }
 
 } // namespace gemma_hip

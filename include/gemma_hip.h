@@ -27,6 +27,7 @@
 #define GEMMA_HIP_H
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -300,6 +301,37 @@ int gemma_hip_lmm_score_panel_batch(int geno_kind, const void *geno, size_t l, s
 int gemma_hip_lmm_score_panel_batch_d(int geno_kind, const void *geno_d, size_t l, size_t ld, gemma_score_rec *out_d, void *stream);
 /* the product alone, on a caller-made U^T x (l x n SNP-major, leading dimension ld_utx >= n) */
 int gemma_hip_lmm_score_panel_assoc_d(const double *UtX_d, size_t l, size_t ld_utx, gemma_score_rec *out_d, void *stream);
+
+/* The hits form of a block: instead of the T x l records, the pairs with p_score <= p_max and the best pair of every phenotype.
+ * The product is the one of the records form and a hit's (beta, se, p_score) are the bits of the record of its pair; the F tail
+ * runs only on pairs whose F statistic passes a pre-filter at the critical value of p_max, and nothing of size T x l is stored.
+ *   hits / cap   the list and its size in entries; snp is the row inside the block.  n_hits always receives the number of
+ *                qualifying pairs of the block: where it exceeds cap the call still returns GEMMA_HIP_OK, the list holds an
+ *                unspecified cap of the hits, and the caller repeats the block with a larger list.  hits == NULL with cap == 0
+ *                counts only.  The host form returns the list sorted by (pheno, snp); the _d forms leave it in ARRIVAL ORDER
+ *                (which differs from run to run: sort it, by (pheno, snp), where the order matters).
+ *   best         NULL, or T entries: per phenotype the pair with the largest finite F of the block (the smallest p_score), the
+ *                smallest row among equal F; snp = -1 and NaN fields where the block has no such pair (and for l == 0).
+ *   p_max        in [0, 1]; anything else, NaN included: GEMMA_HIP_EINVAL.
+ * A pair whose P_xx is below 1e-8 of sum h x^2 (the row is collinear with the covariates -- monomorphic --, its statistics are
+ * rounding noise) or NaN (no called genotype) is neither a hit nor a best.  State rules and genotype handling as the records form. */
+typedef struct {
+  uint32_t snp, pheno;
+  double beta, se, p_score;
+} gemma_score_hit;
+typedef struct {
+  double beta, se, p_score;
+  int64_t snp;
+} gemma_score_best;
+int gemma_hip_lmm_score_panel_hits_batch(int geno_kind, const void *geno, size_t l, size_t ld, double p_max,
+                                         gemma_score_hit *hits, size_t cap, unsigned long long *n_hits, gemma_score_best *best);
+int gemma_hip_lmm_score_panel_hits_batch_d(int geno_kind, const void *geno_d, size_t l, size_t ld, double p_max,
+                                           gemma_score_hit *hits_d, size_t cap, unsigned long long *n_hits_d, gemma_score_best *best_d,
+                                           void *stream);
+/* the product alone, on a caller-made U^T x */
+int gemma_hip_lmm_score_panel_hits_assoc_d(const double *UtX_d, size_t l, size_t ld_utx, double p_max,
+                                           gemma_score_hit *hits_d, size_t cap, unsigned long long *n_hits_d, gemma_score_best *best_d,
+                                           void *stream);
 
 /* ---- multivariate LMM (-lmm 1..4 -n a b c ...) ------------------------------------ */
 /* MVLMM::AnalyzeBimbam / AnalyzePlink, src/mvlmm.cpp:2972-3416 / :3418-3899, and with opt->gxe the interaction test of

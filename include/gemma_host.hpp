@@ -823,6 +823,49 @@ public:
     finish();
   }
 
+  // ---- the hits form of the score panel (gemma_hip_lmm_score_panel_hits_batch): no T x p records on the host ----
+  // scoreHits: every pair with p_score <= p_max, sorted by (pheno, snp); snp counts the analysed SNPs of the whole scan (block
+  // offset + row).  scoreBest[t]: the pair of phenotype t with the smallest p_score over the scan, the smaller snp among equals,
+  // NaN never; snp -1: none.
+  std::vector<gemma_score_hit> scoreHits;
+  std::vector<gemma_score_best> scoreBest;
+
+  void AnalyzePlinkScorePanelHits(const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY, double p_max) {
+    const std::string file_bed = file_bfile + ".bed";
+    std::ifstream infile(file_bed.c_str(), std::ios::binary);
+    if (!infile) throw std::runtime_error("error reading genotype (.bed) file");
+    setup_score_hits(U, eval, UtW, UtY);
+    enforce_hip(gemma_hip_lmm_set_indicator(indicator_idv.data(), indicator_idv.size()), "AnalyzePlinkScorePanelHits");
+    const size_t n_bit = (ni_total + 3) / 4;
+    const size_t B = io_block_rows(LMM_BATCH_SIZE);
+    size_t t_next = 0;
+    const std::vector<int> keep = analysed_snps();
+    BlockPrefetch pf(B * n_bit, [&](void *slot, int) {
+      return read_bed_rows(infile, keep, t_next, n_bit, static_cast<unsigned char *>(slot), B);
+    });
+    for (;;) {
+      void *slot = nullptr;
+      const size_t l = pf.next(slot);
+      if (l == (size_t)-1) throw std::runtime_error("error reading genotype (.bed) file (truncated)");
+      if (l == 0) break;
+      batch_compute_score_hits(GEMMA_GENO_PLINK_2BIT, slot, l, n_bit, p_max);
+    }
+    finish_score_hits();
+  }
+
+  void AnalyzeFeedScorePanelHits(const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY, RowFeeder &feed,
+                                 size_t max_rows, size_t ld, double p_max) {
+    setup_score_hits(U, eval, UtW, UtY);
+    for (;;) {
+      const double *X = nullptr;
+      const size_t l = feed(X);
+      if (l == 0) break;
+      if (l > max_rows) throw HipError(GEMMA_HIP_EINVAL, "AnalyzeFeedScorePanelHits: block larger than max_rows");
+      batch_compute_score_hits(GEMMA_GENO_F64_SNP_MAJOR, X, l, ld, p_max);
+    }
+    finish_score_hits();
+  }
+
   // WriteFiles, src/lmm.cpp:101-225
   void WriteFiles() {
     const std::string file_str = path_out + "/" + file_out + ".assoc.txt";
@@ -935,6 +978,48 @@ private:
     if (l == 0) return;
     enforce_hip(gemma_hip_lmm_score_panel_batch(kind, geno, l, ld, out.data()), "batch_compute (score panel)");
     for (size_t t = 0; t < scorePanel.size(); ++t) scorePanel[t].insert(scorePanel[t].end(), out.begin() + t * l, out.begin() + (t + 1) * l);
+  }
+  std::vector<gemma_score_hit> hits_buf_;
+  std::vector<gemma_score_best> best_buf_;
+  size_t hits_done_ = 0; // analysed SNPs of the blocks so far
+  void setup_score_hits(const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY) {
+    const size_t T = setup_score_panel(U, eval, UtW, UtY);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const gemma_score_best none = {nan, nan, nan, -1};
+    scoreHits.clear();
+    scoreBest.assign(T, none);
+    best_buf_.resize(T);
+    if (hits_buf_.empty()) hits_buf_.resize(4096);
+    hits_done_ = 0;
+  }
+  void batch_compute_score_hits(int kind, const void *geno, size_t l, size_t ld, double p_max) {
+    if (l == 0) return;
+    unsigned long long nh = 0;
+    for (;;) { // a block with more hits than the list holds is run again with a list that holds them
+      enforce_hip(gemma_hip_lmm_score_panel_hits_batch(kind, geno, l, ld, p_max, hits_buf_.data(), hits_buf_.size(), &nh, best_buf_.data()),
+                  "batch_compute (score panel hits)");
+      if (nh <= hits_buf_.size()) break;
+      hits_buf_.resize((size_t)nh);
+    }
+    for (size_t k = 0; k < (size_t)nh; ++k) {
+      gemma_score_hit h = hits_buf_[k];
+      h.snp += (uint32_t)hits_done_;
+      scoreHits.push_back(h);
+    }
+    for (size_t t = 0; t < scoreBest.size(); ++t) {
+      gemma_score_best b = best_buf_[t];
+      if (b.snp < 0 || b.p_score != b.p_score) continue;
+      b.snp += (int64_t)hits_done_;
+      gemma_score_best &o = scoreBest[t];
+      if (o.snp < 0 || b.p_score < o.p_score || (b.p_score == o.p_score && b.snp < o.snp)) o = b;
+    }
+    hits_done_ += l;
+  }
+  void finish_score_hits() {
+    finish();
+    std::stable_sort(scoreHits.begin(), scoreHits.end(), [](const gemma_score_hit &x, const gemma_score_hit &y) {
+      return x.pheno != y.pheno ? x.pheno < y.pheno : x.snp < y.snp;
+    });
   }
   // batch_compute, src/lmm.cpp:1513-1564
   void batch_compute(int kind, const void *geno, size_t l, size_t ld, std::vector<gemma_sumstat> &out) {
