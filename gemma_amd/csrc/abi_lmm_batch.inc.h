@@ -199,18 +199,10 @@ static int lmm_batch_plink_chunked(const void *geno, size_t l, size_t ld, gemma_
   double *UtX = g_ctx.UtX.as<double>();
   g_ctx.last_utx_path = 1;
   I8Dims d;
-  if ((rc = i8_begin(l, &d, s))) return rc;
-  {
-    ProfScope ps(GEMMA_STAGE_INGEST, s);
-    IngestI8Args a;
-    a.src = reinterpret_cast<const unsigned char *>(geno); a.ld = (long)ld; a.l = (long)l;
-    a.idx_map = g_ctx.have_map ? g_ctx.idx_map.as<int>() : nullptr;
-    a.n = (int)d.n; a.A = g_ctx.i8_A.as<int8_t>(); a.ldk = (long)d.ldk;
-    a.mean = g_ctx.i8_mean.as<double>();
-    hipLaunchKernelGGL(ingest_i8_kernel, dim3((unsigned)((l + 3) / 4)), dim3(256), 0, s, a);
-    HIPCHK(hipGetLastError());
-  }
-  if ((rc = i8_meta_build(d, s))) return rc;
+  const bool direct = i8_plink_direct(); // the side stream's surplus kernels then read geno: it is the caller's until this call's
+                                         // work is done, and s waits for the side stream below
+  if ((rc = i8_begin(l, &d, s, true, !direct))) return rc;
+  if ((rc = i8_plink_left(geno, l, ld, d, s, direct))) return rc;
   const size_t per = round_up((l + chunks - 1) / chunks, (size_t)S2_BM);
   hipStream_t side = g_ctx.ov_stream;
   int c = 0;
@@ -296,19 +288,10 @@ extern "C" int gemma_hip_lmm_batch_pipe_d(int kind, const void *geno, size_t l, 
   // the separate combine stays here: ONE g_ctx.UtX serves both blocks in flight, and this block's product must not write it while
   // the block before is read from it on Q
   if ((rc = i8_begin(l, &d, x.P, false))) return xp_abort(rc);
-  {
-    ProfScope ps(GEMMA_STAGE_INGEST, x.P);
-    IngestI8Args a;
-    a.src = reinterpret_cast<const unsigned char *>(geno); a.ld = (long)ld; a.l = (long)l;
-    a.idx_map = g_ctx.have_map ? g_ctx.idx_map.as<int>() : nullptr;
-    a.n = (int)d.n; a.A = g_ctx.i8_A.as<int8_t>(); a.ldk = (long)d.ldk;
-    a.mean = g_ctx.i8_mean.as<double>();
-    hipLaunchKernelGGL(ingest_i8_kernel, dim3((unsigned)((l + 3) / 4)), dim3(256), 0, x.P, a);
-    if (hipGetLastError() != hipSuccess) return xp_abort(fail(GEMMA_HIP_ERUNTIME, "lmm_batch_pipe: ingest launch"));
-  }
-  if (hipEventRecord(x.ingest_done, x.P) != hipSuccess) return xp_abort(fail(GEMMA_HIP_ERUNTIME, "lmm_batch_pipe: event"));
+  // The byte matrix stays here whatever GEMMA_HIP_I8_DIRECT says: the caller may overwrite geno as soon as ingest_done has passed,
+  // long before this block's surplus kernels run on Q -- they need a copy of the missing pattern, and the bytes are one
+  if ((rc = i8_plink_left(geno, l, ld, d, x.P, false, x.ingest_done))) return xp_abort(rc);
   x.ingest_valid = true;
-  if ((rc = i8_meta_build(d, x.P))) return xp_abort(rc);
   if ((rc = i8_gemm_rows(d, 0, d.lpad, x.P))) return xp_abort(rc);
   HIPCHK(hipEventRecord(x.prod_done[slot], x.P));
   HIPCHK(hipStreamWaitEvent(x.Q, x.prod_done[slot], 0));

@@ -9,6 +9,10 @@ struct I8Dims {
   int mdrop; // 1: the 7g6m form -- plane 0 (digit 0 alone) carries the genotype product only
   int complete; // 1: sparse2_meta_kernel flags the block's missing calls (the int after the row counters) and a block without one
                 // takes the genotype product alone (Sparse2Args::anymiss): same planes, same U^T x, bit for bit
+  // GEMMA_HIP_I8_DIRECT (i8_plink_left): the block's records came straight from these 2-bit PLINK rows (plink_records_kernel) and
+  // g_ctx.i8_A holds nothing of it -- the surplus kernels read the missing pattern of their rows here.  nullptr: the byte matrix
+  const unsigned char *bed = nullptr;
+  long bed_ld = 0;
   int epi; // 1: plane 0 is launched last, in the epilogue form of the 16-row records kernel, and writes U^T x itself: i8_gemm_rows
            // must be given the destination, i8_post_rows runs no digit combine, i8_C holds planes 1 .. nplanes - 1 only
 };
@@ -19,7 +23,8 @@ static const int *i8_anymiss(const I8Dims &d) { return d.complete ? g_ctx.i8_row
 static int i8_sparse_mode() { return g_ctx.knobs.i8_sparse; }
 // allow_epi = false: the caller needs the planes and a separate combine (the two-block pipe: its product must not write the ONE
 // g_ctx.UtX while the block before it is still read from there)
-static int i8_begin(size_t l, I8Dims *d, hipStream_t s, bool allow_epi = true) {
+// with_bytes = false: the caller builds the records without the byte matrix (i8_plink_left), g_ctx.i8_A is not touched
+static int i8_begin(size_t l, I8Dims *d, hipStream_t s, bool allow_epi = true, bool with_bytes = true) {
   int rc = i8_prepare_u(s);
   if (rc) return rc;
   d->n = g_ctx.cfg.n; d->ldk = g_ctx.i8_ldk; d->npad = g_ctx.i8_npad;
@@ -34,9 +39,12 @@ static int i8_begin(size_t l, I8Dims *d, hipStream_t s, bool allow_epi = true) {
   // GEMMA_HIP_I8_EPILOGUE=0: every plane to memory and i8_combine_kernel behind the product (rounds 1-6)
   d->epi = (allow_epi && g_ctx.knobs.i8_epilogue && i8_sparse_mode() == 2 && g_ctx.knobs.i8_rows == 16 && d->nplanes >= 2) ? 1 : 0;
   const size_t c_elems = (size_t)(d->nplanes - d->epi) * d->mrows * d->npad;
-  if (g_ctx.i8_A.reserve(d->lpad * d->ldk) || g_ctx.i8_C.reserve(c_elems * 4) || g_ctx.i8_mean.reserve(l * 8))
-    return fail(GEMMA_HIP_ENOMEM, "lmm_batch: int8 product buffers (%zu bytes)", d->lpad * d->ldk + c_elems * 4);
-  if (d->lpad != l) HIPCHK(hipMemsetAsync(g_ctx.i8_A.p, 0, d->lpad * d->ldk, s)); // padding rows
+  const size_t a_bytes = with_bytes ? d->lpad * d->ldk : 0;
+  if ((with_bytes && g_ctx.i8_A.reserve(a_bytes)) || g_ctx.i8_C.reserve(c_elems * 4) || g_ctx.i8_mean.reserve(l * 8))
+    return fail(GEMMA_HIP_ENOMEM, "lmm_batch: int8 product buffers (%zu bytes)", a_bytes + c_elems * 4);
+  // the padding rows [l, lpad) only: every packing kernel writes every byte of the rows below l, K padding included (the whole
+  // matrix was zeroed here until round 8: 406 MB per 20 000 x 20 000 block for 224 rows)
+  if (with_bytes && d->lpad != l) HIPCHK(hipMemsetAsync(g_ctx.i8_A.as<int8_t>() + l * d->ldk, 0, (d->lpad - l) * d->ldk, s));
   return GEMMA_HIP_OK;
 }
 
@@ -181,7 +189,7 @@ static int i8_gemm_rows(const I8Dims &d, size_t row0, size_t rows_pad, hipStream
       g2.plane0 = 0;
       g2.UtX = UtX + row0 * ldx; g2.ldx = (long)ldx; g2.l = (long)rows; g2.n = (long)d.n;
       g2.mean = g_ctx.i8_mean.as<double>() + row0; g2.qinv = g_ctx.i8_qinv.as<double>();
-      g2.m_scale = 1.0; g2.nplanes = d.nplanes;
+      g2.m_scale = 1.0; g2.nplanes = d.nplanes; g2.epi_depth = g_ctx.knobs.i8_epi_depth;
       if (d.mdrop) {
         g2.run_if = 0;
         hipLaunchKernelGGL(i8gemm_sparse2_r16_ep_g_kernel, dim3(wgs, 1u), dim3(512), S2_R16_LDS, s, g2);
@@ -237,14 +245,19 @@ static int i8_post_rows(size_t l, const I8Dims &d, size_t row0, size_t rows, dou
   // the calls the sparse mask operand dropped (groups of four with 3-4 missing calls): rows with up to SUR_MAX of them are
   // completed inside the digit combine from a short per-row list, the rare rows with more by the fp64 fix-up pass
   int *sur_cnt = nullptr, *sur_list = nullptr;
-  const int8_t *Arow = g_ctx.i8_A.as<int8_t>() + row0 * d.ldk;
+  const SurplusBytes from_bytes{g_ctx.i8_A.as<int8_t>() + row0 * d.ldk, (long)d.ldk};
+  const SurplusPlink from_bed{d.bed ? d.bed + row0 * d.bed_ld : nullptr, d.bed_ld, (long)d.n};
   if (sparse) {
     if (g_ctx.i8_surlist.reserve(l * (SUR_MAX + 1) * sizeof(int)))
       return fail(GEMMA_HIP_ENOMEM, "lmm_batch: dropped-call lists");
     sur_cnt = g_ctx.i8_surlist.as<int>() + row0;
     sur_list = g_ctx.i8_surlist.as<int>() + l + row0 * SUR_MAX;
-    hipLaunchKernelGGL(i8_surplus_list_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, Arow, (long)d.ldk,
-                       g_ctx.i8_rowsur.as<int>() + row0, (long)rows, sur_cnt, sur_list);
+    if (d.bed)
+      hipLaunchKernelGGL(i8_surplus_list_kernel<SurplusPlink>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, from_bed,
+                         (long)d.ldk, g_ctx.i8_rowsur.as<int>() + row0, (long)rows, sur_cnt, sur_list);
+    else
+      hipLaunchKernelGGL(i8_surplus_list_kernel<SurplusBytes>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, from_bytes,
+                         (long)d.ldk, g_ctx.i8_rowsur.as<int>() + row0, (long)rows, sur_cnt, sur_list);
     HIPCHK(hipGetLastError());
   }
   if (!d.epi) {
@@ -261,9 +274,14 @@ static int i8_post_rows(size_t l, const I8Dims &d, size_t row0, size_t rows, dou
     HIPCHK(hipGetLastError());
   }
   if (sparse) {
-    hipLaunchKernelGGL(i8_surplus_fix_kernel, dim3((unsigned)rows), dim3(256), 0, s, Arow, (long)d.ldk,
-                       g_ctx.i8_rowsur.as<int>() + row0, g_ctx.i8_mean.as<double>() + row0, g_ctx.U, (long)d.n, (long)d.n,
-                       (long)rows, UtX + row0 * ldx, (long)ldx, SUR_MAX);
+    if (d.bed)
+      hipLaunchKernelGGL(i8_surplus_fix_kernel<SurplusPlink>, dim3((unsigned)rows), dim3(256), 0, s, from_bed, (long)d.ldk,
+                         g_ctx.i8_rowsur.as<int>() + row0, g_ctx.i8_mean.as<double>() + row0, g_ctx.U, (long)d.n, (long)d.n,
+                         (long)rows, UtX + row0 * ldx, (long)ldx, SUR_MAX);
+    else
+      hipLaunchKernelGGL(i8_surplus_fix_kernel<SurplusBytes>, dim3((unsigned)rows), dim3(256), 0, s, from_bytes, (long)d.ldk,
+                         g_ctx.i8_rowsur.as<int>() + row0, g_ctx.i8_mean.as<double>() + row0, g_ctx.U, (long)d.n, (long)d.n,
+                         (long)rows, UtX + row0 * ldx, (long)ldx, SUR_MAX);
     HIPCHK(hipGetLastError());
   }
   return GEMMA_HIP_OK;
@@ -277,22 +295,60 @@ static int i8_product(size_t l, const I8Dims &d, double *UtX, size_t ldx, hipStr
   return rc;
 }
 
+// GEMMA_HIP_I8_DIRECT (default 1): a PLINK block on the records kernel with every individual analysed (no indicator map) goes from
+// its 2-bit rows straight to the records (plink_records.hip.h); 0, an indicator map, GEMMA_HIP_I8_SPARSE=0/1: the byte matrix
+// (ingest_i8_kernel) and, for the sparse forms, the words built from it (i8_meta_build)
+static bool i8_plink_direct() { return g_ctx.knobs.i8_direct && i8_sparse_mode() == 2 && !g_ctx.have_map; }
+
+// The left factor of a PLINK block, ready for i8_gemm_rows, and mean_s: d comes from i8_begin(.., with_bytes = !i8_plink_direct()).
+// The direct form leaves d.bed set: geno must stay as it is until the block's i8_post_rows has run.  after_ingest: recorded on s
+// behind the last kernel that reads geno on the byte-matrix form.
+static int i8_plink_left(const void *geno, size_t l, size_t ld, I8Dims &d, hipStream_t s, bool direct,
+                         hipEvent_t after_ingest = nullptr) {
+  if (!direct) {
+    {
+      ProfScope ps(GEMMA_STAGE_INGEST, s);
+      IngestI8Args a;
+      a.src = reinterpret_cast<const unsigned char *>(geno); a.ld = (long)ld; a.l = (long)l;
+      a.idx_map = g_ctx.have_map ? g_ctx.idx_map.as<int>() : nullptr;
+      a.n = (int)d.n; a.A = g_ctx.i8_A.as<int8_t>(); a.ldk = (long)d.ldk;
+      a.mean = g_ctx.i8_mean.as<double>();
+      hipLaunchKernelGGL(ingest_i8_kernel, dim3((unsigned)((l + 3) / 4)), dim3(256), 0, s, a);
+      HIPCHK(hipGetLastError());
+    }
+    if (after_ingest) HIPCHK(hipEventRecord(after_ingest, s));
+    return i8_meta_build(d, s);
+  }
+  if (after_ingest || i8_sparse_mode() != 2 || g_ctx.have_map)
+    return fail(GEMMA_HIP_ESTATE, "lmm_batch: records straight from the 2-bit rows on a path that needs the byte matrix");
+  ProfScope ps(GEMMA_STAGE_INGEST, s);
+  const size_t nk = d.ldk / I8_BK;
+  if (g_ctx.i8_meta.reserve(d.lpad * nk * 4 * sizeof(uint4)) || g_ctx.i8_rowsur.reserve((d.lpad + 1) * sizeof(int)))
+    return fail(GEMMA_HIP_ENOMEM, "lmm_batch: records of the sparse product");
+  // the block's any-missing flag; the kernel writes every row counter itself
+  HIPCHK(hipMemsetAsync(g_ctx.i8_rowsur.as<int>() + d.lpad, 0, sizeof(int), s));
+  PlinkRecordsArgs a;
+  a.src = reinterpret_cast<const unsigned char *>(geno); a.ld = (long)ld; a.l = (long)l; a.lpad = (long)d.lpad;
+  a.n = (int)d.n; a.ldk = (long)d.ldk;
+  a.AM = g_ctx.i8_meta.as<uint4>(); a.row_surplus = g_ctx.i8_rowsur.as<int>();
+  a.anymiss = const_cast<int *>(i8_anymiss(d)); a.mean = g_ctx.i8_mean.as<double>();
+  hipLaunchKernelGGL(plink_records_kernel, dim3((unsigned)(d.lpad / 4)), dim3(256), 0, s, a);
+  HIPCHK(hipGetLastError());
+  g_ctx.i8_flag_at = d.complete ? (long)d.lpad : -1;
+  g_ctx.i8_rowsur_n = (long)d.lpad;
+  d.bed = a.src; d.bed_ld = (long)ld;
+  return GEMMA_HIP_OK;
+}
+
 // PLINK 2-bit batch
 static int utx_plink_i8(const void *geno, size_t l, size_t ld, double *UtX, size_t ldx, hipStream_t s) {
   I8Dims d;
-  int rc = i8_begin(l, &d, s);
-  if (rc) return rc;
-  {
-    ProfScope ps(GEMMA_STAGE_INGEST, s);
-    IngestI8Args a;
-    a.src = reinterpret_cast<const unsigned char *>(geno); a.ld = (long)ld; a.l = (long)l;
-    a.idx_map = g_ctx.have_map ? g_ctx.idx_map.as<int>() : nullptr;
-    a.n = (int)d.n; a.A = g_ctx.i8_A.as<int8_t>(); a.ldk = (long)d.ldk;
-    a.mean = g_ctx.i8_mean.as<double>();
-    hipLaunchKernelGGL(ingest_i8_kernel, dim3((unsigned)((l + 3) / 4)), dim3(256), 0, s, a);
-    HIPCHK(hipGetLastError());
-  }
-  return i8_product(l, d, UtX, ldx, s);
+  const bool direct = i8_plink_direct();
+  int rc = i8_begin(l, &d, s, true, !direct);
+  if (!rc) rc = i8_plink_left(geno, l, ld, d, s, direct);
+  if (!rc) rc = i8_gemm_rows(d, 0, d.lpad, s, UtX, ldx, l);
+  if (!rc) rc = i8_post_rows(l, d, 0, l, UtX, ldx, s);
+  return rc;
 }
 
 // Fixed-point dosage rows (i8gemm.hip.h: pack_dosage_kernel): byte planes a0 [, a1] [, mask] x the digits of U on the dense int8

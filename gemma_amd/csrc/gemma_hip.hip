@@ -28,6 +28,7 @@
 #include "i8gemm_sparse.hip.h"
 #include "i8gemm_sparse2.hip.h"
 #include "i8gemm_sparse2_r16.hip.h"
+#include "plink_records.hip.h"
 #include "i8gemm_dense16.hip.h"
 #include "qc.hip.h"
 #include "mvlmm.hip.h"
@@ -60,6 +61,8 @@ struct Knobs {
   int i8_mdrop = 0;        // GEMMA_HIP_I8_FORM=7g6m: seven digits for the genotype product, the mask product on the upper six
   int i8_complete = 1;     // GEMMA_HIP_I8_COMPLETE: 0 = blocks without a missing call take the mask product like any other block
   int i8_epilogue = 1;     // GEMMA_HIP_I8_EPILOGUE: 0 = every digit plane to memory and the digit combine as a pass of its own
+  int i8_epi_depth = 4;    // GEMMA_HIP_I8_EPI_DEPTH: 1 = the epilogue of the records kernel reads the planes back one step ahead (round 7)
+  int i8_direct = 1;       // GEMMA_HIP_I8_DIRECT: 0 = PLINK blocks reach the records through the byte matrix (ingest_i8_kernel + sparse2_meta_kernel)
   int dosage_i8 = 1;       // GEMMA_HIP_UTX_DOSAGE_I8
   int dosage_rows = 16;    // GEMMA_HIP_DOSAGE_ROWS: 32 = the dosage planes on the 32-row dense kernel (rounds 3-4)
   int overlap = 0;         // GEMMA_HIP_OVERLAP
@@ -97,6 +100,9 @@ struct Knobs {
     i8_complete = (ecp && ecp[0] == '0') ? 0 : 1;
     const char *eep = getenv("GEMMA_HIP_I8_EPILOGUE");
     i8_epilogue = (eep && eep[0] == '0') ? 0 : 1;
+    i8_epi_depth = geti("GEMMA_HIP_I8_EPI_DEPTH", 4) <= 1 ? 1 : 4;
+    const char *edr = getenv("GEMMA_HIP_I8_DIRECT");
+    i8_direct = (edr && edr[0] == '0') ? 0 : 1;
     const char *ed = getenv("GEMMA_HIP_UTX_DOSAGE_I8");
     dosage_i8 = (ed && ed[0] == '0') ? 0 : 1;
     dosage_rows = geti("GEMMA_HIP_DOSAGE_ROWS", 16) == 32 ? 32 : 16;

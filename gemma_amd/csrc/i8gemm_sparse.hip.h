@@ -77,11 +77,37 @@ static inline int sparse_meta_build(const int8_t *A, long lpad, long ldk, Sparse
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
+// Where the surplus kernels read a row's missing pattern: bit q of pat(s, gq) = call q of group gq (individuals 4 gq .. 4 gq + 3)
+// of row s is missing.  SurplusBytes: the packed byte matrix (byte = g | m << 4).  SurplusPlink: the 2-bit PLINK rows themselves
+// (code 1 = missing; calls n .. are none), for blocks whose records came from plink_records_kernel and have no byte matrix.
+struct SurplusBytes {
+  const int8_t *A;
+  long ldk;
+  __device__ __forceinline__ unsigned pat(long s, long gq) const {
+    const unsigned word = *reinterpret_cast<const unsigned *>(A + s * ldk + 4 * gq);
+    const unsigned m = (word >> 4) & 0x01010101u;
+    return (m | (m >> 7) | (m >> 14) | (m >> 21)) & 0xFu;
+  }
+};
+struct SurplusPlink {
+  const unsigned char *src;
+  long ld, n;
+  __device__ __forceinline__ unsigned pat(long s, long gq) const {
+    const long left = n - 4 * gq;
+    if (left <= 0) return 0u;
+    const unsigned b = src[s * ld + gq];
+    const unsigned m = b & ~(b >> 1) & 0x55u; // code 01 at bits 2 q
+    const unsigned p = (m & 1u) | ((m >> 1) & 2u) | ((m >> 2) & 4u) | ((m >> 3) & 8u);
+    return left >= 4 ? p : p & ((1u << left) - 1u);
+  }
+};
+
 // Rows whose sparse mask operand dropped calls (row_surplus > 0: a group of four with three or four missing calls keeps its
 // first two): UtX[s][k] += mean_s * sum over the dropped individuals i of U[i][k], in fp64, after the digits were combined.
 // Deterministic: the dropped individuals of 256 groups at a time are listed in group order by one thread, every thread k adds
 // them in that order.  ~2 % of the rows at 1 % missingness, one or two individuals each.
-__global__ __launch_bounds__(256) void i8_surplus_fix_kernel(const int8_t *__restrict__ A, long ldk,
+template <class Src>
+__global__ __launch_bounds__(256) void i8_surplus_fix_kernel(Src src, long ldk,
                                                              const int *__restrict__ row_surplus,
                                                              const double *__restrict__ mean, const double *__restrict__ U,
                                                              long ldu, long n, long l, double *__restrict__ UtX, long ldx,
@@ -96,9 +122,7 @@ __global__ __launch_bounds__(256) void i8_surplus_fix_kernel(const int8_t *__res
     const long gq = g0 + t;
     int f0 = -1, f1 = -1;
     if (gq < ngroups) {
-      const unsigned word = *reinterpret_cast<const unsigned *>(A + s * ldk + 4 * gq);
-      const unsigned m = (word >> 4) & 0x01010101u;
-      unsigned pat = (m | (m >> 7) | (m >> 14) | (m >> 21)) & 0xFu;
+      unsigned pat = src.pat(s, gq);
       if (__popc(pat) > 2) {
         pat &= pat - 1; // drop the first two (kept by the sparse operand)
         pat &= pat - 1;
@@ -135,7 +159,8 @@ __global__ __launch_bounds__(256) void i8_surplus_fix_kernel(const int8_t *__res
 // sur_list[row][..] (group order: deterministic), the count to sur_cnt[row]; a row with more (a SNP missing for most
 // individuals) keeps cnt = -1 and is left to i8_surplus_fix_kernel.
 static_assert(SUR_MAX >= 2, "SUR_MAX (i8gemm.hip.h) is the list stride of this kernel, of i8_combine_kernel and of the host's buffers");
-__global__ __launch_bounds__(256) void i8_surplus_list_kernel(const int8_t *__restrict__ A, long ldk, const int *__restrict__ row_surplus,
+template <class Src>
+__global__ __launch_bounds__(256) void i8_surplus_list_kernel(Src src, long ldk, const int *__restrict__ row_surplus,
                                                              long l, int *__restrict__ sur_cnt, int *__restrict__ sur_list) {
   const int lane = threadIdx.x & 63;
   const long s = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -151,9 +176,7 @@ __global__ __launch_bounds__(256) void i8_surplus_list_kernel(const int8_t *__re
     const long gq = g0 + lane;
     int f0 = -1, f1 = -1;
     if (gq < ngroups) {
-      const unsigned word = *reinterpret_cast<const unsigned *>(A + s * ldk + 4 * gq);
-      const unsigned m = (word >> 4) & 0x01010101u;
-      unsigned pat = (m | (m >> 7) | (m >> 14) | (m >> 21)) & 0xFu;
+      unsigned pat = src.pat(s, gq);
       if (__popc(pat) > 2) {
         pat &= pat - 1;
         pat &= pat - 1;

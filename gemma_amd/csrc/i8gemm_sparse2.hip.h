@@ -62,6 +62,7 @@ struct Sparse2Args {
   const double *mean = nullptr, *qinv = nullptr;
   double m_scale = 1.0;
   int nplanes = 0;
+  int epi_depth = 1; // GEMMA_HIP_I8_EPI_DEPTH: > 1 = the fused forms (nplanes 3, 4) read the planes back four steps ahead, 1 = one step
 };
 // Tried in round 4 and dropped: one digit fewer for the MASK product (the mask product sums only the row's missing calls, so
 // five digits keep its worst-case error at the level of the six-digit genotype product: -1/18 of the matrix instructions).  The

@@ -23,6 +23,7 @@
 // Per K-tile and wavefront: 4 record reads + 16 digit reads (ds_read_b128), 32 dense + 16 sparse instructions, 4 LDS-DMA pieces, one
 // counted s_waitcnt vmcnt(8) + one s_barrier; tests/test_isa_schedule.py holds the built loop to that.
 #pragma once
+#include <type_traits>
 #include "i8gemm_sparse2.hip.h"
 
 #ifndef S2_R16_PREP_SPREAD
@@ -47,6 +48,7 @@
 namespace gemma_hip {
 
 constexpr int S2_R16_LDS = S2_R16_NST * S2_STAGE; // dynamic LDS of a launch
+static_assert(S2_R16_LDS >= 16 * 512 * 16, "the epilogue parks 16 x 16 bytes per lane of the mask accumulators in the launch's LDS");
 
 // WITH_S = false: the genotype product alone (round 6, the "7g6m" form: the lowest of seven digits is multiplied with the genotypes
 // only -- its mask term is below the rounding of the other six): no sparse instruction, no mask accumulators, no M rows
@@ -308,9 +310,10 @@ __device__ __forceinline__ void s2_r16_body(const Sparse2Args &g) {
   asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
   if constexpr (COMBINE) {
     // Entry (i, sb, r) of this lane: row tm * 256 + wave * 32 + 16 i + 4 q + r, column tn * 128 + 16 sb + r16.  A batch is the 8
-    // entries (i, sb = 2 h, 2 h + 1, r); per batch and plane 8 G + 8 M dwords are requested one step ahead of the Horner step that
-    // uses them, so 16 - 32 loads per wavefront are in flight (beside the 128 accumulators there is no room for more: 16 entries a
-    // batch spill).  Every load is issued behind the last K-tile: the counted waits of the loop never see one.
+    // entries (i, sb = 2 h, 2 h + 1, r); per batch and plane 8 G + 8 M dwords are requested ahead of the Horner step that uses them:
+    // four steps ahead in the bodies for three and four planes (ep_fixed), one step in the generic body (16 - 32 loads per
+    // wavefront in flight; 16 entries a batch spill).  Every load is issued behind the last K-tile: the counted waits of the loop
+    // never see one.
     const int np = g.nplanes;
     const bool load_m = !(g.anymiss && __builtin_amdgcn_readfirstlane(*g.anymiss) == 0); // complete block: no M row was written
     const double w_hi = g.fuse ? 65536.0 : 256.0;          // planes above plane 0 sit two digits apart when fused
@@ -329,6 +332,125 @@ __device__ __forceinline__ void s2_r16_body(const Sparse2Args &g) {
       DM[4 * k_ + r_] = load_m ? EP_AT(const int, cp_ + (g.m_row0 + r_) * g.ldc + 16 * k_, lo_c) : 0;             \
     }                                                                                                             \
   } while (0)
+    // The fused forms (three planes: six digits, the headline shape; four: seven digits) with the plane read-back EP_DEPTH steps
+    // ahead (round 8, Sparse2Args::epi_depth).  A workgroup's 16 (np = 3) dependent round trips of ~1.6 us were the whole 26 us of
+    // this epilogue; the 768 KiB they move take 5 us.  Room for 64 dwords in flight: the mask accumulators -- 64 registers x 512
+    // lanes x 4 B = the 128 KiB of LDS, which hold nothing behind the K loop -- are parked in a lane-private LDS slot (slot j of
+    // lane t at (512 j + t) * 16: consecutive lanes 16 bytes apart, conflict-free 16-byte accesses) and read back batch by batch.
+    // The Horner steps, the last step and their order are the ones of the generic body below: only when the loads are issued differs.
+    constexpr int EP_DEPTH = 4;
+    if constexpr (WITH_S) {
+      // every wavefront is behind its last read of the K loop's stages (their last reads sit before the loop's last barrier; this
+      // one costs nothing and does not depend on that).  The generic body reads its mask accumulators from there as well: with
+      // them in registers it had five registers to spare, and a second body in the kernel made it spill.
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < 16; ++j) *reinterpret_cast<i32x4 *>(i8lds + ((j * 512 + t) << 4)) = accm[j >> 3][j & 7];
+      GEMMA_SB();
+    }
+    // LM: the planes have M rows (load_m) -- a template parameter here: a run-time choice per load is a branch and a full wait per load
+    // Addresses: per step two uniform bases (G rows, M rows) that the compiler must keep in scalar registers -- through
+    // readfirstlane, or it folds them into per-load 64-bit vector addresses: 66 registers -- plus one of four 32-bit lane offsets
+    // (row r of the lane's four; 3 ldc ints + the lane's own stay far below 2^32 bytes: fused planes mean n < 32 640)
+    // (the integer round trip drops the address space: named again, or the loads become FLAT ones that count on lgkmcnt as well)
+    typedef const __attribute__((address_space(1))) int *ep_gint_t;
+    typedef const __attribute__((address_space(1))) char *ep_gchar_t;
+#define EP_UNI(PTR)                                                                                               \
+  ((ep_gint_t)(((unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned long)(PTR) >> 32)) << 32) | \
+               (unsigned long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned long)(PTR))))
+#define EP_ATG(BASE, LO) (*(ep_gint_t)((ep_gchar_t)(BASE) + (LO)))
+#define EP_LOADF(DG, DM, I, H, P)                                                                                 \
+  do {                                                                                                            \
+    const int *cp_ = g.C + (long)(P) * g.strideC + (row_w + 16 * (I)) * g.ldc + col_w + 32 * (H);                 \
+    const ep_gint_t cg_ = EP_UNI(cp_), cm_ = EP_UNI(cp_ + g.m_row0 * g.ldc);                                      \
+    _Pragma("unroll") for (int k_ = 0; k_ < 2; ++k_) _Pragma("unroll") for (int r_ = 0; r_ < 4; ++r_) {           \
+      DG[4 * k_ + r_] = EP_ATG(cg_ + 16 * k_, lo_r[r_]);                                                          \
+      if constexpr (LM) DM[4 * k_ + r_] = EP_ATG(cm_ + 16 * k_, lo_r[r_]);                                        \
+      else DM[4 * k_ + r_] = 0;                                                                                   \
+    }                                                                                                             \
+  } while (0)
+    auto ep_fixed = [&](auto np_tag, auto lm_tag) {
+      constexpr int NP = decltype(np_tag)::value, SPB = NP - 1, NS = 8 * SPB; // plane steps per batch, steps
+      constexpr bool LM = decltype(lm_tag)::value;
+      // the lane's own offsets once more, from laundered lane coordinates: as common subexpressions of this body and the generic
+      // one the compiler computes them in front of the branch and keeps them across the generic body, which has no register to spare
+      int qf = q, cf = r16;
+      asm volatile("" : "+v"(qf), "+v"(cf));
+      const long row_lf = row_w + 4 * qf, col_lf = col_w + cf;
+      // rows / columns of the block from the lane's first on (<= 0: none), as ints: the bounds checks of the 64 entries compare
+      // constants with these two registers instead of keeping sixteen 64-bit indices
+      const int rows_left = (int)min(g.l - row_lf, 64L), cols_left = (int)min(g.n - col_lf, 256L);
+      const unsigned lo_xf = (unsigned)((4 * qf * g.ldx + cf) * 8);
+      unsigned lo_r[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) lo_r[r] = (unsigned)(((4 * qf + r) * g.ldc + cf) * 4);
+      // mean_s of the lane's 8 rows and 1 / q_j of its 8 columns first: a load in a batch's last step would be the youngest of
+      // everything in flight, and waiting for it is waiting for all the planes requested ahead
+      double msv[2][4], qv[8];
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          msv[i][r] = g.mean[row_lf + min(16 * i + r, rows_left - 1)]; // clamped (to l - 1, n - 1), not guarded: sixteen loads back
+#pragma unroll                                                           // to back, one wait; what is outside is never stored
+      for (int sb = 0; sb < 8; ++sb) qv[sb] = g.qinv[col_lf + min(16 * sb, cols_left - 1)];
+      // The body is straight-line code: without the scheduling barriers the compiler moves the loads of later steps up as far as
+      // their addresses allow and spills what they hold (555 scratch accesses in the first build).  The order is the source order.
+      GEMMA_SB();
+      int lg[EP_DEPTH][8], lm[EP_DEPTH][8]; // step s = SPB b + j (batch b, plane NP - 1 - j) lands in slot s % EP_DEPTH
+#pragma unroll
+      for (int s = 0; s < EP_DEPTH; ++s) {
+        EP_LOADF(lg[s], lm[s], (s / SPB) >> 2, (s / SPB) & 3, NP - 1 - s % SPB);
+        GEMMA_SB();
+      }
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+        const int i = b >> 2, h = b & 3;
+        double tg[8], tk[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) tg[e] = tk[e] = 0.0;
+#pragma unroll
+        for (int j = 0; j < SPB; ++j) {
+          const int s = SPB * b + j, sl = s % EP_DEPTH, s2 = s + EP_DEPTH;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            tg[e] = tg[e] * w_hi + (double)lg[sl][e];
+            tk[e] = tk[e] * w_hi + (double)lm[sl][e];
+          }
+          GEMMA_SB();
+          if (s2 < NS) EP_LOADF(lg[sl], lm[sl], (s2 / SPB) >> 2, (s2 / SPB) & 3, NP - 1 - s2 % SPB);
+          GEMMA_SB();
+        }
+        i32x4 mk[2] = {(i32x4){0, 0, 0, 0}, (i32x4){0, 0, 0, 0}};
+        if constexpr (WITH_S) {
+#pragma unroll
+          for (int k = 0; k < 2; ++k) mk[k] = *reinterpret_cast<const i32x4 *>(i8lds + (((8 * i + 2 * h + k) * 512 + t) << 4));
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const bool row_in = 16 * i + r < rows_left;
+          const double ms = msv[i][r] * g.m_scale;
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            const int e = 4 * k + r, sb = 2 * h + k;
+            tg[e] = tg[e] * w0 + (double)accg[i][sb][r];
+            tk[e] = tk[e] * w0 + (double)mk[k][r];
+            if (row_in && 16 * sb < cols_left)
+              EP_AT(double, g.UtX + (row_w + 16 * i + r) * g.ldx + col_w + 16 * sb, lo_xf) =
+                  fma(ms, tk[e], tg[e]) * qv[sb];
+          }
+        }
+        GEMMA_SB();
+      }
+    };
+    if (g.epi_depth > 1 && np == 3) {
+      if (load_m) ep_fixed(std::integral_constant<int, 3>(), std::true_type());
+      else ep_fixed(std::integral_constant<int, 3>(), std::false_type());
+    } else if (g.epi_depth > 1 && np == 4) {
+      if (load_m) ep_fixed(std::integral_constant<int, 4>(), std::true_type());
+      else ep_fixed(std::integral_constant<int, 4>(), std::false_type());
+    } else {
+    // every other plane count (unfused planes, n = 50 000) and GEMMA_HIP_I8_EPI_DEPTH=1: the schedule of round 7, one step ahead
     int cg[8], cm[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) cg[e] = cm[e] = 0;
@@ -353,6 +475,11 @@ __device__ __forceinline__ void s2_r16_body(const Sparse2Args &g) {
           cm[e] = nm[e];
         }
       }
+      i32x4 mk[2] = {(i32x4){0, 0, 0, 0}, (i32x4){0, 0, 0, 0}};
+      if constexpr (WITH_S) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) mk[k] = *reinterpret_cast<const i32x4 *>(i8lds + (((8 * i + 2 * h + k) * 512 + t) << 4));
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const bool row_in = row_l + 16 * i + r < g.l;
@@ -360,7 +487,7 @@ __device__ __forceinline__ void s2_r16_body(const Sparse2Args &g) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           const int e = 4 * k + r, sb = 2 * h + k;
-          const int m0 = WITH_S ? accm[i][sb][r] : 0;
+          const int m0 = mk[k][r];
           tg[e] = tg[e] * w0 + (double)accg[i][sb][r];
           tk[e] = tk[e] * w0 + (double)m0;
           if (row_in && col_l + 16 * sb < g.n)
@@ -369,8 +496,12 @@ __device__ __forceinline__ void s2_r16_body(const Sparse2Args &g) {
         }
       }
     }
+    }
 #undef EP_AT
 #undef EP_LOAD
+#undef EP_LOADF
+#undef EP_UNI
+#undef EP_ATG
   } else {
     int *Cg = g.C + (long)plane * g.strideC;
 #pragma unroll
