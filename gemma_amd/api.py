@@ -48,6 +48,12 @@ def _ld(a):
     return a.shape[1] if a.ndim == 2 and a.shape[0] <= 1 else (a.strides[0] // 8 if a.ndim == 2 else a.shape[0])
 
 
+def _row_ld(a):
+    """Row stride of a 2-D genotype block in items.  numpy is free to report any stride for an axis of length 1, so a block of
+    one SNP takes its width (with one row every stride >= the width is the same layout)."""
+    return a.shape[1] if a.shape[0] <= 1 else a.strides[0] // a.itemsize
+
+
 def _ptr(a):
     return C.c_void_p(a.ctypes.data)
 
@@ -226,7 +232,7 @@ def kin_add(geno, geno_kind, l=None, ld=None):
             l = geno.shape[1] if l is None else l
         else:
             l = geno.shape[0] if l is None else l
-        ld = (geno.strides[0] // geno.itemsize) if ld is None else ld
+        ld = _row_ld(geno) if ld is None else ld
         rc = L.lib().gemma_hip_kin_add(geno_kind, _ptr(geno), l, ld)
     L.check(rc, "kin_add")
 
@@ -316,7 +322,7 @@ def SnpQC(geno, geno_kind, indicator_idv, W, maf_level=0.01, miss_level=0.05, hw
     out_i = np.zeros(l, dtype=np.int32)
     out_maf = np.zeros(l)
     out_nm = np.zeros(l, dtype=np.uint64)
-    L.check(L.lib().gemma_hip_snp_qc(geno_kind, _ptr(geno), l, geno.strides[0] // geno.itemsize,
+    L.check(L.lib().gemma_hip_snp_qc(geno_kind, _ptr(geno), l, _row_ld(geno),
                                      _ptr(ind) if ind is not None else None, ni_total, _ptr(W), n, c, C.byref(cfg),
                                      _ptr(out_i), _ptr(out_maf), _ptr(out_nm)), "SnpQC")
     return out_i, out_maf, out_nm.astype(np.int64)
@@ -473,7 +479,7 @@ class LMM:
             l = geno.shape[1] if l is None else l
         else:
             l = geno.shape[0] if l is None else l
-        ld = (geno.strides[0] // geno.itemsize) if ld is None else ld
+        ld = _row_ld(geno) if ld is None else ld
         if out is None:
             out = np.zeros(l, dtype=SUMSTAT_DTYPE)
         L.check(L.lib().gemma_hip_lmm_batch(geno_kind, _ptr(geno), l, ld, _ptr(out)), "LMM.batch")
@@ -589,7 +595,7 @@ class LMM:
             l = geno.shape[1] if l is None else l
         else:
             l = geno.shape[0] if l is None else l
-        ld = (geno.strides[0] // geno.itemsize) if ld is None else ld
+        ld = _row_ld(geno) if ld is None else ld
         if out is None:
             out = np.zeros((T, l), dtype=SUMSTAT_DTYPE)
         L.check(L.lib().gemma_hip_lmm_multi_batch(geno_kind, _ptr(geno), l, ld, _ptr(out)), "LMM.batch_multi")
@@ -665,7 +671,7 @@ class LMM:
             l = geno.shape[1] if l is None else l
         else:
             l = geno.shape[0] if l is None else l
-        ld = (geno.strides[0] // geno.itemsize) if ld is None else ld
+        ld = _row_ld(geno) if ld is None else ld
         if out is None:
             out = np.zeros((T, l), dtype=SCORE_DTYPE)
         L.check(L.lib().gemma_hip_lmm_score_panel_batch(geno_kind, _ptr(geno), l, ld, _ptr(out)), "LMM.batch_score_panel")
@@ -755,7 +761,7 @@ class LMM:
             return self._hits_dev(lambda raw, cap_, cnt, best: L.lib().gemma_hip_lmm_score_panel_hits_batch_d(
                 geno_kind, gp, l, ld, p_max, raw, cap_, cnt, best, st), l, p_max, cap, geno.device)
         l = geno.shape[1] if geno_kind == L.GENO_F64_IDV_MAJOR else geno.shape[0]
-        ld = geno.strides[0] // geno.itemsize
+        ld = _row_ld(geno)
         cap = self._hits_cap(l, p_max, cap)
         best = np.zeros(T, dtype=SCORE_BEST_DTYPE)
         cnt = C.c_ulonglong(0)
@@ -926,7 +932,7 @@ class LM:
             for s0 in range(0, geno.shape[0], batch):
                 blk = geno[s0:s0 + batch]
                 out = np.zeros(blk.shape[0], dtype=SUMSTAT_DTYPE)
-                L.check(L.lib().gemma_hip_lm_batch(geno_kind, _ptr(blk), blk.shape[0], blk.strides[0] // blk.itemsize,
+                L.check(L.lib().gemma_hip_lm_batch(geno_kind, _ptr(blk), blk.shape[0], _row_ld(blk),
                                                    _ptr(out)), "LM.batch")
                 outs.append(out)
             self.sumStat = np.concatenate(outs) if outs else np.zeros(0, dtype=SUMSTAT_DTYPE)
@@ -1191,7 +1197,7 @@ def ridge_batch(geno, geno_kind, out=None):
     geno = np.ascontiguousarray(geno)
     if out is None:
         out = np.zeros(l)
-    L.check(L.lib().gemma_hip_ridge_batch(geno_kind, _ptr(geno), l, geno.strides[0] // geno.itemsize if l else 0, _ptr(out)),
+    L.check(L.lib().gemma_hip_ridge_batch(geno_kind, _ptr(geno), l, _row_ld(geno) if l else 0, _ptr(out)),
             "ridge_batch")
     return out
 
@@ -1352,7 +1358,7 @@ class PRDT:
             blk = rows[s0:s0 + batch]
             w = np.ascontiguousarray(eff[s0:s0 + batch])
             used = np.zeros(blk.shape[0], dtype=np.int32)
-            L.check(L.lib().gemma_hip_prdt_add(geno_kind, _ptr(blk), blk.shape[0], blk.strides[0] // blk.itemsize, _ptr(w),
+            L.check(L.lib().gemma_hip_prdt_add(geno_kind, _ptr(blk), blk.shape[0], _row_ld(blk), _ptr(w),
                                                _ptr(used)), "PRDT.Analyze")
             self.ns_test += int(used.sum())
             self.ignored += [rs[sel[s0 + i]] for i in np.flatnonzero(used == 0)]
@@ -1528,7 +1534,7 @@ class MQS:
         for s0 in range(0, l, batch):
             blk, cb = geno[s0:s0 + batch], cat[s0:s0 + batch]
             wb = None if weight is None else weight[s0:s0 + batch]
-            L.check(lib.gemma_hip_mqs_add(geno_kind, _ptr(blk), blk.shape[0], blk.strides[0] // blk.itemsize, _ptr(cb),
+            L.check(lib.gemma_hip_mqs_add(geno_kind, _ptr(blk), blk.shape[0], _row_ld(blk), _ptr(cb),
                                           None if wb is None else _ptr(wb)), "MQS.add")
 
     def AnalyzePlink(self, bed_rows, cat, weight=None, slot=0, batch=K_BATCH_SIZE):
@@ -1624,7 +1630,7 @@ class CI:
                                                C.c_void_p(cat_t[s0:s0 + batch].data_ptr()), C.c_void_p(z_t[s0:s0 + batch].data_ptr()), wp,
                                                C.byref(skipped), _stream()), "CI.xwz")
             else:
-                L.check(lib.gemma_hip_ci_xwz(geno_kind, _ptr(blk), blk.shape[0], blk.strides[0] // blk.itemsize, _ptr(cat[s0:s0 + batch]),
+                L.check(lib.gemma_hip_ci_xwz(geno_kind, _ptr(blk), blk.shape[0], _row_ld(blk), _ptr(cat[s0:s0 + batch]),
                                              _ptr(z[s0:s0 + batch]), None if w is None else _ptr(w[s0:s0 + batch]), C.byref(skipped)),
                         "CI.xwz")
             n_skipped += skipped.value
@@ -1635,7 +1641,7 @@ class CI:
                 L.check(lib.gemma_hip_ci_xtxwz_d(geno_kind, C.c_void_p(blk.data_ptr()), blk.shape[0], _tld(geno),
                                                  C.c_void_p(ob.data_ptr()), _stream()), "CI.xtxwz")
             else:
-                L.check(lib.gemma_hip_ci_xtxwz(geno_kind, _ptr(blk), blk.shape[0], blk.strides[0] // blk.itemsize, _ptr(ob)), "CI.xtxwz")
+                L.check(lib.gemma_hip_ci_xtxwz(geno_kind, _ptr(blk), blk.shape[0], _row_ld(blk), _ptr(ob)), "CI.xtxwz")
         if dev:
             import torch
             torch.cuda.synchronize()
@@ -1750,7 +1756,7 @@ class VARCOV:
                                                   C.c_void_p(nb_t[s0:s1].data_ptr()), C.c_void_p(var[s0:s1].data_ptr()),
                                                   C.c_void_p(cor[int(off[s0]):].data_ptr()), _stream()), "VARCOV.block")
             else:
-                L.check(lib.gemma_hip_cor_block(geno_kind, _ptr(blk), l_in, blk.strides[0] // blk.itemsize, s1 - s0, _ptr(nb[s0:s1]),
+                L.check(lib.gemma_hip_cor_block(geno_kind, _ptr(blk), l_in, _row_ld(blk), s1 - s0, _ptr(nb[s0:s1]),
                                                 _ptr(var[s0:s1]), _ptr(cor[int(off[s0]):])), "VARCOV.block")
         if dev:
             import torch
