@@ -40,6 +40,7 @@ SYMBOLS = [
     "gemma_hip_lmm_score_panel_setup", "gemma_hip_lmm_score_panel_setup_d", "gemma_hip_lmm_score_panel_setup_kept",
     "gemma_hip_lmm_score_panel_batch", "gemma_hip_lmm_score_panel_batch_d", "gemma_hip_lmm_score_panel_assoc_d",
     "gemma_hip_lmm_score_panel_hits_batch", "gemma_hip_lmm_score_panel_hits_batch_d", "gemma_hip_lmm_score_panel_hits_assoc_d",
+    "gemma_hip_lmm_null_panel", "gemma_hip_lmm_null_panel_d",
 ]
 LMM_MULTI_MAX = 64
 COMM_ID_BYTES = 128
@@ -67,6 +68,12 @@ class ScoreHit(C.Structure):
 class ScoreBest(C.Structure):
     """gemma_score_best: the best pair of one phenotype over a block; snp -1 and NaN fields: none"""
     _fields_ = [("beta", C.c_double), ("se", C.c_double), ("p_score", C.c_double), ("snp", C.c_int64)]
+
+
+class NullFit(C.Structure):
+    """gemma_null_fit: the null model of one phenotype, out8 of gemma_hip_lmm_null"""
+    _fields_ = [(k, C.c_double) for k in
+                ("l_mle_null", "logl_mle_H0", "l_remle_null", "logl_remle_H0", "pve", "pve_se", "vg_remle", "ve_remle")]
 
 
 class LmmCfg(C.Structure):
@@ -209,6 +216,8 @@ def lib():
     L.gemma_hip_lmm_score_panel_hits_batch.argtypes = [ci, vp, sz, sz, C.c_double, vp, sz, vp, vp]
     L.gemma_hip_lmm_score_panel_hits_batch_d.argtypes = [ci, vp, sz, sz, C.c_double, vp, sz, vp, vp, vp]
     L.gemma_hip_lmm_score_panel_hits_assoc_d.argtypes = [dp, sz, sz, C.c_double, vp, sz, vp, vp, vp]
+    L.gemma_hip_lmm_null_panel.argtypes = [sz, sz, sz, dp, dp, dp, cd, cd, sz, cd, vp, dp, dp]
+    L.gemma_hip_lmm_null_panel_d.argtypes = [sz, sz, sz, dp, dp, dp, cd, cd, sz, cd, vp, dp, dp, vp]
     L.gemma_hip_dbg_i8_digits.argtypes = [sz, C.POINTER(ci)]
     L.gemma_hip_dbg_last_utx_path.argtypes = [C.POINTER(ci)]
     L.gemma_hip_dbg_last_utx_kernel.argtypes = [C.POINTER(UtxKernelInfo)]

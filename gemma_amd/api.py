@@ -9,6 +9,7 @@ GEMMA tree) so that the parity tests read like the reference's own tests:
     CalcUtX               src/mathfunc.cpp:504-506
     CalcKin / BimbamKin / PlinkKin   src/param.cpp:1300-1321, src/gemma_io.cpp:1418-1738
     CalcLambdaNull / CalcPve         src/lmm.cpp:2143-2205
+    CalcLambdaNullPanel              the same for every column of U^T Y at once, with CalcLmmVgVeBeta's beta :2210-2281
     class LMM  (CopyFromParam fields, Analyze*, WriteFiles)   src/lmm.h:49-125
 
 Arrays may be numpy arrays (host entry points; the library stages through HBM) or torch CUDA
@@ -28,6 +29,8 @@ SUMSTAT_DTYPE = np.dtype([(k, "f8") for k in
 SCORE_DTYPE = np.dtype([(k, "f8") for k in ("beta", "se", "p_score")])  # gemma_score_rec
 SCORE_HIT_DTYPE = np.dtype([("snp", "u4"), ("pheno", "u4"), ("beta", "f8"), ("se", "f8"), ("p_score", "f8")])  # gemma_score_hit
 SCORE_BEST_DTYPE = np.dtype([("beta", "f8"), ("se", "f8"), ("p_score", "f8"), ("snp", "i8")])  # gemma_score_best
+NULL_DTYPE = np.dtype([(k, "f8") for k in ("l_mle_null", "logl_mle_H0", "l_remle_null", "logl_remle_H0", "pve", "pve_se", "vg_remle",
+                                             "ve_remle")])  # gemma_null_fit
 LMM_BATCH_SIZE = 20000  # src/lmm.h:33
 K_BATCH_SIZE = 20000  # src/param.h:32
 
@@ -379,6 +382,53 @@ def CalcLambdaNull(eval_, UtW, Uty, l_min=1e-5, l_max=1e5, n_region=10, trace_G=
     return dict(zip(keys, out.tolist()))
 
 
+def CalcLambdaNullPanel(eval_, UtW, UtY, l_min=1e-5, l_max=1e5, n_region=10, trace_G=1.0, want_beta=False):
+    """CalcLambdaNull for every column of UtY (n x T) in one launch per chunk of columns, one wavefront per phenotype: row t holds,
+    bit for bit, what CalcLambdaNull gives for UtY[:, t].  numpy in: a (T,) NULL_DTYPE array; torch device tensors in: a (T, 8)
+    device tensor in the field order of NULL_DTYPE.  want_beta: also the (T, c) covariate effects at l_remle_null and their
+    standard errors (CalcLmmVgVeBeta, src/lmm.cpp:2210-2281; c <= 16), NaN in the row of a phenotype whose UtW' H UtW is not
+    positive definite."""
+    if _is_torch(UtY):
+        import torch
+        for name, t in (("eval", eval_), ("UtW", UtW), ("UtY", UtY)):
+            if not _is_torch(t) or t.dtype != torch.float64 or not t.is_cuda:
+                raise TypeError("CalcLambdaNullPanel: %s must be a float64 device tensor" % name)
+        n = UtY.shape[0]
+        if UtY.dim() == 1:
+            UtY = UtY.reshape(n, 1)
+        if UtW.dim() == 1:
+            UtW = UtW.reshape(-1, 1)
+        UtW, UtY, eval_ = UtW.contiguous(), UtY.contiguous(), eval_.contiguous()
+        _tld(UtW), _tld(UtY)  # 2-D row-major
+        if eval_.dim() != 1 or eval_.shape[0] != n or UtW.shape[0] != n:
+            raise ValueError("CalcLambdaNullPanel: eval (%d), UtW (%d rows) and UtY (%d rows) disagree"
+                             % (eval_.shape[0], UtW.shape[0], n))
+        T, c = UtY.shape[1], UtW.shape[1]
+        fit = torch.empty((T, 8), dtype=torch.float64, device=UtY.device)
+        beta = torch.empty((T, c), dtype=torch.float64, device=UtY.device) if want_beta else None
+        se = torch.empty((T, c), dtype=torch.float64, device=UtY.device) if want_beta else None
+        L.check(L.lib().gemma_hip_lmm_null_panel_d(n, c, T, C.c_void_p(eval_.data_ptr()), C.c_void_p(UtW.data_ptr()),
+                                                   C.c_void_p(UtY.data_ptr()), l_min, l_max, n_region, trace_G,
+                                                   C.c_void_p(fit.data_ptr()), C.c_void_p(beta.data_ptr()) if want_beta else None,
+                                                   C.c_void_p(se.data_ptr()) if want_beta else None, _stream()),
+                "CalcLambdaNullPanel")
+        return (fit, beta, se) if want_beta else fit
+    n = len(eval_)
+    UtW = np.ascontiguousarray(UtW, dtype=np.float64).reshape(n, -1)
+    UtY_c = np.ascontiguousarray(UtY, dtype=np.float64).reshape(n, -1)
+    ev_c = _np64(np.ascontiguousarray(eval_, dtype=np.float64), "eval")
+    c, T = UtW.shape[1], UtY_c.shape[1]
+    if ev_c.ndim != 1 or UtW.shape[0] != n or UtY_c.shape[0] != n:
+        raise ValueError("CalcLambdaNullPanel: eval (%d), UtW and UtY disagree in their rows" % n)
+    fit = np.zeros(T, dtype=NULL_DTYPE)
+    beta = np.zeros((T, c)) if want_beta else None
+    se = np.zeros((T, c)) if want_beta else None
+    L.check(L.lib().gemma_hip_lmm_null_panel(n, c, T, _ptr(ev_c), _ptr(UtW), _ptr(UtY_c), l_min, l_max, n_region, trace_G,
+                                             _ptr(fit), _ptr(beta) if want_beta else None, _ptr(se) if want_beta else None),
+            "CalcLambdaNullPanel")
+    return (fit, beta, se) if want_beta else fit
+
+
 # ----------------------------------------------------------------------------- B4
 ScoreHitsDev = collections.namedtuple("ScoreHitsDev", "snp pheno stats")  # device tensors: int64 (m,), int64 (m,), float64 (m, 3)
 ScoreBestDev = collections.namedtuple("ScoreBestDev", "stats snp")       # device tensors: float64 (T, 3), int64 (T,)
@@ -604,15 +654,15 @@ class LMM:
     def AnalyzeMulti(self, U, eval_, UtW, UtY, geno, geno_kind=L.GENO_F64_SNP_MAJOR, plink=False, indicator_idv=None,
                      l_mle_null=None, logl_mle_H0=None, batch=LMM_BATCH_SIZE):
         """LMM::Analyze for every column of UtY (n x T) over ONE pass of the genotypes: returns (and keeps in self.sumStat) a (T, p)
-        record array, row t what Analyze gives for UtY[:, t].  Nulls that are not given are fitted per phenotype (CalcLambdaNull)."""
+        record array, row t what Analyze gives for UtY[:, t].  Nulls that are not given are fitted in one call (CalcLambdaNullPanel)."""
         UtY = np.ascontiguousarray(UtY, dtype=np.float64).reshape(len(eval_), -1)
         T = UtY.shape[1]
         if l_mle_null is None or logl_mle_H0 is None:
-            fits = [CalcLambdaNull(eval_, UtW, UtY[:, t], self.l_min, self.l_max, self.n_region) for t in range(T)]
+            fits = CalcLambdaNullPanel(eval_, UtW, UtY, self.l_min, self.l_max, self.n_region)
             if l_mle_null is None:
-                l_mle_null = [f["l_mle_null"] for f in fits]
+                l_mle_null = fits["l_mle_null"].copy()
             if logl_mle_H0 is None:
-                logl_mle_H0 = [f["logl_mle_H0"] for f in fits]
+                logl_mle_H0 = fits["logl_mle_H0"].copy()
         self.setup_multi(U, eval_, UtW, UtY, l_mle_null, logl_mle_H0, plink=plink)
         try:
             if indicator_idv is not None:
@@ -691,7 +741,7 @@ class LMM:
                           batch=LMM_BATCH_SIZE):
         """`-lmm 3` for every column of UtY (n x T) over ONE pass of the genotypes and one product per block: a (T, p) array of
         (beta, se, p_score) records (numpy in), or a (T, p, 3) device tensor (torch in; l_mle_null is then required).  Nulls that
-        are not given are fitted per phenotype (CalcLambdaNull)."""
+        are not given are fitted in one call (CalcLambdaNullPanel)."""
         if self.a_mode != 3:
             raise ValueError("LMM.AnalyzeScorePanel: a_mode %d (the score panel is a_mode 3)" % self.a_mode)
         tor = _is_torch(U)
@@ -701,8 +751,7 @@ class LMM:
         if l_mle_null is None:
             if tor:
                 raise ValueError("LMM.AnalyzeScorePanel: device inputs need l_mle_null")
-            l_mle_null = [CalcLambdaNull(eval_, UtW, UtY[:, t], self.l_min, self.l_max, self.n_region)["l_mle_null"]
-                          for t in range(T)]
+            l_mle_null = CalcLambdaNullPanel(eval_, UtW, UtY, self.l_min, self.l_max, self.n_region)["l_mle_null"].copy()
         self.setup_score_panel(U, eval_, UtW, UtY, l_mle_null)
         try:
             if indicator_idv is not None:
@@ -794,8 +843,7 @@ class LMM:
         if l_mle_null is None:
             if tor:
                 raise ValueError("LMM.AnalyzeScorePanelHits: device inputs need l_mle_null")
-            l_mle_null = [CalcLambdaNull(eval_, UtW, UtY[:, t], self.l_min, self.l_max, self.n_region)["l_mle_null"]
-                          for t in range(T)]
+            l_mle_null = CalcLambdaNullPanel(eval_, UtW, UtY, self.l_min, self.l_max, self.n_region)["l_mle_null"].copy()
         self.setup_score_panel(U, eval_, UtW, UtY, l_mle_null)
         try:
             if indicator_idv is not None:

@@ -8,12 +8,12 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgemma_hip.so")
 # one object per source, compiled concurrently; the headers each one depends on (staleness by mtime)
 UNITS = {
-    "gemma_hip.hip": ["dgemm_mfma.hip.h", "lmm_grid.hip.h", "lmm_score_panel.hip.h", "i8gemm.hip.h", "i8gemm_sparse.hip.h", "i8gemm_sparse2.hip.h", "i8gemm_sparse2_r16.hip.h", "plink_records.hip.h", "i8gemm_dense16.hip.h", "lmm_assoc.hip.h",
+    "gemma_hip.hip": ["dgemm_mfma.hip.h", "lmm_grid.hip.h", "lmm_score_panel.hip.h", "lmm_null_panel.hip.h", "i8gemm.hip.h", "i8gemm_sparse.hip.h", "i8gemm_sparse2.hip.h", "i8gemm_sparse2_r16.hip.h", "plink_records.hip.h", "i8gemm_dense16.hip.h", "lmm_assoc.hip.h",
                       "lmm_search.hip.h", "comm.hip.h", "comm_shm.hpp", "kin_i8.hip.h", "ingest.hip.h", "qc.hip.h", "lm_assoc.hip.h", "mvlmm.hip.h",
                       "mvlmm_kernels.hip.h", "eigh_tu.h", "tu_common.h",
                       # the stages of the C ABI: textual parts of gemma_hip.hip (one translation unit around g_ctx)
                       "abi_kinship.inc.h", "abi_eigen_qc.inc.h", "abi_lmm_stage.inc.h", "abi_utx.inc.h", "abi_lmm_batch.inc.h",
-                      "abi_mvlmm.inc.h", "abi_gxe_lm.inc.h", "abi_kept_comm.inc.h", "abi_lmm_multi.inc.h", "abi_lmm_score_panel.inc.h", "abi_vc.inc.h", "vc_tu.h", "abi_prdt.inc.h", "prdt_tu.h",
+                      "abi_mvlmm.inc.h", "abi_gxe_lm.inc.h", "abi_kept_comm.inc.h", "abi_lmm_multi.inc.h", "abi_lmm_score_panel.inc.h", "abi_lmm_null_panel.inc.h", "abi_vc.inc.h", "vc_tu.h", "abi_prdt.inc.h", "prdt_tu.h",
                       "abi_mqs.inc.h", "mqs_tu.h", "abi_cor.inc.h", "cor_tu.h"],
     "eigh_tu.hip": ["dgemm_mfma.hip.h", "eigh.hip.h", "eigh2.hip.h", "eigh_tu.h", "tu_common.h"],  # the eigensolver: its own object file
     "vc_tu.hip": ["dgemm_mfma.hip.h", "spd_inv.hip.h", "vc.hip.h", "vc_tu.h", "tu_common.h", "host_linalg.h", "../../include/gemma_vc_hybrid.hpp"],  # -vc 1 / -vc 2

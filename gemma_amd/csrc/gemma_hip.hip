@@ -24,6 +24,7 @@
 #include "lmm_assoc.hip.h"
 #include "lmm_grid.hip.h"
 #include "lmm_score_panel.hip.h"
+#include "lmm_null_panel.hip.h"
 #include "i8gemm.hip.h"
 #include "i8gemm_sparse.hip.h"
 #include "i8gemm_sparse2.hip.h"
@@ -572,6 +573,7 @@ extern "C" int gemma_hip_dgemm(char ta, char tb, size_t M, size_t N, size_t K, d
 #include "abi_kept_comm.inc.h"
 #include "abi_lmm_multi.inc.h"
 #include "abi_lmm_score_panel.inc.h"
+#include "abi_lmm_null_panel.inc.h"
 #include "abi_vc.inc.h"
 #include "abi_prdt.inc.h"
 #include "abi_mqs.inc.h"

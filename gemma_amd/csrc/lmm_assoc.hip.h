@@ -1220,12 +1220,13 @@ struct NullOut {
   double l_mle, logl_mle, l_remle, logl_remle, dev2_remle, Pyy_remle, Pyy_mle;
 };
 
+// y: the phenotype's U^T y -- g.Uty for the single fit, a row of the transposed panel for lmm_null_panel.hip.h
 template <class M>
-__device__ __forceinline__ void null_model(const AssocArgs &g, const M &model, int cp, int lane, NullOut *out) {
+__device__ __forceinline__ void null_model(const AssocArgs &g, const M &model, int cp, int lane, const double *y, NullOut *out) {
   SnpCtx<M> cx;
   cx.g = &g;
   cx.x = g.UtWt + (long)cp * g.n; // last covariate column
-  cx.y = g.Uty;
+  cx.y = y;
   cx.lane = lane;
   cx.m = model;
   cx.trow = nullptr;
@@ -1265,11 +1266,11 @@ __global__ __launch_bounds__(64) void lmm_null_wide_kernel(AssocArgs g, int cp, 
   m.cc = cp;
   m.L = wide_lds;
   m.ni = gen_ni_for(cp);
-  null_model(g, m, cp, threadIdx.x & 63, out);
+  null_model(g, m, cp, threadIdx.x & 63, g.Uty, out);
 }
 template <int CP>
 __global__ __launch_bounds__(64) void lmm_null_kernel(AssocArgs g, NullOut *out) {
-  null_model(g, FixedC<CP>(), CP, threadIdx.x & 63, out);
+  null_model(g, FixedC<CP>(), CP, threadIdx.x & 63, g.Uty, out);
 }
 
 __global__ __launch_bounds__(64) void lmm_null_generic_kernel(AssocArgs g, int cp, NullOut *out) {
@@ -1277,7 +1278,7 @@ __global__ __launch_bounds__(64) void lmm_null_generic_kernel(AssocArgs g, int c
   GenericC m;
   m.cc = cp;
   m.L = lds;
-  null_model(g, m, cp, threadIdx.x & 63, out);
+  null_model(g, m, cp, threadIdx.x & 63, g.Uty, out);
 }
 
 } // namespace gemma_hip

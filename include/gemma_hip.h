@@ -333,6 +333,28 @@ int gemma_hip_lmm_score_panel_hits_assoc_d(const double *UtX_d, size_t l, size_t
                                            gemma_score_hit *hits_d, size_t cap, unsigned long long *n_hits_d, gemma_score_best *best_d,
                                            void *stream);
 
+/* ---- null fits of a whole panel: what gemma_hip_lmm_null gives for one column of U^T Y, for every column ------------------- */
+/* The nulls the panel setups above are handed (l_mle_null, logl_mle_H0) and each trait's own result -- heritability, vg / ve, the
+ * covariate effects (the reference prints them in its log, src/gemma.cpp:3402-3430) -- in one launch per chunk of columns, one
+ * wavefront per phenotype.  fit[t] equals, in all eight fields and in every bit, what gemma_hip_lmm_null returns for column t.
+ * UtY: n x T row-major, the layout the panel setups take.  beta / se_beta: NULL (both), or T x n_cvt row-major: the covariate
+ * effects at l_remle_null and their standard errors, CalcLmmVgVeBeta src/lmm.cpp:2210-2281, for n_cvt <= 16; a phenotype whose
+ * UtW^T H UtW is not positive definite there (or whose lambda is not finite) gets NaN in its own row and the call still succeeds.
+ * Stateless like gemma_hip_lmm_null: no LMM setup is needed or disturbed.  The columns are walked in chunks sized from the free
+ * device memory (GEMMA_HIP_NULL_PANEL_CHUNK=<columns>, read at the call, forces the size); a chunk that does not fit returns
+ * GEMMA_HIP_ENOMEM with the byte count.  GEMMA_HIP_EINVAL: T == 0, a null pointer (other than beta with se_beta), one of beta /
+ * se_beta without the other, n <= n_cvt, n above 2 097 120 (65 535 x 32), n_cvt outside 1..65, beta with n_cvt > 16, l_max <= l_min, n_region outside 1..64.
+ * The _d form takes device pointers throughout, queues its work on `stream` and synchronises it before it returns. */
+typedef struct {
+  double l_mle_null, logl_mle_H0, l_remle_null, logl_remle_H0, pve, pve_se, vg_remle, ve_remle;
+} gemma_null_fit; /* = out8 of gemma_hip_lmm_null */
+int gemma_hip_lmm_null_panel(size_t n, size_t n_cvt, size_t T, const double *eval, const double *UtW, const double *UtY,
+                             double l_min, double l_max, size_t n_region, double trace_G, gemma_null_fit *fit, double *beta,
+                             double *se_beta);
+int gemma_hip_lmm_null_panel_d(size_t n, size_t n_cvt, size_t T, const double *eval_d, const double *UtW_d, const double *UtY_d,
+                               double l_min, double l_max, size_t n_region, double trace_G, gemma_null_fit *fit_d, double *beta_d,
+                               double *se_beta_d, void *stream);
+
 /* ---- multivariate LMM (-lmm 1..4 -n a b c ...) ------------------------------------ */
 /* MVLMM::AnalyzeBimbam / AnalyzePlink, src/mvlmm.cpp:2972-3416 / :3418-3899, and with opt->gxe the interaction test of
  * AnalyzeBimbamGXE / AnalyzePlinkGXE (:3970-4414 / :4416-4870).  d phenotypes (1..GEMMA_MV_DMAX), n_cvt covariates with

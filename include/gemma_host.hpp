@@ -499,6 +499,28 @@ inline NullModel CalcLambdaNull(const Vector *eval, const Matrix *UtW, const Vec
               "CalcLambda (null)");
   return NullModel{o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]};
 }
+// The same for every column of UtY (ni_test x T) in one call (gemma_hip_lmm_null_panel): element t is, bit for bit, CalcLambdaNull of
+// column t.  beta / se_beta: T x n_cvt, the covariate effects at l_remle_null and their standard errors (CalcLmmVgVeBeta,
+// src/lmm.cpp:2210-2281; n_cvt <= 16), both or neither.
+inline std::vector<NullModel> CalcLambdaNullPanel(const Vector *eval, const Matrix *UtW, const Matrix *UtY, double l_min, double l_max,
+                                                  size_t n_region, double trace_G, Matrix *beta = nullptr, Matrix *se_beta = nullptr) {
+  const size_t T = UtY->size2, c = UtW->size2;
+  if (UtW->tda != UtW->size2 || UtY->tda != UtY->size2 || eval->stride != 1)
+    throw HipError(GEMMA_HIP_EINVAL, "CalcLambdaNullPanel: contiguous inputs");
+  if (UtY->size1 != UtW->size1 || eval->size != UtW->size1)
+    throw HipError(GEMMA_HIP_EINVAL, "CalcLambdaNullPanel: eval, UtW and UtY disagree in their rows");
+  for (const Matrix *m : {beta, se_beta})
+    if (m && (m->size1 != T || m->size2 != c || m->tda != c)) throw HipError(GEMMA_HIP_EINVAL, "CalcLambdaNullPanel: beta / se_beta are T x n_cvt");
+  std::vector<gemma_null_fit> fit(T);
+  enforce_hip(gemma_hip_lmm_null_panel(UtW->size1, c, T, eval->data, UtW->data, UtY->data, l_min, l_max, n_region, trace_G, fit.data(),
+                                       beta ? beta->data : nullptr, se_beta ? se_beta->data : nullptr),
+              "CalcLambda (null panel)");
+  std::vector<NullModel> out;
+  out.reserve(T);
+  for (const gemma_null_fit &f : fit)
+    out.push_back(NullModel{f.l_mle_null, f.logl_mle_H0, f.l_remle_null, f.logl_remle_H0, f.pve, f.pve_se, f.vg_remle, f.ve_remle});
+  return out;
+}
 
 // class LMM, src/lmm.h:49-125 -- the members CopyFromParam fills (src/lmm.cpp:56-90) and the drivers
 class LMM {
@@ -722,11 +744,23 @@ public:
   }
 
   // ---- T univariate scans over ONE pass of the genotypes (gemma_hip_lmm_multi_*; the reference runs `-n t` once per trait) ----
-  // UtY: ni_test x T (column t = U^T y_t), l_mle_null_multi / logl_mle_H0_multi: the T null fits (CalcLambdaNull per column; read
+  // UtY: ni_test x T (column t = U^T y_t), l_mle_null_multi / logl_mle_H0_multi: the T null fits (CalcNullMulti below; read
   // for a_mode 2, 3, 4, 9).  One set of analysed individuals: those that have every phenotype.  sumStatMulti[t] is what Analyze*
   // leaves in sumStat for phenotype t, bit for bit; WriteFilesMulti writes it through WriteFiles.
   std::vector<std::vector<SUMSTAT>> sumStatMulti;
   std::vector<double> l_mle_null_multi, logl_mle_H0_multi;
+  // the T null fits in one call: fills l_mle_null_multi / logl_mle_H0_multi from CalcLambdaNullPanel and returns the fits
+  std::vector<NullModel> CalcNullMulti(const Vector *eval, const Matrix *UtW, const Matrix *UtY, double trace_G = 1.0,
+                                       Matrix *beta = nullptr, Matrix *se_beta = nullptr) {
+    std::vector<NullModel> fits = CalcLambdaNullPanel(eval, UtW, UtY, l_min, l_max, n_region, trace_G, beta, se_beta);
+    l_mle_null_multi.clear();
+    logl_mle_H0_multi.clear();
+    for (const NullModel &f : fits) {
+      l_mle_null_multi.push_back(f.l_mle_null);
+      logl_mle_H0_multi.push_back(f.logl_mle_H0);
+    }
+    return fits;
+  }
 
   void AnalyzePlinkMulti(const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY) {
     const std::string file_bed = file_bfile + ".bed";

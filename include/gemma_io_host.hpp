@@ -1235,8 +1235,9 @@ inline void ReadFile_eigenD(const std::string &file_kd, bool &error, Vector *eva
 // ---------------------------------------------------------------------------------------------------------------
 // <o>.log.txt -- the lines of GEMMA::WriteLog (src/gemma.cpp:3159-3590) that belong to this path, in its format
 // ("## key = value", ostream default precision): the summary counts, the null-model estimates of the univariate LMM and
-// the five timers (minutes), plus one line naming the device.  The null model's beta / se(beta) lines are not written
-// (gemma_hip_lmm_null returns the variance components only).
+// the five timers (minutes), plus one line naming the device.  The null model's beta / se(beta) lines are not written by this
+// log: gemma_hip_lmm_null returns the variance components only.  The covariate effects come from gemma_hip_lmm_null_panel
+// (CalcLambdaNullPanel of gemma_host.hpp, T >= 1); tests/cpp/null_panel_file_driver.cpp prints them per phenotype.
 // ---------------------------------------------------------------------------------------------------------------
 struct RunLog {
   std::string command_line;
