@@ -72,6 +72,30 @@ def _tld(t):
     return t.stride(0) if t.shape[0] > 1 else t.shape[1]
 
 
+def _block_dims(geno, geno_kind, l=None, ld=None):
+    """(l, ld) of a genotype block, numpy or torch: l SNPs -- the columns of individual-major input (the reference's Xlarge), the rows
+    otherwise -- and the row stride in items.  Values the caller gives are kept."""
+    if l is None:
+        l = geno.shape[1] if geno_kind == L.GENO_F64_IDV_MAJOR else geno.shape[0]
+    if ld is None:
+        ld = _tld(geno) if _is_torch(geno) else _row_ld(geno)
+    return l, ld
+
+
+def _scan(setup, set_indicator, finish, indicator_idv, geno, batch, block, prepare=None):
+    """The frame of every Analyze*: setup(), the indicator, prepare() (what else the state needs before its first block), then
+    block(s0, geno[s0:s0 + batch]) for every block -> the list of their results.  finish() runs whatever a block raises."""
+    setup()
+    try:
+        if indicator_idv is not None:
+            set_indicator(indicator_idv)
+        if prepare is not None:
+            prepare()
+        return [block(s0, geno[s0:s0 + batch]) for s0 in range(0, geno.shape[0], batch)]
+    finally:
+        finish()
+
+
 def init(device=-1, verbose=0):
     L.check(L.lib().gemma_hip_init(device, verbose), "gemma_hip_init")
 
@@ -225,17 +249,10 @@ def kin_begin(n_total, k_mode=1):
 
 
 def kin_add(geno, geno_kind, l=None, ld=None):
+    l, ld = _block_dims(geno, geno_kind, l, ld)
     if _is_torch(geno):
-        if l is None:  # individual-major: SNP j is column j (the reference's Xlarge)
-            l = geno.shape[1] if geno_kind == L.GENO_F64_IDV_MAJOR else geno.shape[0]
-        ld = _tld(geno) if ld is None else ld
         rc = L.lib().gemma_hip_kin_add_d(geno_kind, C.c_void_p(geno.data_ptr()), l, ld, _stream())
     else:
-        if geno_kind == L.GENO_F64_IDV_MAJOR:
-            l = geno.shape[1] if l is None else l
-        else:
-            l = geno.shape[0] if l is None else l
-        ld = _row_ld(geno) if ld is None else ld
         rc = L.lib().gemma_hip_kin_add(geno_kind, _ptr(geno), l, ld)
     L.check(rc, "kin_add")
 
@@ -477,27 +494,27 @@ class LMM:
         cfg.plink_nan_rule = 1 if plink else 0
         return cfg
 
-    def setup(self, U, eval_, UtW, Uty, plink=False):
+    def _setup(self, where, U, eval_, UtW, UtY, plink, host, dev):
+        """(U, eval, UtW, UtY) to the library: torch device tensors are borrowed in place -- dev(cfg, U, eval, UtW, UtY, stream) --,
+        numpy arrays go as contiguous float64 copies -- host(cfg, U, eval, UtW, UtY)."""
         n = U.shape[0]
         if _is_torch(U):
             c = UtW.shape[1] if UtW.dim() == 2 else 1
-            cfg = self._cfg(n, c, plink)
-            self._keep = (U, eval_, UtW, Uty)  # borrowed by the library until finish()
-            rc = L.lib().gemma_hip_lmm_setup_d(C.byref(cfg), C.c_void_p(U.data_ptr()),
-                                               C.c_void_p(eval_.data_ptr()), C.c_void_p(UtW.data_ptr()),
-                                               C.c_void_p(Uty.data_ptr()), _stream())
+            self._keep = (U, eval_, UtW, UtY.contiguous())  # borrowed by the library until finish()
+            rc = dev(C.byref(self._cfg(n, c, plink)), *[C.c_void_p(t.data_ptr()) for t in self._keep], _stream())
         else:
             UtW = np.ascontiguousarray(UtW, dtype=np.float64).reshape(n, -1)
             c = UtW.shape[1]
-            cfg = self._cfg(n, c, plink)
-            # converted copies stay bound to names until the call returns (_ptr keeps only the address)
-            U_c = _np64(np.ascontiguousarray(U), "U")
-            ev_c = np.ascontiguousarray(eval_, dtype=np.float64)
-            Uty_c = np.ascontiguousarray(Uty, dtype=np.float64)
-            rc = L.lib().gemma_hip_lmm_setup(C.byref(cfg), _ptr(U_c), _ptr(ev_c), _ptr(UtW), _ptr(Uty_c))
-        L.check(rc, "LMM.setup")
+            # converted copies stay bound to a name until the call returns (_ptr keeps only the address)
+            arrs = (_np64(np.ascontiguousarray(U), "U"), np.ascontiguousarray(eval_, dtype=np.float64), UtW,
+                    np.ascontiguousarray(UtY, dtype=np.float64))
+            rc = host(C.byref(self._cfg(n, c, plink)), *[_ptr(a) for a in arrs])
+        L.check(rc, where)
         self.ni_test, self.n_cvt = n, c
         self._active = True
+
+    def setup(self, U, eval_, UtW, Uty, plink=False):
+        self._setup("LMM.setup", U, eval_, UtW, Uty, plink, L.lib().gemma_hip_lmm_setup, L.lib().gemma_hip_lmm_setup_d)
 
     def setup_kept(self, UtW, Uty, plink=False):
         """lmm_setup on the kept (U, eval) of EigenDecomp_kept_K (host UtW n x c, Uty n)."""
@@ -515,21 +532,15 @@ class LMM:
 
     def batch(self, geno, geno_kind, out=None, l=None, ld=None):
         """One block of SNPs -> SUMSTAT records (numpy in/out, or torch device tensors in/out)."""
+        l, ld = _block_dims(geno, geno_kind, l, ld)
         if _is_torch(geno):
             import torch
-            l = geno.shape[0] if l is None else l
-            ld = _tld(geno) if ld is None else ld
             if out is None:
                 out = torch.empty((l, 8), dtype=torch.float64, device=geno.device)
             rc = L.lib().gemma_hip_lmm_batch_d(geno_kind, C.c_void_p(geno.data_ptr()), l, ld,
                                                C.c_void_p(out.data_ptr()), _stream())
             L.check(rc, "LMM.batch")
             return out
-        if geno_kind == L.GENO_F64_IDV_MAJOR:
-            l = geno.shape[1] if l is None else l
-        else:
-            l = geno.shape[0] if l is None else l
-        ld = _row_ld(geno) if ld is None else ld
         if out is None:
             out = np.zeros(l, dtype=SUMSTAT_DTYPE)
         L.check(L.lib().gemma_hip_lmm_batch(geno_kind, _ptr(geno), l, ld, _ptr(out)), "LMM.batch")
@@ -582,23 +593,15 @@ class LMM:
                 indicator_idv=None, batch=LMM_BATCH_SIZE):
         """LMM::Analyze (src/lmm.cpp:1474-1658): stream SNP-major `geno` in blocks of LMM_BATCH_SIZE;
         results are appended in SNP order to self.sumStat."""
-        self.setup(U, eval_, UtW, Uty, plink=plink)
-        try:
-            if indicator_idv is not None:
-                self.set_indicator(indicator_idv)
-            outs = []
-            for s0 in range(0, geno.shape[0], batch):
-                outs.append(self.batch(geno[s0:s0 + batch], geno_kind))
-            self.sumStat = np.concatenate(outs) if outs else np.zeros(0, dtype=SUMSTAT_DTYPE)
-        finally:
-            self.finish()
+        outs = _scan(lambda: self.setup(U, eval_, UtW, Uty, plink=plink), self.set_indicator, self.finish, indicator_idv, geno, batch,
+                     lambda s0, blk: self.batch(blk, geno_kind))
+        self.sumStat = np.concatenate(outs) if outs else np.zeros(0, dtype=SUMSTAT_DTYPE)
         return self.sumStat
 
     # -- T phenotypes over one U^T x (gemma_hip_lmm_multi_*) ----------------------------
     def setup_multi(self, U, eval_, UtW, UtY, l_mle_null=None, logl_mle_H0=None, plink=False):
         """lmm_setup for the T columns of UtY (n x T) at once: same individuals, kinship and covariates.  l_mle_null /
         logl_mle_H0: T values each (a_mode 2, 3, 4, 9); self.l_mle_null / self.logl_mle_H0 are not read."""
-        n = U.shape[0]
         T = UtY.shape[1]
         nul = None if l_mle_null is None else np.ascontiguousarray(l_mle_null, dtype=np.float64)
         lgl = None if logl_mle_H0 is None else np.ascontiguousarray(logl_mle_H0, dtype=np.float64)
@@ -607,45 +610,24 @@ class LMM:
                 raise ValueError("LMM.setup_multi: %d null values for %d phenotypes" % (v.size, T))
         pn = _ptr(nul) if nul is not None else None
         pl = _ptr(lgl) if lgl is not None else None
-        if _is_torch(U):
-            c = UtW.shape[1] if UtW.dim() == 2 else 1
-            cfg = self._cfg(n, c, plink)
-            UtY = UtY.contiguous()
-            self._keep = (U, eval_, UtW, UtY)  # U, eval: borrowed by the library until finish()
-            rc = L.lib().gemma_hip_lmm_multi_setup_d(C.byref(cfg), T, pn, pl, C.c_void_p(U.data_ptr()),
-                                                     C.c_void_p(eval_.data_ptr()), C.c_void_p(UtW.data_ptr()),
-                                                     C.c_void_p(UtY.data_ptr()), _stream())
-        else:
-            UtW = np.ascontiguousarray(UtW, dtype=np.float64).reshape(n, -1)
-            c = UtW.shape[1]
-            cfg = self._cfg(n, c, plink)
-            U_c = _np64(np.ascontiguousarray(U), "U")
-            ev_c = np.ascontiguousarray(eval_, dtype=np.float64)
-            UtY_c = np.ascontiguousarray(UtY, dtype=np.float64)
-            rc = L.lib().gemma_hip_lmm_multi_setup(C.byref(cfg), T, pn, pl, _ptr(U_c), _ptr(ev_c), _ptr(UtW), _ptr(UtY_c))
-        L.check(rc, "LMM.setup_multi")
-        self.ni_test, self.n_cvt, self.n_ph = n, c, T
-        self._active = True
+        self._setup("LMM.setup_multi", U, eval_, UtW, UtY, plink,
+                    lambda cfg, *arrs: L.lib().gemma_hip_lmm_multi_setup(cfg, T, pn, pl, *arrs),
+                    lambda cfg, *arrs: L.lib().gemma_hip_lmm_multi_setup_d(cfg, T, pn, pl, *arrs))
+        self.n_ph = T
 
     def batch_multi(self, geno, geno_kind, out=None, l=None, ld=None):
         """One block of SNPs -> (T, l) SUMSTAT records (numpy), or a (T, l, 8) device tensor (torch): U^T x once, the per-SNP
         stage per phenotype."""
         T = self.n_ph
+        l, ld = _block_dims(geno, geno_kind, l, ld)
         if _is_torch(geno):
             import torch
-            l = geno.shape[0] if l is None else l
-            ld = _tld(geno) if ld is None else ld
             if out is None:
                 out = torch.empty((T, l, 8), dtype=torch.float64, device=geno.device)
             rc = L.lib().gemma_hip_lmm_multi_batch_d(geno_kind, C.c_void_p(geno.data_ptr()), l, ld,
                                                      C.c_void_p(out.data_ptr()), _stream())
             L.check(rc, "LMM.batch_multi")
             return out
-        if geno_kind == L.GENO_F64_IDV_MAJOR:
-            l = geno.shape[1] if l is None else l
-        else:
-            l = geno.shape[0] if l is None else l
-        ld = _row_ld(geno) if ld is None else ld
         if out is None:
             out = np.zeros((T, l), dtype=SUMSTAT_DTYPE)
         L.check(L.lib().gemma_hip_lmm_multi_batch(geno_kind, _ptr(geno), l, ld, _ptr(out)), "LMM.batch_multi")
@@ -663,65 +645,36 @@ class LMM:
                 l_mle_null = fits["l_mle_null"].copy()
             if logl_mle_H0 is None:
                 logl_mle_H0 = fits["logl_mle_H0"].copy()
-        self.setup_multi(U, eval_, UtW, UtY, l_mle_null, logl_mle_H0, plink=plink)
-        try:
-            if indicator_idv is not None:
-                self.set_indicator(indicator_idv)
-            outs = []
-            for s0 in range(0, geno.shape[0], batch):
-                outs.append(self.batch_multi(geno[s0:s0 + batch], geno_kind))
-            self.sumStat = np.concatenate(outs, axis=1) if outs else np.zeros((T, 0), dtype=SUMSTAT_DTYPE)
-        finally:
-            self.finish()
+        outs = _scan(lambda: self.setup_multi(U, eval_, UtW, UtY, l_mle_null, logl_mle_H0, plink=plink), self.set_indicator, self.finish,
+                     indicator_idv, geno, batch, lambda s0, blk: self.batch_multi(blk, geno_kind))
+        self.sumStat = np.concatenate(outs, axis=1) if outs else np.zeros((T, 0), dtype=SUMSTAT_DTYPE)
         return self.sumStat
 
     # -- score panel: -lmm 3 of T phenotypes from one product per block (gemma_hip_lmm_score_panel_*) --
     def setup_score_panel(self, U, eval_, UtW, UtY, l_mle_null):
         """Score-panel setup for the T columns of UtY (n x T): a_mode must be 3; l_mle_null holds the T null lambdas.  numpy
         arrays are uploaded, torch device tensors are used in place (U, eval: borrowed until finish())."""
-        n = U.shape[0]
         T = UtY.shape[1]
         nul = np.ascontiguousarray(l_mle_null, dtype=np.float64).ravel()
         if nul.size != T:
             raise ValueError("LMM.setup_score_panel: %d null values for %d phenotypes" % (nul.size, T))
-        if _is_torch(U):
-            c = UtW.shape[1] if UtW.dim() == 2 else 1
-            cfg = self._cfg(n, c, False)
-            UtY = UtY.contiguous()
-            self._keep = (U, eval_, UtW, UtY)
-            rc = L.lib().gemma_hip_lmm_score_panel_setup_d(C.byref(cfg), T, _ptr(nul), C.c_void_p(U.data_ptr()),
-                                                           C.c_void_p(eval_.data_ptr()), C.c_void_p(UtW.data_ptr()),
-                                                           C.c_void_p(UtY.data_ptr()), _stream())
-        else:
-            UtW = np.ascontiguousarray(UtW, dtype=np.float64).reshape(n, -1)
-            c = UtW.shape[1]
-            cfg = self._cfg(n, c, False)
-            U_c = _np64(np.ascontiguousarray(U), "U")
-            ev_c = np.ascontiguousarray(eval_, dtype=np.float64)
-            UtY_c = np.ascontiguousarray(UtY, dtype=np.float64)
-            rc = L.lib().gemma_hip_lmm_score_panel_setup(C.byref(cfg), T, _ptr(nul), _ptr(U_c), _ptr(ev_c), _ptr(UtW), _ptr(UtY_c))
-        L.check(rc, "LMM.setup_score_panel")
-        self.ni_test, self.n_cvt, self.n_ph = n, c, T
-        self._active = True
+        self._setup("LMM.setup_score_panel", U, eval_, UtW, UtY, False,
+                    lambda cfg, *arrs: L.lib().gemma_hip_lmm_score_panel_setup(cfg, T, _ptr(nul), *arrs),
+                    lambda cfg, *arrs: L.lib().gemma_hip_lmm_score_panel_setup_d(cfg, T, _ptr(nul), *arrs))
+        self.n_ph = T
 
     def batch_score_panel(self, geno, geno_kind, out=None, l=None, ld=None):
         """One block of SNPs -> (T, l) SCORE_DTYPE records (numpy), or a (T, l, 3) device tensor (torch)."""
         T = self.n_ph
+        l, ld = _block_dims(geno, geno_kind, l, ld)
         if _is_torch(geno):
             import torch
-            l = geno.shape[0] if l is None else l
-            ld = _tld(geno) if ld is None else ld
             if out is None:
                 out = torch.empty((T, l, 3), dtype=torch.float64, device=geno.device)
             rc = L.lib().gemma_hip_lmm_score_panel_batch_d(geno_kind, C.c_void_p(geno.data_ptr()), l, ld,
                                                            C.c_void_p(out.data_ptr()), _stream())
             L.check(rc, "LMM.batch_score_panel")
             return out
-        if geno_kind == L.GENO_F64_IDV_MAJOR:
-            l = geno.shape[1] if l is None else l
-        else:
-            l = geno.shape[0] if l is None else l
-        ld = _row_ld(geno) if ld is None else ld
         if out is None:
             out = np.zeros((T, l), dtype=SCORE_DTYPE)
         L.check(L.lib().gemma_hip_lmm_score_panel_batch(geno_kind, _ptr(geno), l, ld, _ptr(out)), "LMM.batch_score_panel")
@@ -752,20 +705,13 @@ class LMM:
             if tor:
                 raise ValueError("LMM.AnalyzeScorePanel: device inputs need l_mle_null")
             l_mle_null = CalcLambdaNullPanel(eval_, UtW, UtY, self.l_min, self.l_max, self.n_region)["l_mle_null"].copy()
-        self.setup_score_panel(U, eval_, UtW, UtY, l_mle_null)
-        try:
-            if indicator_idv is not None:
-                self.set_indicator(indicator_idv)
-            outs = []
-            for s0 in range(0, geno.shape[0], batch):
-                outs.append(self.batch_score_panel(geno[s0:s0 + batch], geno_kind))
-            if tor:
-                import torch
-                self.scorePanel = torch.cat(outs, dim=1) if outs else torch.empty((T, 0, 3), dtype=torch.float64, device=U.device)
-            else:
-                self.scorePanel = np.concatenate(outs, axis=1) if outs else np.zeros((T, 0), dtype=SCORE_DTYPE)
-        finally:
-            self.finish()
+        outs = _scan(lambda: self.setup_score_panel(U, eval_, UtW, UtY, l_mle_null), self.set_indicator, self.finish, indicator_idv, geno,
+                     batch, lambda s0, blk: self.batch_score_panel(blk, geno_kind))
+        if tor:
+            import torch
+            self.scorePanel = torch.cat(outs, dim=1) if outs else torch.empty((T, 0, 3), dtype=torch.float64, device=U.device)
+        else:
+            self.scorePanel = np.concatenate(outs, axis=1) if outs else np.zeros((T, 0), dtype=SCORE_DTYPE)
         return self.scorePanel
 
     # -- the hits form of the score panel: pairs with p_score <= p_max and the best pair per phenotype --
@@ -804,13 +750,11 @@ class LMM:
         size of the first list; a block with more hits is run again with a list that holds them."""
         T = self.n_ph
         p_max = float(p_max)
+        l, ld = _block_dims(geno, geno_kind)
         if _is_torch(geno):
-            l, ld = geno.shape[0], _tld(geno)
             gp, st = C.c_void_p(geno.data_ptr()), _stream()
             return self._hits_dev(lambda raw, cap_, cnt, best: L.lib().gemma_hip_lmm_score_panel_hits_batch_d(
                 geno_kind, gp, l, ld, p_max, raw, cap_, cnt, best, st), l, p_max, cap, geno.device)
-        l = geno.shape[1] if geno_kind == L.GENO_F64_IDV_MAJOR else geno.shape[0]
-        ld = _row_ld(geno)
         cap = self._hits_cap(l, p_max, cap)
         best = np.zeros(T, dtype=SCORE_BEST_DTYPE)
         cnt = C.c_ulonglong(0)
@@ -844,17 +788,9 @@ class LMM:
             if tor:
                 raise ValueError("LMM.AnalyzeScorePanelHits: device inputs need l_mle_null")
             l_mle_null = CalcLambdaNullPanel(eval_, UtW, UtY, self.l_min, self.l_max, self.n_region)["l_mle_null"].copy()
-        self.setup_score_panel(U, eval_, UtW, UtY, l_mle_null)
-        try:
-            if indicator_idv is not None:
-                self.set_indicator(indicator_idv)
-            parts, bests = [], []
-            for s0 in range(0, geno.shape[0], batch):
-                h, b = self.batch_score_panel_hits(geno[s0:s0 + batch], geno_kind, p_max)
-                parts.append((s0, h))
-                bests.append((s0, b))
-        finally:
-            self.finish()
+        outs = _scan(lambda: self.setup_score_panel(U, eval_, UtW, UtY, l_mle_null), self.set_indicator, self.finish, indicator_idv, geno,
+                     batch, lambda s0, blk: (s0,) + self.batch_score_panel_hits(blk, geno_kind, p_max))
+        parts, bests = [(s0, h) for s0, h, _ in outs], [(s0, b) for s0, _, b in outs]
         if tor:
             import torch
             dev = U.device
@@ -913,22 +849,16 @@ class LMM:
         """LMM::AnalyzeBimbamGXE / AnalyzePlinkGXE (src/lmm.cpp:2283-2608): covariates [W, env, x_s], tested variable
         x_s . env; env is over the analysed individuals."""
         plink = geno_kind == L.GENO_PLINK_2BIT
-        self.setup(U, eval_, UtW, Uty, plink=plink)
-        try:
-            if indicator_idv is not None:
-                self.set_indicator(indicator_idv)
-            env = np.ascontiguousarray(env, dtype=np.float64)
-            L.check(L.lib().gemma_hip_lmm_set_env(_ptr(env)), "LMM.set_env")
-            geno = np.ascontiguousarray(geno)
-            outs = []
-            for s0 in range(0, geno.shape[0], batch):
-                blk = geno[s0:s0 + batch]
-                out = np.zeros(blk.shape[0], dtype=SUMSTAT_DTYPE)
-                L.check(L.lib().gemma_hip_lmm_gxe_batch(geno_kind, _ptr(blk), blk.shape[0], blk.shape[1], _ptr(out)),
-                        "LMM.AnalyzeGXE")
-                outs.append(out)
-        finally:
-            self.finish()
+        env = np.ascontiguousarray(env, dtype=np.float64)
+
+        def block(s0, blk):
+            l, ld = _block_dims(blk, geno_kind)
+            out = np.zeros(l, dtype=SUMSTAT_DTYPE)
+            L.check(L.lib().gemma_hip_lmm_gxe_batch(geno_kind, _ptr(blk), l, ld, _ptr(out)), "LMM.AnalyzeGXE")
+            return out
+        outs = _scan(lambda: self.setup(U, eval_, UtW, Uty, plink=plink), self.set_indicator, self.finish, indicator_idv,
+                     np.ascontiguousarray(geno), batch, block,
+                     prepare=lambda: L.check(L.lib().gemma_hip_lmm_set_env(_ptr(env)), "LMM.set_env"))
         self.sumStat = np.concatenate(outs) if outs else np.zeros(0, dtype=SUMSTAT_DTYPE)
         return self.sumStat
 
@@ -970,22 +900,20 @@ class LM:
         """LM::AnalyzeBimbam / AnalyzePlink (src/lm.cpp:382-640) over SNP-major `geno`."""
         y = np.ascontiguousarray(y, dtype=np.float64)
         W = np.ascontiguousarray(W, dtype=np.float64).reshape(len(y), -1)
-        L.check(L.lib().gemma_hip_lm_setup(self.a_mode, W.shape[0], W.shape[1], _ptr(W), _ptr(y)), "LM.setup")
         geno = np.ascontiguousarray(geno)  # SNP-major rows (a Fortran-ordered array would hand over a stride of 1)
-        try:
-            if indicator_idv is not None:
-                ind = np.ascontiguousarray(indicator_idv, dtype=np.int32)
-                L.check(L.lib().gemma_hip_lmm_set_indicator(_ptr(ind), ind.size), "LM.set_indicator")
-            outs = []
-            for s0 in range(0, geno.shape[0], batch):
-                blk = geno[s0:s0 + batch]
-                out = np.zeros(blk.shape[0], dtype=SUMSTAT_DTYPE)
-                L.check(L.lib().gemma_hip_lm_batch(geno_kind, _ptr(blk), blk.shape[0], _row_ld(blk),
-                                                   _ptr(out)), "LM.batch")
-                outs.append(out)
-            self.sumStat = np.concatenate(outs) if outs else np.zeros(0, dtype=SUMSTAT_DTYPE)
-        finally:
-            L.check(L.lib().gemma_hip_lm_finish(), "LM.finish")
+
+        def set_indicator(indicator_idv):
+            ind = np.ascontiguousarray(indicator_idv, dtype=np.int32)
+            L.check(L.lib().gemma_hip_lmm_set_indicator(_ptr(ind), ind.size), "LM.set_indicator")
+
+        def block(s0, blk):
+            l, ld = _block_dims(blk, geno_kind)
+            out = np.zeros(l, dtype=SUMSTAT_DTYPE)
+            L.check(L.lib().gemma_hip_lm_batch(geno_kind, _ptr(blk), l, ld, _ptr(out)), "LM.batch")
+            return out
+        outs = _scan(lambda: L.check(L.lib().gemma_hip_lm_setup(self.a_mode, W.shape[0], W.shape[1], _ptr(W), _ptr(y)), "LM.setup"),
+                     set_indicator, lambda: L.check(L.lib().gemma_hip_lm_finish(), "LM.finish"), indicator_idv, geno, batch, block)
+        self.sumStat = np.concatenate(outs) if outs else np.zeros(0, dtype=SUMSTAT_DTYPE)
         return self.sumStat
 
 
@@ -1052,9 +980,9 @@ class MVLMM:
             geno = np.ascontiguousarray(geno)
             for s0 in range(0, geno.shape[0], batch):
                 blk = geno[s0:s0 + batch]
-                out = np.zeros((blk.shape[0], stride))
-                L.check(L.lib().gemma_hip_mvlmm_batch(geno_kind, _ptr(blk), blk.shape[0], blk.shape[1], _ptr(out)),
-                        "MVLMM.Analyze")
+                l, ld = _block_dims(blk, geno_kind)
+                out = np.zeros((l, stride))
+                L.check(L.lib().gemma_hip_mvlmm_batch(geno_kind, _ptr(blk), l, ld, _ptr(out)), "MVLMM.Analyze")
                 outs.append(out)
         finally:
             lmm.finish()

@@ -12,7 +12,7 @@ UNITS = {
                       "lmm_search.hip.h", "comm.hip.h", "comm_shm.hpp", "kin_i8.hip.h", "ingest.hip.h", "qc.hip.h", "lm_assoc.hip.h", "mvlmm.hip.h",
                       "mvlmm_kernels.hip.h", "eigh_tu.h", "tu_common.h",
                       # the stages of the C ABI: textual parts of gemma_hip.hip (one translation unit around g_ctx)
-                      "abi_kinship.inc.h", "abi_eigen_qc.inc.h", "abi_lmm_stage.inc.h", "abi_utx.inc.h", "abi_lmm_batch.inc.h",
+                      "abi_host_block.inc.h", "abi_kinship.inc.h", "abi_eigen_qc.inc.h", "abi_lmm_stage.inc.h", "abi_utx.inc.h", "abi_lmm_batch.inc.h",
                       "abi_mvlmm.inc.h", "abi_gxe_lm.inc.h", "abi_kept_comm.inc.h", "abi_lmm_multi.inc.h", "abi_lmm_score_panel.inc.h", "abi_lmm_null_panel.inc.h", "abi_vc.inc.h", "vc_tu.h", "abi_prdt.inc.h", "prdt_tu.h",
                       "abi_mqs.inc.h", "mqs_tu.h", "abi_cor.inc.h", "cor_tu.h"],
     "eigh_tu.hip": ["dgemm_mfma.hip.h", "eigh.hip.h", "eigh2.hip.h", "eigh_tu.h", "tu_common.h"],  # the eigensolver: its own object file

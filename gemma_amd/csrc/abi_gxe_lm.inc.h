@@ -1,6 +1,6 @@
 // Part of gemma_hip.hip (ONE translation unit: the parts share the context g_ctx and the helpers of its anonymous namespace, and are
 // included there in this order; round 6: the 3 500-line file cut along its stages for reading -- no behaviour change).
-// This part: GXE, host-pointer batch, dbg_utx, the linear model (-lm), the null model, lmm_finish.
+// This part: GXE, host-pointer batch, dbg_utx, the linear model (-lm) with its release list (lm_release), the null model, lmm_finish.
 
 // ---- GXE variants: LMM::AnalyzeBimbamGXE / AnalyzePlinkGXE, src/lmm.cpp:2283-2608
 // env over the analysed individuals (after lmm_setup): U^T env becomes the (c+1)-th shared covariate row (:2307-2309)
@@ -33,7 +33,7 @@ extern "C" int gemma_hip_lmm_gxe_batch_d(int kind, const void *geno, size_t l, s
   if (!g_ctx.lmm_active || !g_ctx.gxe_ready) return fail(GEMMA_HIP_ESTATE, "lmm_gxe_batch before lmm_setup + lmm_set_env");
   if (l == 0) return GEMMA_HIP_OK;
   if (kind == GEMMA_GENO_F64_IDV_MAJOR) return fail(GEMMA_HIP_EINVAL, "lmm_gxe_batch: SNP-major input only");
-  int rc = check_batch_args("lmm_gxe_batch", kind, geno, l, ld, out_d);
+  int rc = block_geom("lmm_gxe_batch", kind, g_ctx.cfg.n, true, geno, l, ld, out_d);
   if (rc) return rc;
   hipStream_t s = S(stream);
   const size_t n = g_ctx.cfg.n, c = g_ctx.cfg.n_cvt;
@@ -104,29 +104,21 @@ extern "C" int gemma_hip_lmm_gxe_batch(int kind, const void *geno, size_t l, siz
   if (!g_ctx.lmm_active || !g_ctx.gxe_ready) return fail(GEMMA_HIP_ESTATE, "lmm_gxe_batch before lmm_setup + lmm_set_env");
   if (l == 0) return GEMMA_HIP_OK;
   if (kind == GEMMA_GENO_F64_IDV_MAJOR) return fail(GEMMA_HIP_EINVAL, "lmm_gxe_batch: SNP-major input only");
-  int rc = check_batch_args("lmm_gxe_batch", kind, geno, l, ld, out);
-  if (rc) return rc;
-  const size_t esz = (kind == GEMMA_GENO_PLINK_2BIT) ? 1 : 8;
-  if (g_ctx.stage_in.reserve(l * ld * esz) || g_ctx.stage_out.reserve(l * sizeof(gemma_sumstat)))
-    return fail(GEMMA_HIP_ENOMEM, "lmm_gxe_batch: staging %zu bytes", l * ld * esz);
-  HIPCHK(hipMemcpy(g_ctx.stage_in.p, geno, l * ld * esz, hipMemcpyHostToDevice));
-  rc = gemma_hip_lmm_gxe_batch_d(kind, g_ctx.stage_in.p, l, ld, g_ctx.stage_out.as<gemma_sumstat>(), nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(out, g_ctx.stage_out.p, l * sizeof(gemma_sumstat), hipMemcpyDeviceToHost));
-  return GEMMA_HIP_OK;
+  return host_batch("lmm_gxe_batch", kind, geno, l, ld, g_ctx.stage_out, out, l * sizeof(gemma_sumstat),
+                    [&](const void *in_d, void *out_d) {
+                      return gemma_hip_lmm_gxe_batch_d(kind, in_d, l, ld, static_cast<gemma_sumstat *>(out_d), nullptr);
+                    });
 }
 
 extern "C" int gemma_hip_dbg_utx(int kind, const void *geno, size_t l, size_t ld, int path, double *UtX_host) {
   NEED_INIT();
   if (!g_ctx.lmm_active) return fail(GEMMA_HIP_ESTATE, "dbg_utx before lmm_setup");
   if (l == 0) return GEMMA_HIP_OK;
-  int rc = check_batch_args("dbg_utx", kind, geno, l, ld, UtX_host);
+  BlockGeom g;
+  int rc = block_geom("dbg_utx", kind, g_ctx.cfg.n, true, geno, l, ld, UtX_host, &g);
+  if (!rc) rc = stage_block("dbg_utx", g, geno, ld);
   if (rc) return rc;
   const size_t n = g_ctx.cfg.n;
-  const size_t rows = (kind == GEMMA_GENO_F64_IDV_MAJOR) ? n : l;
-  const size_t esz = (kind == GEMMA_GENO_PLINK_2BIT) ? 1 : 8;
-  if (g_ctx.stage_in.reserve(rows * ld * esz)) return fail(GEMMA_HIP_ENOMEM, "dbg_utx: staging");
-  HIPCHK(hipMemcpy(g_ctx.stage_in.p, geno, rows * ld * esz, hipMemcpyHostToDevice));
   double *UtX;
   size_t ldx;
   rc = compute_utx(kind, g_ctx.stage_in.p, l, ld, path ? 1 : 0, &UtX, &ldx, 0);
@@ -140,20 +132,10 @@ extern "C" int gemma_hip_lmm_batch(int kind, const void *geno, size_t l, size_t 
   if (!g_ctx.lmm_active) return fail(GEMMA_HIP_ESTATE, "lmm_batch before lmm_setup");
   NEED_SINGLE("lmm_batch");
   if (l == 0) return GEMMA_HIP_OK;
-  const size_t n = g_ctx.cfg.n;
-  const size_t per_row = (kind == GEMMA_GENO_PLINK_2BIT && g_ctx.have_map) ? g_ctx.ni_total : n;
-  const size_t need = min_ld_for(kind, per_row, l);
-  if (need == (size_t)-1) return fail(GEMMA_HIP_EINVAL, "lmm_batch: unknown geno_kind %d", kind);
-  if (!geno || !out || ld < need) return fail(GEMMA_HIP_EINVAL, "lmm_batch: ld=%zu < %zu", ld, need);
-  const size_t rows = (kind == GEMMA_GENO_F64_IDV_MAJOR) ? n : l;
-  const size_t esz = (kind == GEMMA_GENO_PLINK_2BIT) ? 1 : 8;
-  if (g_ctx.stage_in.reserve(rows * ld * esz) || g_ctx.stage_out.reserve(l * sizeof(gemma_sumstat)))
-    return fail(GEMMA_HIP_ENOMEM, "lmm_batch: staging %zu bytes", rows * ld * esz);
-  HIPCHK(hipMemcpy2D(g_ctx.stage_in.p, ld * esz, geno, ld * esz, need * esz, rows, hipMemcpyHostToDevice));
-  int rc = gemma_hip_lmm_batch_d(kind, g_ctx.stage_in.p, l, ld, g_ctx.stage_out.as<gemma_sumstat>(), nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(out, g_ctx.stage_out.p, l * sizeof(gemma_sumstat), hipMemcpyDeviceToHost));
-  return GEMMA_HIP_OK;
+  return host_batch("lmm_batch", kind, geno, l, ld, g_ctx.stage_out, out, l * sizeof(gemma_sumstat),
+                    [&](const void *in_d, void *out_d) {
+                      return gemma_hip_lmm_batch_d(kind, in_d, l, ld, static_cast<gemma_sumstat *>(out_d), nullptr);
+                    });
 }
 
 // ------------------------------------------------------------------------------ linear model (-lm)
@@ -213,33 +195,12 @@ extern "C" int gemma_hip_lm_batch_d(int kind, const void *geno, size_t l, size_t
   if (!g_ctx.lm_active) return fail(GEMMA_HIP_ESTATE, "lm_batch before lm_setup");
   if (l == 0) return GEMMA_HIP_OK;
   const size_t n = g_ctx.cfg.n;
-  const size_t per_row = (kind == GEMMA_GENO_PLINK_2BIT && g_ctx.have_map) ? g_ctx.ni_total : n;
-  const size_t need = min_ld_for(kind, per_row, l);
-  if (need == (size_t)-1) return fail(GEMMA_HIP_EINVAL, "lm_batch: unknown geno_kind %d", kind);
-  if (!geno || !out_d || ld < need) return fail(GEMMA_HIP_EINVAL, "lm_batch: ld=%zu < %zu", ld, need);
+  if (int rc = block_geom("lm_batch", kind, n, true, geno, l, ld, out_d)) return rc;
   hipStream_t s = S(stream);
   const size_t ldx = (n + 1) & ~(size_t)1;
   if (g_ctx.X.reserve(l * ldx * 8)) return fail(GEMMA_HIP_ENOMEM, "lm_batch: cannot allocate %zu bytes", l * ldx * 8);
   double *X = g_ctx.X.as<double>();
-  {
-    ProfScope ps(GEMMA_STAGE_INGEST, s);
-    if (kind == GEMMA_GENO_F64_IDV_MAJOR) {
-      dim3 grid((unsigned)((l + 31) / 32), (unsigned)((n + 31) / 32));
-      hipLaunchKernelGGL(transpose_kernel, grid, dim3(32, 8), 0, s, reinterpret_cast<const double *>(geno), (long)n,
-                         (long)l, (long)ld, X, (long)ldx);
-    } else {
-      IngestArgs a;
-      a.src = geno; a.ld = (long)ld; a.l = (long)l;
-      a.idx_map = g_ctx.have_map ? g_ctx.idx_map.as<int>() : nullptr;
-      a.n = (int)n; a.dst = X; a.ldo = (long)ldx; a.k_mode = 0;
-      const unsigned grid = (unsigned)((l + 3) / 4);
-      if (kind == GEMMA_GENO_PLINK_2BIT)
-        hipLaunchKernelGGL(ingest_lmm_kernel<true>, dim3(grid), dim3(256), 0, s, a);
-      else
-        hipLaunchKernelGGL(ingest_lmm_kernel<false>, dim3(grid), dim3(256), 0, s, a);
-    }
-    HIPCHK(hipGetLastError());
-  }
+  if (int rc = ingest_f64(kind, geno, l, ld, X, ldx, s)) return rc;
   LmArgs a = g_ctx.lm_proto;
   a.X = X; a.ld = (long)ldx; a.l = (long)l;
   a.out = reinterpret_cast<SumStat *>(out_d);
@@ -255,29 +216,24 @@ extern "C" int gemma_hip_lm_batch(int kind, const void *geno, size_t l, size_t l
   NEED_INIT();
   if (!g_ctx.lm_active) return fail(GEMMA_HIP_ESTATE, "lm_batch before lm_setup");
   if (l == 0) return GEMMA_HIP_OK;
-  const size_t n = g_ctx.cfg.n;
-  const size_t per_row = (kind == GEMMA_GENO_PLINK_2BIT && g_ctx.have_map) ? g_ctx.ni_total : n;
-  const size_t need = min_ld_for(kind, per_row, l);
-  if (need == (size_t)-1) return fail(GEMMA_HIP_EINVAL, "lm_batch: unknown geno_kind %d", kind);
-  if (!geno || !out || ld < need) return fail(GEMMA_HIP_EINVAL, "lm_batch: ld=%zu < %zu", ld, need);
-  const size_t rows = (kind == GEMMA_GENO_F64_IDV_MAJOR) ? n : l;
-  const size_t esz = (kind == GEMMA_GENO_PLINK_2BIT) ? 1 : 8;
-  if (g_ctx.stage_in.reserve(rows * ld * esz) || g_ctx.stage_out.reserve(l * sizeof(gemma_sumstat)))
-    return fail(GEMMA_HIP_ENOMEM, "lm_batch: staging %zu bytes", rows * ld * esz);
-  HIPCHK(hipMemcpy2D(g_ctx.stage_in.p, ld * esz, geno, ld * esz, need * esz, rows, hipMemcpyHostToDevice));
-  int rc = gemma_hip_lm_batch_d(kind, g_ctx.stage_in.p, l, ld, g_ctx.stage_out.as<gemma_sumstat>(), nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(out, g_ctx.stage_out.p, l * sizeof(gemma_sumstat), hipMemcpyDeviceToHost));
-  return GEMMA_HIP_OK;
+  return host_batch("lm_batch", kind, geno, l, ld, g_ctx.stage_out, out, l * sizeof(gemma_sumstat),
+                    [&](const void *in_d, void *out_d) {
+                      return gemma_hip_lm_batch_d(kind, in_d, l, ld, static_cast<gemma_sumstat *>(out_d), nullptr);
+                    });
+}
+
+// everything the -lm state owns (X, the staging buffers and the indicator map it shares with the LMM state)
+static void lm_release() {
+  g_ctx.lm_Wt.release(); g_ctx.lm_y.release(); g_ctx.lm_small.release();
+  g_ctx.X.release(); g_ctx.stage_in.release(); g_ctx.stage_out.release(); g_ctx.idx_map.release();
+  g_ctx.lm_active = false;
 }
 
 extern "C" int gemma_hip_lm_finish(void) {
   NEED_INIT();
   if (!g_ctx.lm_active) return fail(GEMMA_HIP_ESTATE, "lm_finish before lm_setup");
   HIPCHK(hipDeviceSynchronize());
-  g_ctx.lm_Wt.release(); g_ctx.lm_y.release(); g_ctx.lm_small.release();
-  g_ctx.X.release(); g_ctx.stage_in.release(); g_ctx.stage_out.release(); g_ctx.idx_map.release();
-  g_ctx.lm_active = false;
+  lm_release();
   return GEMMA_HIP_OK;
 }
 
@@ -360,29 +316,6 @@ extern "C" int gemma_hip_lmm_finish(double *time_UtX_min, double *time_opt_min) 
   if (time_UtX_min)
     *time_UtX_min = (g_ctx.prof[GEMMA_STAGE_UTX_GEMM].acc_ms + g_ctx.prof[GEMMA_STAGE_UTX_POST].acc_ms) / 60000.0;
   if (time_opt_min) *time_opt_min = g_ctx.prof[GEMMA_STAGE_ASSOC].acc_ms / 60000.0;
-  g_ctx.own_U.release(); g_ctx.own_eval.release(); g_ctx.own_Uty.release(); g_ctx.own_UtW.release();
-  g_ctx.UtWt.release(); g_ctx.idx_map.release(); g_ctx.X.release(); g_ctx.UtX.release();
-  g_ctx.stage_in.release(); g_ctx.stage_out.release();
-  g_ctx.grid_R.release(); g_ctx.grid_F.release(); g_ctx.grid_T.release();
-  g_ctx.table_P.release();
-  g_ctx.cheb_R.release(); g_ctx.cheb_F.release(); g_ctx.cheb_T.release(); g_ctx.cheb_slots.release();
-  g_ctx.cheb_list.release(); g_ctx.cheb_count.release(); g_ctx.cheb_D.release(); g_ctx.cheb_Ck.release();
-  g_ctx.cheb_Gk.release(); g_ctx.cheb_Lk.release(); g_ctx.cheb_iv.release(); g_ctx.cheb_dends.release(); g_ctx.cheb_res.release();
-  g_ctx.i8_Bt.release(); g_ctx.i8_q.release(); g_ctx.i8_qinv.release(); g_ctx.i8_cmax.release(); g_ctx.i8_A.release(); g_ctx.i8_C.release();
-  raster_release();
-  g_ctx.i8_mean.release(); g_ctx.i8_meta.release(); g_ctx.i8_rowsur.release(); g_ctx.i8_colsum.release(); g_ctx.i8_surlist.release();
-  g_ctx.i8_ready = false;
-  g_ctx.i8_colsum_ready = false;
-  g_ctx.gxe_env.release(); g_ctx.gxe_UtWt.release(); g_ctx.gxe_Z.release(); g_ctx.gxe_UtZ.release();
-  g_ctx.mv_Yt.release(); g_ctx.mv_out.release(); g_ctx.mv_scratch.release();
-  g_ctx.mv_ready = g_ctx.mv_gxe = false;
-  g_ctx.gxe_flip.release();
-  g_ctx.gxe_ready = false;
-  multi_release();
-  score_release();
-  g_ctx.U = g_ctx.eval = g_ctx.Uty = nullptr;
-  g_ctx.U_even_of = nullptr;
-  g_ctx.U_even.release();
-  g_ctx.lmm_active = false;
+  lmm_release();
   return GEMMA_HIP_OK;
 }

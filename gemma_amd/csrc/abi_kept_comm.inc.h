@@ -1,6 +1,7 @@
 // Part of gemma_hip.hip (ONE translation unit: the parts share the context g_ctx and the helpers of its anonymous namespace, and are
 // included there in this order; round 6: the 3 500-line file cut along its stages for reading -- no behaviour change).
-// This part: device-resident chain (kin_end_keep -> eigh_kept_K -> lmm_setup_kept), pinned host-block pipeline, the communicator, diagnostics.
+// This part: device-resident chain (kin_end_keep -> eigh_kept_K -> lmm_setup_kept: single_setup of abi_lmm_stage.inc.h on the kept U), pinned
+// host-block pipeline (its own buffers, streams and events; the geometry from block_geom), the communicator, diagnostics.
 
 // ------------------------------------------------------------------------------ device-resident chain
 namespace {
@@ -9,8 +10,6 @@ __global__ void subselect_kernel(const double *__restrict__ K, long ni_total, co
   const long c = (long)blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
   if (c < n) G[r * n + c] = K[(long)map[r] * ni_total + map[c]];
 }
-double *kept_U() { return g_ctx.kept_UE.as<double>(); }
-double *kept_eval() { return g_ctx.kept_UE.as<double>() + g_ctx.kept_n * g_ctx.kept_n; }
 } // namespace
 
 extern "C" int gemma_hip_kin_end_keep(size_t *ns_used, int allreduce) {
@@ -45,9 +44,7 @@ extern "C" int gemma_hip_kin_end_keep(size_t *ns_used, int allreduce) {
   g_ctx.kept_K = g_ctx.kin_K; // ownership moves: K stays where the SYRK left it
   g_ctx.kin_K = DevBuf();
   g_ctx.kept_K_n = n;
-  g_ctx.kin_active = false;
-  g_ctx.kin_X.release();
-  g_ctx.kin_stage.release();
+  kin_release();
   return GEMMA_HIP_OK;
 }
 
@@ -204,21 +201,7 @@ extern "C" int gemma_hip_lmm_setup_kept(const gemma_lmm_cfg *cfg, const double *
   if (!g_ctx.kept_n) return fail(GEMMA_HIP_ESTATE, "lmm_setup_kept: no kept U");
   if (!cfg || !UtW || !Uty) return fail(GEMMA_HIP_EINVAL, "lmm_setup_kept: null pointer");
   if (cfg->n != g_ctx.kept_n) return fail(GEMMA_HIP_EINVAL, "lmm_setup_kept: cfg.n=%zu, kept U is %zu", cfg->n, g_ctx.kept_n);
-  int rc = lmm_common_setup(cfg);
-  if (rc) return rc;
-  const size_t n = cfg->n, c = cfg->n_cvt;
-  if (g_ctx.own_Uty.reserve(n * 8) || g_ctx.own_UtW.reserve(n * c * 8)) return fail(GEMMA_HIP_ENOMEM, "lmm_setup_kept");
-  HIPCHK(hipMemcpy(g_ctx.own_Uty.p, Uty, n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(g_ctx.own_UtW.p, UtW, n * c * 8, hipMemcpyHostToDevice));
-  g_ctx.U = kept_U();
-  g_ctx.U_even_of = nullptr;
-  g_ctx.eval = kept_eval();
-  g_ctx.Uty = g_ctx.own_Uty.as<double>();
-  rc = make_utwt(g_ctx.own_UtW.as<double>(), 0);
-  if (rc) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  g_ctx.lmm_active = true;
-  return GEMMA_HIP_OK;
+  return single_setup("lmm_setup_kept", SetupSrc::Kept, cfg, nullptr, nullptr, UtW, Uty, nullptr);
 }
 
 // ---- pipelined host blocks --------------------------------------------------------------------------------------
@@ -246,8 +229,8 @@ extern "C" int gemma_hip_lmm_batch_submit(int kind, const void *geno, size_t l, 
   NEED_SINGLE("lmm_batch_submit");
   if (g_ctx.pipe_count >= 2) return fail(GEMMA_HIP_ESTATE, "lmm_batch_submit: two blocks already in flight (collect first)");
   if (l == 0) return fail(GEMMA_HIP_EINVAL, "lmm_batch_submit: empty block");
-  int dummy = 0;
-  int rc = check_batch_args("lmm_batch_submit", kind, geno, l, ld, &dummy);
+  BlockGeom g;
+  int rc = block_geom("lmm_batch_submit", kind, g_ctx.cfg.n, true, geno, l, ld, geno, &g); // the output is the collect call's
   if (rc) return rc;
   if (!g_ctx.pipe_copy) {
     HIPCHK(hipStreamCreateWithFlags(&g_ctx.pipe_copy, hipStreamNonBlocking));
@@ -255,12 +238,8 @@ extern "C" int gemma_hip_lmm_batch_submit(int kind, const void *geno, size_t l, 
   }
   const int slot = (g_ctx.pipe_head + g_ctx.pipe_count) & 1;
   Ctx::PipeSlot &p = g_ctx.pipe[slot];
-  const size_t esz = (kind == GEMMA_GENO_PLINK_2BIT) ? 1 : 8;
-  const size_t rows = (kind == GEMMA_GENO_F64_IDV_MAJOR) ? g_ctx.cfg.n : l;
-  const size_t n = g_ctx.cfg.n;
-  const size_t per_row = (kind == GEMMA_GENO_PLINK_2BIT && g_ctx.have_map) ? g_ctx.ni_total : n;
-  const size_t need = min_ld_for(kind, per_row, l);
-  const size_t bytes = ((rows - 1) * ld + need) * esz; // the last row may be shorter than ld in the caller's buffer
+  const size_t rows = g.rows, esz = g.esz;
+  const size_t bytes = ((rows - 1) * ld + g.need) * esz; // the last row may be shorter than ld in the caller's buffer
   if (p.pin_in_cap < rows * ld * esz) {
     if (p.pin_in) (void)hipHostFree(p.pin_in);
     p.pin_in = nullptr;

@@ -1,6 +1,7 @@
 // Part of gemma_hip.hip (ONE translation unit: the parts share the context g_ctx and the helpers of its anonymous namespace, and are
 // included there in this order; round 6: the 3 500-line file cut along its stages for reading -- no behaviour change).
-// This part: kinship: PARAM::CalcKin -> BimbamKin / PlinkKin (gemma_hip_kin_begin / kin_add / kin_end), the exact-integer path of hard calls.
+// This part: kinship: PARAM::CalcKin -> BimbamKin / PlinkKin (gemma_hip_kin_begin / kin_add / kin_end), the exact-integer path of hard calls,
+// the release list of the kinship state (kin_release).  Blocks are checked by block_geom (abi_host_block.inc.h).
 
 // ------------------------------------------------------------------------------ kinship
 extern "C" int gemma_hip_kin_begin(size_t n_total, int k_mode) {
@@ -31,6 +32,13 @@ static void kin_i8_release() {
   g_ctx.kin_tmap.release();
   g_ctx.kin_tmap_tm = g_ctx.kin_tmap_tn = g_ctx.kin_tmap_count = 0;
   g_ctx.kin_i8_used = false;
+}
+
+// everything the kinship state owns (the upload stream and its events stay until shutdown)
+static void kin_release() {
+  g_ctx.kin_K.release(); g_ctx.kin_X.release(); g_ctx.kin_stage.release();
+  kin_i8_release();
+  g_ctx.kin_active = false;
 }
 
 // (tile_m, tile_n) of the 128 x 256 tiles of G^T G that hold an entry with column >= row, in the order the kernel's raster
@@ -205,23 +213,12 @@ static int kin_fold_i8(hipStream_t s) {
   return GEMMA_HIP_OK;
 }
 
-static size_t min_ld_for(int kind, size_t n_items_per_row, size_t l) {
-  switch (kind) {
-  case GEMMA_GENO_F64_SNP_MAJOR: return n_items_per_row;
-  case GEMMA_GENO_PLINK_2BIT: return (n_items_per_row + 3) / 4;
-  case GEMMA_GENO_F64_IDV_MAJOR: return l;
-  default: return (size_t)-1;
-  }
-}
-
 extern "C" int gemma_hip_kin_add_d(int kind, const void *geno, size_t l, size_t ld, void *stream) {
   NEED_INIT();
   if (!g_ctx.kin_active) return fail(GEMMA_HIP_ESTATE, "kin_add before kin_begin");
   if (l == 0) return GEMMA_HIP_OK;
   const size_t n = g_ctx.kin_n;
-  const size_t need = min_ld_for(kind, n, l);
-  if (need == (size_t)-1) return fail(GEMMA_HIP_EINVAL, "kin_add: unknown geno_kind %d", kind);
-  if (!geno || ld < need) return fail(GEMMA_HIP_EINVAL, "kin_add: ld=%zu < %zu", ld, need);
+  if (int rc = block_geom("kin_add", kind, n, false, geno, l, ld, geno)) return rc;
   hipStream_t s = S(stream);
   if (g_ctx.kin_i8 && kind == GEMMA_GENO_PLINK_2BIT) return kin_add_i8(geno, l, ld, s);
   const size_t ldx = (n + 1) & ~(size_t)1;
@@ -264,17 +261,14 @@ extern "C" int gemma_hip_kin_add(int kind, const void *geno, size_t l, size_t ld
   NEED_INIT();
   if (!g_ctx.kin_active) return fail(GEMMA_HIP_ESTATE, "kin_add before kin_begin");
   if (l == 0) return GEMMA_HIP_OK;
-  const size_t n = g_ctx.kin_n;
-  const size_t need = min_ld_for(kind, n, l);
-  if (need == (size_t)-1) return fail(GEMMA_HIP_EINVAL, "kin_add: unknown geno_kind %d", kind);
-  if (!geno || ld < need) return fail(GEMMA_HIP_EINVAL, "kin_add: ld=%zu < %zu", ld, need);
-  const size_t rows = (kind == GEMMA_GENO_F64_IDV_MAJOR) ? n : l;
-  const size_t esz = (kind == GEMMA_GENO_PLINK_2BIT) ? 1 : 8;
+  BlockGeom g;
+  if (int rc = block_geom("kin_add", kind, g_ctx.kin_n, false, geno, l, ld, geno, &g)) return rc;
+  const size_t rows = g.rows, esz = g.esz;
   const size_t bytes = rows * ld * esz;
   if (bytes > g_ctx.kin_stage.cap) g_ctx.kin_ingested_valid = false; // (the hipFree inside reserve waits for the device)
   if (g_ctx.kin_stage.reserve(bytes)) return fail(GEMMA_HIP_ENOMEM, "kin_add: staging %zu bytes", bytes);
   // last row may be shorter than ld in the caller's buffer
-  const size_t width = need * esz;
+  const size_t width = g.need * esz;
   if (!g_ctx.kin_copy) { // created once; without it the upload stays on the null stream (behind the previous block's kernels)
     if (hipStreamCreateWithFlags(&g_ctx.kin_copy, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&g_ctx.kin_copied, hipEventDisableTiming) != hipSuccess ||
@@ -318,10 +312,7 @@ extern "C" int gemma_hip_kin_end_d(double *K_d, size_t *ns_used, void *stream) {
   HIPCHK(hipGetLastError());
   if (K_d) HIPCHK(hipMemcpyAsync(K_d, g_ctx.kin_K.p, n * n * 8, hipMemcpyDeviceToDevice, s));
   HIPCHK(hipStreamSynchronize(s));
-  g_ctx.kin_active = false;
-  g_ctx.kin_X.release();
-  g_ctx.kin_stage.release();
-  g_ctx.kin_K.release();
+  kin_release();
   return GEMMA_HIP_OK;
 }
 
@@ -340,9 +331,6 @@ extern "C" int gemma_hip_kin_end(double *K, size_t *ns_used) {
                      (long)n, (long)n, scale);
   HIPCHK(hipGetLastError());
   if (K) HIPCHK(hipMemcpy(K, g_ctx.kin_K.p, n * n * 8, hipMemcpyDeviceToHost));
-  g_ctx.kin_active = false;
-  g_ctx.kin_X.release();
-  g_ctx.kin_stage.release();
-  g_ctx.kin_K.release();
+  kin_release();
   return GEMMA_HIP_OK;
 }

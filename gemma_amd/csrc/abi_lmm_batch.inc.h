@@ -1,6 +1,6 @@
 // Part of gemma_hip.hip (ONE translation unit: the parts share the context g_ctx and the helpers of its anonymous namespace, and are
 // included there in this order; round 6: the 3 500-line file cut along its stages for reading -- no behaviour change).
-// This part: batch entry points: the two-block pipeline, gemma_hip_lmm_batch_d, -gene.
+// This part: batch entry points: the fp64 ingest (ingest_f64), compute_utx, the two-block pipeline, gemma_hip_lmm_batch_d, -gene.
 
 // ---- stream / buffer plumbing of gemma_hip_lmm_batch_pipe_d (the two-block pipeline, described where that entry point is defined)
 static void xp_release() {
@@ -89,6 +89,30 @@ static void xp_swap_sets() {
 }
 
 
+// The fp64 rows of a block, SNP-major and mean-imputed (X: l x ldx): the transpose of individual-major input (the reference's Xlarge,
+// already imputed), ingest_lmm_kernel for the two SNP-major kinds.  compute_utx and the linear model.
+static int ingest_f64(int kind, const void *geno, size_t l, size_t ld, double *X, size_t ldx, hipStream_t s) {
+  const size_t n = g_ctx.cfg.n;
+  ProfScope ps(GEMMA_STAGE_INGEST, s);
+  if (kind == GEMMA_GENO_F64_IDV_MAJOR) {
+    dim3 grid((unsigned)((l + 31) / 32), (unsigned)((n + 31) / 32));
+    hipLaunchKernelGGL(transpose_kernel, grid, dim3(32, 8), 0, s, reinterpret_cast<const double *>(geno), (long)n, (long)l, (long)ld,
+                       X, (long)ldx);
+  } else {
+    IngestArgs a;
+    a.src = geno; a.ld = (long)ld; a.l = (long)l;
+    a.idx_map = g_ctx.have_map ? g_ctx.idx_map.as<int>() : nullptr;
+    a.n = (int)n; a.dst = X; a.ldo = (long)ldx; a.k_mode = 0;
+    const unsigned grid = (unsigned)((l + 3) / 4);
+    if (kind == GEMMA_GENO_PLINK_2BIT)
+      hipLaunchKernelGGL(ingest_lmm_kernel<true>, dim3(grid), dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL(ingest_lmm_kernel<false>, dim3(grid), dim3(256), 0, s, a);
+  }
+  HIPCHK(hipGetLastError());
+  return GEMMA_HIP_OK;
+}
+
 // UtX (l x ldx, SNP-major) = mean-imputed X (l x n) * U (n x n): row s is (U^T x_s)^T, i.e. the column the
 // reference's fast_dgemm("T","N",U,Xlarge) (src/lmm.cpp:1521) produces for SNP s.  path < 0: by GEMMA_HIP_UTX_I8.
 static int compute_utx(int kind, const void *geno, size_t l, size_t ld, int path, double **UtX_out, size_t *ldx_out,
@@ -111,13 +135,7 @@ static int compute_utx(int kind, const void *geno, size_t l, size_t ld, int path
   double *X = g_ctx.X.as<double>();
   bool done = false;
   if (kind == GEMMA_GENO_F64_IDV_MAJOR) {
-    { // the reference's Xlarge (individuals x SNPs, already mean-imputed) -> SNP-major
-      ProfScope ps(GEMMA_STAGE_INGEST, s);
-      dim3 grid((unsigned)((l + 31) / 32), (unsigned)((n + 31) / 32));
-      hipLaunchKernelGGL(transpose_kernel, grid, dim3(32, 8), 0, s, reinterpret_cast<const double *>(geno),
-                         (long)n, (long)l, (long)ld, X, (long)ldx);
-      HIPCHK(hipGetLastError());
-    }
+    if (int rc = ingest_f64(kind, geno, l, ld, X, ldx, s)) return rc; // Xlarge -> SNP-major
     if (want_i8) { // hard calls with one imputed value per SNP take the exact int8-digit product as well
       int rc = utx_f64_try_i8(X, l, ldx, false, UtX, ldx, s, &done);
       if (rc) return rc;
@@ -127,19 +145,8 @@ static int compute_utx(int kind, const void *geno, size_t l, size_t ld, int path
     if (rc) return rc;
   }
   if (done) return GEMMA_HIP_OK;
-  if (kind != GEMMA_GENO_F64_IDV_MAJOR) {
-    ProfScope ps(GEMMA_STAGE_INGEST, s);
-    IngestArgs a;
-    a.src = geno; a.ld = (long)ld; a.l = (long)l;
-    a.idx_map = g_ctx.have_map ? g_ctx.idx_map.as<int>() : nullptr;
-    a.n = (int)n; a.dst = X; a.ldo = (long)ldx; a.k_mode = 0;
-    const unsigned grid = (unsigned)((l + 3) / 4);
-    if (kind == GEMMA_GENO_PLINK_2BIT)
-      hipLaunchKernelGGL(ingest_lmm_kernel<true>, dim3(grid), dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL(ingest_lmm_kernel<false>, dim3(grid), dim3(256), 0, s, a);
-    HIPCHK(hipGetLastError());
-  }
+  if (kind != GEMMA_GENO_F64_IDV_MAJOR)
+    if (int rc = ingest_f64(kind, geno, l, ld, X, ldx, s)) return rc;
   {
     ProfScope ps(GEMMA_STAGE_UTX_GEMM, s);
     const double *Ug;
@@ -150,15 +157,6 @@ static int compute_utx(int kind, const void *geno, size_t l, size_t ld, int path
     HIPCHK(launch_dgemm('N', 'N', (long)l, (long)n, (long)n, 1.0, X, (long)ldx, Ug, ldu, 0.0, UtX,
                         (long)ldx, false, false, s));
   }
-  return GEMMA_HIP_OK;
-}
-
-static int check_batch_args(const char *who, int kind, const void *geno, size_t l, size_t ld, const void *out) {
-  const size_t n = g_ctx.cfg.n;
-  const size_t per_row = (kind == GEMMA_GENO_PLINK_2BIT && g_ctx.have_map) ? g_ctx.ni_total : n;
-  const size_t need = min_ld_for(kind, per_row, l);
-  if (need == (size_t)-1) return fail(GEMMA_HIP_EINVAL, "%s: unknown geno_kind %d", who, kind);
-  if (!geno || !out || ld < need) return fail(GEMMA_HIP_EINVAL, "%s: ld=%zu < %zu", who, ld, need);
   return GEMMA_HIP_OK;
 }
 
@@ -251,7 +249,7 @@ extern "C" int gemma_hip_lmm_batch_pipe_d(int kind, const void *geno, size_t l, 
   if (!g_ctx.lmm_active) return fail(GEMMA_HIP_ESTATE, "lmm_batch_pipe before lmm_setup");
   NEED_SINGLE("lmm_batch_pipe");
   if (l == 0) return GEMMA_HIP_OK;
-  int rc = check_batch_args("lmm_batch_pipe", kind, geno, l, ld, out_d);
+  int rc = block_geom("lmm_batch_pipe", kind, g_ctx.cfg.n, true, geno, l, ld, out_d);
   if (rc) return rc;
   hipStream_t s = S(stream);
   if (kind != GEMMA_GENO_PLINK_2BIT || utx_i8_mode() != 1 || i8_sparse_mode() != 2) {
@@ -312,7 +310,7 @@ extern "C" int gemma_hip_lmm_batch_d(int kind, const void *geno, size_t l, size_
   if (!g_ctx.lmm_active) return fail(GEMMA_HIP_ESTATE, "lmm_batch before lmm_setup");
   NEED_SINGLE("lmm_batch");
   if (l == 0) return GEMMA_HIP_OK;
-  int rc = check_batch_args("lmm_batch", kind, geno, l, ld, out_d);
+  int rc = block_geom("lmm_batch", kind, g_ctx.cfg.n, true, geno, l, ld, out_d);
   if (rc) return rc;
   hipStream_t s = S(stream);
   if ((rc = xp_flush(s))) return rc; // blocks of gemma_hip_lmm_batch_pipe_d still in flight share this call's buffers
@@ -386,11 +384,8 @@ extern "C" int gemma_hip_lmm_gene_batch(const double *Y, size_t l, size_t ld, ge
   if (l == 0) return GEMMA_HIP_OK;
   const size_t n = g_ctx.cfg.n;
   if (!Y || !out || ld < n) return fail(GEMMA_HIP_EINVAL, "lmm_gene_batch: ld=%zu < n=%zu", ld, n);
-  if (g_ctx.stage_in.reserve(l * ld * 8) || g_ctx.stage_out.reserve(l * sizeof(gemma_sumstat)))
-    return fail(GEMMA_HIP_ENOMEM, "lmm_gene_batch: staging %zu bytes", l * ld * 8);
-  HIPCHK(hipMemcpy(g_ctx.stage_in.p, Y, l * ld * 8, hipMemcpyHostToDevice));
-  int rc = gemma_hip_lmm_gene_batch_d(g_ctx.stage_in.as<double>(), l, ld, g_ctx.stage_out.as<gemma_sumstat>(), nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(out, g_ctx.stage_out.p, l * sizeof(gemma_sumstat), hipMemcpyDeviceToHost));
-  return GEMMA_HIP_OK;
+  return host_block("lmm_gene_batch", BlockGeom{n, l, 8}, Y, ld, g_ctx.stage_out, out, l * sizeof(gemma_sumstat), // l rows of n doubles
+                    [&](const void *in_d, void *out_d) {
+                      return gemma_hip_lmm_gene_batch_d(static_cast<const double *>(in_d), l, ld, static_cast<gemma_sumstat *>(out_d), nullptr);
+                    });
 }

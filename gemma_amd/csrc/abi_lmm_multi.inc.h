@@ -8,6 +8,8 @@
 // phenotype in nq of its columns only: table_v2_kernel on the weight matrix of a group of multi_G phenotypes and
 // table_multi_reduce_kernel (lmm_grid.hip.h) give the group's tables from one read, bit for bit the tables launch_grid_table
 // gives (GEMMA_HIP_MULTI_TABLE=0: every phenotype computes its own).
+// The three setups are multi_setup: lmm_bind (abi_lmm_stage.inc.h) for U, eval, UtW and U^T Y, then multi_setup_slots; the host form
+// of a block is host_batch (abi_host_block.inc.h).
 
 // weight matrices of the shared table, one per group of multi_G phenotypes; needs the slots' Uty and the setup's UtWt / eval
 static int multi_make_weights(hipStream_t s) {
@@ -37,7 +39,7 @@ static int multi_make_weights(hipStream_t s) {
   return GEMMA_HIP_OK;
 }
 
-// After lmm_common_setup(cfg) with g_ctx.U / g_ctx.eval in place.  UtW_d: n x c, UtY_d: n x T row-major, both on the device.
+// After lmm_bind: g_ctx.U / g_ctx.eval in place.  UtW_d: n x c, UtY_d: n x T row-major, both on the device.
 static int multi_setup_slots(size_t T, const double *l_mle_null, const double *logl_mle_H0, const double *UtW_d,
                              const double *UtY_d, hipStream_t s) {
   const size_t n = g_ctx.cfg.n;
@@ -82,10 +84,20 @@ static int multi_check(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_n
     return fail(GEMMA_HIP_EINVAL, "lmm_multi_setup: a_mode %d needs l_mle_null and logl_mle_H0 of every phenotype", cfg->a_mode);
   return GEMMA_HIP_OK;
 }
-// a failed setup leaves no slots behind (lmm_active is already false)
-static int multi_fail(int rc) {
-  multi_release();
-  return rc;
+// the three multi setups after their argument checks (lmm_bind: a failed setup leaves lmm_active false) -- and no slots behind
+static int multi_setup(const char *who, SetupSrc src, const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null,
+                       const double *logl_mle_H0, const double *U, const double *eval, const double *UtW, const double *UtY,
+                       hipStream_t s) {
+  const double *UtW_d, *UtY_d;
+  int rc = lmm_bind(who, src, cfg, U, eval, UtW, UtY, T, &UtW_d, &UtY_d);
+  if (rc) return rc;
+  if ((rc = multi_setup_slots(T, l_mle_null, logl_mle_H0, UtW_d, UtY_d, s))) {
+    multi_release();
+    return rc;
+  }
+  if (src != SetupSrc::Device) HIPCHK(hipDeviceSynchronize());
+  g_ctx.lmm_active = true;
+  return GEMMA_HIP_OK;
 }
 
 extern "C" int gemma_hip_lmm_multi_setup_d(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null,
@@ -93,42 +105,16 @@ extern "C" int gemma_hip_lmm_multi_setup_d(const gemma_lmm_cfg *cfg, size_t T, c
                                            const double *UtW_d, const double *UtY_d, void *stream) {
   NEED_INIT();
   if (!U_d || !eval_d || !UtW_d || !UtY_d) return fail(GEMMA_HIP_EINVAL, "lmm_multi_setup: null pointer");
-  int rc = multi_check(cfg, T, l_mle_null, logl_mle_H0);
-  if (rc) return rc;
-  if ((rc = lmm_common_setup(cfg))) return rc;
-  g_ctx.lmm_active = false; // a failed setup leaves no state behind
-  g_ctx.U = U_d;
-  g_ctx.U_even_of = nullptr;
-  g_ctx.eval = eval_d;
-  if ((rc = multi_setup_slots(T, l_mle_null, logl_mle_H0, UtW_d, UtY_d, S(stream)))) return multi_fail(rc);
-  g_ctx.lmm_active = true;
-  return GEMMA_HIP_OK;
+  if (int rc = multi_check(cfg, T, l_mle_null, logl_mle_H0)) return rc;
+  return multi_setup("lmm_multi_setup", SetupSrc::Device, cfg, T, l_mle_null, logl_mle_H0, U_d, eval_d, UtW_d, UtY_d, S(stream));
 }
 
 extern "C" int gemma_hip_lmm_multi_setup(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null, const double *logl_mle_H0,
                                          const double *U, const double *eval, const double *UtW, const double *UtY) {
   NEED_INIT();
   if (!U || !eval || !UtW || !UtY) return fail(GEMMA_HIP_EINVAL, "lmm_multi_setup: null pointer");
-  int rc = multi_check(cfg, T, l_mle_null, logl_mle_H0);
-  if (rc) return rc;
-  if ((rc = lmm_common_setup(cfg))) return rc;
-  g_ctx.lmm_active = false;
-  const size_t n = cfg->n, c = cfg->n_cvt;
-  if (g_ctx.own_U.reserve(n * n * 8) || g_ctx.own_eval.reserve(n * 8) || g_ctx.own_Uty.reserve(n * T * 8) ||
-      g_ctx.own_UtW.reserve(n * c * 8))
-    return fail(GEMMA_HIP_ENOMEM, "lmm_multi_setup: cannot allocate U (%zu bytes)", n * n * 8);
-  HIPCHK(hipMemcpy(g_ctx.own_U.p, U, n * n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(g_ctx.own_eval.p, eval, n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(g_ctx.own_Uty.p, UtY, n * T * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(g_ctx.own_UtW.p, UtW, n * c * 8, hipMemcpyHostToDevice));
-  g_ctx.U = g_ctx.own_U.as<double>();
-  g_ctx.U_even_of = nullptr;
-  g_ctx.eval = g_ctx.own_eval.as<double>();
-  if ((rc = multi_setup_slots(T, l_mle_null, logl_mle_H0, g_ctx.own_UtW.as<double>(), g_ctx.own_Uty.as<double>(), 0)))
-    return multi_fail(rc);
-  HIPCHK(hipDeviceSynchronize());
-  g_ctx.lmm_active = true;
-  return GEMMA_HIP_OK;
+  if (int rc = multi_check(cfg, T, l_mle_null, logl_mle_H0)) return rc;
+  return multi_setup("lmm_multi_setup", SetupSrc::Host, cfg, T, l_mle_null, logl_mle_H0, U, eval, UtW, UtY, nullptr);
 }
 
 extern "C" int gemma_hip_lmm_multi_setup_kept(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null,
@@ -136,24 +122,10 @@ extern "C" int gemma_hip_lmm_multi_setup_kept(const gemma_lmm_cfg *cfg, size_t T
   NEED_INIT();
   if (!g_ctx.kept_n) return fail(GEMMA_HIP_ESTATE, "lmm_multi_setup_kept: no kept U");
   if (!UtW || !UtY) return fail(GEMMA_HIP_EINVAL, "lmm_multi_setup_kept: null pointer");
-  int rc = multi_check(cfg, T, l_mle_null, logl_mle_H0);
-  if (rc) return rc;
+  if (int rc = multi_check(cfg, T, l_mle_null, logl_mle_H0)) return rc;
   if (cfg->n != g_ctx.kept_n)
     return fail(GEMMA_HIP_EINVAL, "lmm_multi_setup_kept: cfg.n=%zu, kept U is %zu", cfg->n, g_ctx.kept_n);
-  if ((rc = lmm_common_setup(cfg))) return rc;
-  g_ctx.lmm_active = false;
-  const size_t n = cfg->n, c = cfg->n_cvt;
-  if (g_ctx.own_Uty.reserve(n * T * 8) || g_ctx.own_UtW.reserve(n * c * 8)) return fail(GEMMA_HIP_ENOMEM, "lmm_multi_setup_kept");
-  HIPCHK(hipMemcpy(g_ctx.own_Uty.p, UtY, n * T * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(g_ctx.own_UtW.p, UtW, n * c * 8, hipMemcpyHostToDevice));
-  g_ctx.U = kept_U();
-  g_ctx.U_even_of = nullptr;
-  g_ctx.eval = kept_eval();
-  if ((rc = multi_setup_slots(T, l_mle_null, logl_mle_H0, g_ctx.own_UtW.as<double>(), g_ctx.own_Uty.as<double>(), 0)))
-    return multi_fail(rc);
-  HIPCHK(hipDeviceSynchronize());
-  g_ctx.lmm_active = true;
-  return GEMMA_HIP_OK;
+  return multi_setup("lmm_multi_setup_kept", SetupSrc::Kept, cfg, T, l_mle_null, logl_mle_H0, nullptr, nullptr, UtW, UtY, nullptr);
 }
 
 // the tables of group grp (Gn phenotypes) for the l rows of UtX -> multi_T_buf, Gn tables of l * grid_ld doubles
@@ -189,7 +161,7 @@ extern "C" int gemma_hip_lmm_multi_batch_d(int kind, const void *geno, size_t l,
   NEED_INIT();
   if (!g_ctx.lmm_active || !g_ctx.multi_T) return fail(GEMMA_HIP_ESTATE, "lmm_multi_batch before lmm_multi_setup");
   if (l == 0) return GEMMA_HIP_OK;
-  int rc = check_batch_args("lmm_multi_batch", kind, geno, l, ld, out_d);
+  int rc = block_geom("lmm_multi_batch", kind, g_ctx.cfg.n, true, geno, l, ld, out_d);
   if (rc) return rc;
   hipStream_t s = S(stream);
   double *UtX;
@@ -223,18 +195,8 @@ extern "C" int gemma_hip_lmm_multi_batch(int kind, const void *geno, size_t l, s
   NEED_INIT();
   if (!g_ctx.lmm_active || !g_ctx.multi_T) return fail(GEMMA_HIP_ESTATE, "lmm_multi_batch before lmm_multi_setup");
   if (l == 0) return GEMMA_HIP_OK;
-  const size_t n = g_ctx.cfg.n, T = g_ctx.multi_T;
-  const size_t per_row = (kind == GEMMA_GENO_PLINK_2BIT && g_ctx.have_map) ? g_ctx.ni_total : n;
-  const size_t need = min_ld_for(kind, per_row, l);
-  if (need == (size_t)-1) return fail(GEMMA_HIP_EINVAL, "lmm_multi_batch: unknown geno_kind %d", kind);
-  if (!geno || !out || ld < need) return fail(GEMMA_HIP_EINVAL, "lmm_multi_batch: ld=%zu < %zu", ld, need);
-  const size_t rows = (kind == GEMMA_GENO_F64_IDV_MAJOR) ? n : l;
-  const size_t esz = (kind == GEMMA_GENO_PLINK_2BIT) ? 1 : 8;
-  if (g_ctx.stage_in.reserve(rows * ld * esz) || g_ctx.stage_out.reserve(T * l * sizeof(gemma_sumstat)))
-    return fail(GEMMA_HIP_ENOMEM, "lmm_multi_batch: staging %zu bytes", rows * ld * esz + T * l * sizeof(gemma_sumstat));
-  HIPCHK(hipMemcpy2D(g_ctx.stage_in.p, ld * esz, geno, ld * esz, need * esz, rows, hipMemcpyHostToDevice));
-  int rc = gemma_hip_lmm_multi_batch_d(kind, g_ctx.stage_in.p, l, ld, g_ctx.stage_out.as<gemma_sumstat>(), nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(out, g_ctx.stage_out.p, T * l * sizeof(gemma_sumstat), hipMemcpyDeviceToHost));
-  return GEMMA_HIP_OK;
+  return host_batch("lmm_multi_batch", kind, geno, l, ld, g_ctx.stage_out, out, g_ctx.multi_T * l * sizeof(gemma_sumstat),
+                    [&](const void *in_d, void *out_d) {
+                      return gemma_hip_lmm_multi_batch_d(kind, in_d, l, ld, static_cast<gemma_sumstat *>(out_d), nullptr);
+                    });
 }

@@ -5,6 +5,8 @@
 // the closed form of CalcRLScore at the phenotype's null lambda (score_setup_kernel, lmm_score_panel.hip.h) -- n (c + 2) doubles
 // per phenotype, no lambda-search tables -- and a block is compute_utx as every batch entry point runs it followed by ONE product
 // kernel with the statistics in its epilogue (score_panel_kernel).
+// The three setups are score_setup: lmm_bind (abi_lmm_stage.inc.h) for U, eval, UtW and U^T Y, then score_setup_dev; the host forms
+// of a block stage it with host_batch / stage_block (abi_host_block.inc.h).
 
 static int score_check(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null) {
   if (!cfg) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup: null cfg");
@@ -17,12 +19,7 @@ static int score_check(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_n
   if (!l_mle_null) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup: l_mle_null of every phenotype is needed");
   return GEMMA_HIP_OK;
 }
-static int score_fail(int rc) {
-  score_release();
-  return rc;
-}
-
-// After lmm_common_setup(cfg) with g_ctx.U / g_ctx.eval in place.  UtW_d: n x c, UtY_d: n x T row-major, both on the device;
+// After lmm_bind: g_ctx.U / g_ctx.eval in place.  UtW_d: n x c, UtY_d: n x T row-major, both on the device;
 // l_mle_null: T values on the host.
 static int score_setup_dev(size_t T, const double *l_mle_null, const double *UtW_d, const double *UtY_d, hipStream_t s) {
   const size_t n = g_ctx.cfg.n, c = g_ctx.cfg.n_cvt;
@@ -63,70 +60,47 @@ static int score_setup_dev(size_t T, const double *l_mle_null, const double *UtW
   return GEMMA_HIP_OK;
 }
 
+// the three score-panel setups after their argument checks (lmm_bind: a failed setup leaves lmm_active false) -- and no score
+// state behind.  score_setup_dev has synchronised its stream: the uploaded U^T Y, read by the setup kernel only, goes at once.
+static int score_setup(const char *who, SetupSrc src, const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null, const double *U,
+                       const double *eval, const double *UtW, const double *UtY, hipStream_t s) {
+  const double *UtW_d, *UtY_d;
+  int rc = lmm_bind(who, src, cfg, U, eval, UtW, UtY, T, &UtW_d, &UtY_d);
+  if (rc) return rc;
+  if ((rc = score_setup_dev(T, l_mle_null, UtW_d, UtY_d, s))) {
+    score_release();
+    return rc;
+  }
+  if (src != SetupSrc::Device) g_ctx.own_Uty.release();
+  g_ctx.lmm_active = true;
+  return GEMMA_HIP_OK;
+}
+
 extern "C" int gemma_hip_lmm_score_panel_setup_d(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null, const double *U_d,
                                                  const double *eval_d, const double *UtW_d, const double *UtY_d, void *stream) {
   NEED_INIT();
-  int rc = score_check(cfg, T, l_mle_null); // the shape first: T = 0 has no U^T Y to point to
-  if (rc) return rc;
+  if (int rc = score_check(cfg, T, l_mle_null)) return rc; // the shape first: T = 0 has no U^T Y to point to
   if (!U_d || !eval_d || !UtW_d || !UtY_d) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup: null pointer");
-  if ((rc = lmm_common_setup(cfg))) return rc;
-  g_ctx.lmm_active = false; // a failed setup leaves no state behind
-  g_ctx.U = U_d;
-  g_ctx.U_even_of = nullptr;
-  g_ctx.eval = eval_d;
-  if ((rc = score_setup_dev(T, l_mle_null, UtW_d, UtY_d, S(stream)))) return score_fail(rc);
-  g_ctx.lmm_active = true;
-  return GEMMA_HIP_OK;
+  return score_setup("lmm_score_panel_setup", SetupSrc::Device, cfg, T, l_mle_null, U_d, eval_d, UtW_d, UtY_d, S(stream));
 }
 
 extern "C" int gemma_hip_lmm_score_panel_setup(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null, const double *U,
                                                const double *eval, const double *UtW, const double *UtY) {
   NEED_INIT();
-  int rc = score_check(cfg, T, l_mle_null); // the shape first: T = 0 has no U^T Y to point to
-  if (rc) return rc;
+  if (int rc = score_check(cfg, T, l_mle_null)) return rc; // the shape first: T = 0 has no U^T Y to point to
   if (!U || !eval || !UtW || !UtY) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup: null pointer");
-  if ((rc = lmm_common_setup(cfg))) return rc;
-  g_ctx.lmm_active = false;
-  const size_t n = cfg->n, c = cfg->n_cvt;
-  if (g_ctx.own_U.reserve(n * n * 8) || g_ctx.own_eval.reserve(n * 8) || g_ctx.own_Uty.reserve(n * T * 8) ||
-      g_ctx.own_UtW.reserve(n * c * 8))
-    return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_setup: cannot allocate U and U^T Y (%zu bytes)", n * n * 8 + n * T * 8);
-  HIPCHK(hipMemcpy(g_ctx.own_U.p, U, n * n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(g_ctx.own_eval.p, eval, n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(g_ctx.own_Uty.p, UtY, n * T * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(g_ctx.own_UtW.p, UtW, n * c * 8, hipMemcpyHostToDevice));
-  g_ctx.U = g_ctx.own_U.as<double>();
-  g_ctx.U_even_of = nullptr;
-  g_ctx.eval = g_ctx.own_eval.as<double>();
-  if ((rc = score_setup_dev(T, l_mle_null, g_ctx.own_UtW.as<double>(), g_ctx.own_Uty.as<double>(), 0))) return score_fail(rc);
-  g_ctx.own_Uty.release(); // read by the setup kernel only
-  g_ctx.lmm_active = true;
-  return GEMMA_HIP_OK;
+  return score_setup("lmm_score_panel_setup", SetupSrc::Host, cfg, T, l_mle_null, U, eval, UtW, UtY, nullptr);
 }
 
 extern "C" int gemma_hip_lmm_score_panel_setup_kept(const gemma_lmm_cfg *cfg, size_t T, const double *l_mle_null, const double *UtW,
                                                     const double *UtY) {
   NEED_INIT();
   if (!g_ctx.kept_n) return fail(GEMMA_HIP_ESTATE, "lmm_score_panel_setup_kept: no kept U");
-  int rc = score_check(cfg, T, l_mle_null); // the shape first: T = 0 has no U^T Y to point to
-  if (rc) return rc;
+  if (int rc = score_check(cfg, T, l_mle_null)) return rc; // the shape first: T = 0 has no U^T Y to point to
   if (!UtW || !UtY) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup_kept: null pointer");
   if (cfg->n != g_ctx.kept_n)
     return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_setup_kept: cfg.n=%zu, kept U is %zu", cfg->n, g_ctx.kept_n);
-  if ((rc = lmm_common_setup(cfg))) return rc;
-  g_ctx.lmm_active = false;
-  const size_t n = cfg->n, c = cfg->n_cvt;
-  if (g_ctx.own_Uty.reserve(n * T * 8) || g_ctx.own_UtW.reserve(n * c * 8))
-    return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_setup_kept: cannot allocate U^T Y (%zu bytes)", n * T * 8);
-  HIPCHK(hipMemcpy(g_ctx.own_Uty.p, UtY, n * T * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(g_ctx.own_UtW.p, UtW, n * c * 8, hipMemcpyHostToDevice));
-  g_ctx.U = kept_U();
-  g_ctx.U_even_of = nullptr;
-  g_ctx.eval = kept_eval();
-  if ((rc = score_setup_dev(T, l_mle_null, g_ctx.own_UtW.as<double>(), g_ctx.own_Uty.as<double>(), 0))) return score_fail(rc);
-  g_ctx.own_Uty.release();
-  g_ctx.lmm_active = true;
-  return GEMMA_HIP_OK;
+  return score_setup("lmm_score_panel_setup_kept", SetupSrc::Kept, cfg, T, l_mle_null, nullptr, nullptr, UtW, UtY, nullptr);
 }
 
 // the product + statistics of the l rows of UtX -> out_d[t * l + s]
@@ -169,7 +143,7 @@ extern "C" int gemma_hip_lmm_score_panel_batch_d(int kind, const void *geno, siz
   NEED_INIT();
   NEED_SCORE("lmm_score_panel_batch");
   if (l == 0) return GEMMA_HIP_OK;
-  int rc = check_batch_args("lmm_score_panel_batch", kind, geno, l, ld, out_d);
+  int rc = block_geom("lmm_score_panel_batch", kind, g_ctx.cfg.n, true, geno, l, ld, out_d);
   if (rc) return rc;
   hipStream_t s = S(stream);
   double *UtX;
@@ -182,20 +156,10 @@ extern "C" int gemma_hip_lmm_score_panel_batch(int kind, const void *geno, size_
   NEED_INIT();
   NEED_SCORE("lmm_score_panel_batch");
   if (l == 0) return GEMMA_HIP_OK;
-  const size_t n = g_ctx.cfg.n, T = g_ctx.score_T;
-  const size_t per_row = (kind == GEMMA_GENO_PLINK_2BIT && g_ctx.have_map) ? g_ctx.ni_total : n;
-  const size_t need = min_ld_for(kind, per_row, l);
-  if (need == (size_t)-1) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_batch: unknown geno_kind %d", kind);
-  if (!geno || !out || ld < need) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_batch: ld=%zu < %zu", ld, need);
-  const size_t rows = (kind == GEMMA_GENO_F64_IDV_MAJOR) ? n : l;
-  const size_t esz = (kind == GEMMA_GENO_PLINK_2BIT) ? 1 : 8;
-  if (g_ctx.stage_in.reserve(rows * ld * esz) || g_ctx.stage_out.reserve(T * l * sizeof(gemma_score_rec)))
-    return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_batch: staging %zu bytes", rows * ld * esz + T * l * sizeof(gemma_score_rec));
-  HIPCHK(hipMemcpy2D(g_ctx.stage_in.p, ld * esz, geno, ld * esz, need * esz, rows, hipMemcpyHostToDevice));
-  int rc = gemma_hip_lmm_score_panel_batch_d(kind, g_ctx.stage_in.p, l, ld, g_ctx.stage_out.as<gemma_score_rec>(), nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(out, g_ctx.stage_out.p, T * l * sizeof(gemma_score_rec), hipMemcpyDeviceToHost));
-  return GEMMA_HIP_OK;
+  return host_batch("lmm_score_panel_batch", kind, geno, l, ld, g_ctx.stage_out, out, g_ctx.score_T * l * sizeof(gemma_score_rec),
+                    [&](const void *in_d, void *out_d) {
+                      return gemma_hip_lmm_score_panel_batch_d(kind, in_d, l, ld, static_cast<gemma_score_rec *>(out_d), nullptr);
+                    });
 }
 
 // ---- the hits form: pairs with p_score <= p_max, the best pair per phenotype (lmm_score_panel.hip.h) ----
@@ -285,7 +249,7 @@ extern "C" int gemma_hip_lmm_score_panel_hits_batch_d(int kind, const void *geno
   if (rc) return rc;
   hipStream_t s = S(stream);
   if (l == 0) return score_hits_empty(n_hits_d, best_d, s);
-  if ((rc = check_batch_args("lmm_score_panel_hits_batch", kind, geno, l, ld, n_hits_d))) return rc;
+  if ((rc = block_geom("lmm_score_panel_hits_batch", kind, g_ctx.cfg.n, true, geno, l, ld, n_hits_d))) return rc;
   double *UtX;
   size_t ldx;
   if ((rc = compute_utx(kind, geno, l, ld, -1, &UtX, &ldx, s))) return rc;
@@ -299,7 +263,7 @@ extern "C" int gemma_hip_lmm_score_panel_hits_batch(int kind, const void *geno, 
   NEED_SCORE("lmm_score_panel_hits_batch");
   int rc = score_hits_check("lmm_score_panel_hits_batch", l, p_max, hits, cap, n_hits);
   if (rc) return rc;
-  const size_t n = g_ctx.cfg.n, T = g_ctx.score_T;
+  const size_t T = g_ctx.score_T;
   if (g_ctx.score_cnt.reserve(8) || (best && g_ctx.score_best.reserve(T * sizeof(gemma_score_best))) ||
       (cap && g_ctx.score_hits.reserve(cap * sizeof(gemma_score_hit))))
     return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_hits_batch: a list of %zu hits (%zu bytes)", cap, cap * sizeof(gemma_score_hit));
@@ -308,14 +272,9 @@ extern "C" int gemma_hip_lmm_score_panel_hits_batch(int kind, const void *geno, 
   if (l == 0) {
     if ((rc = score_hits_empty(g_ctx.score_cnt.as<unsigned long long>(), best_d, nullptr))) return rc;
   } else {
-    const size_t per_row = (kind == GEMMA_GENO_PLINK_2BIT && g_ctx.have_map) ? g_ctx.ni_total : n;
-    const size_t need = min_ld_for(kind, per_row, l);
-    if (need == (size_t)-1) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_hits_batch: unknown geno_kind %d", kind);
-    if (!geno || ld < need) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_hits_batch: ld=%zu < %zu", ld, need);
-    const size_t rows = (kind == GEMMA_GENO_F64_IDV_MAJOR) ? n : l;
-    const size_t esz = (kind == GEMMA_GENO_PLINK_2BIT) ? 1 : 8;
-    if (g_ctx.stage_in.reserve(rows * ld * esz)) return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_hits_batch: staging %zu bytes", rows * ld * esz);
-    HIPCHK(hipMemcpy2D(g_ctx.stage_in.p, ld * esz, geno, ld * esz, need * esz, rows, hipMemcpyHostToDevice));
+    BlockGeom g;
+    if ((rc = block_geom("lmm_score_panel_hits_batch", kind, g_ctx.cfg.n, true, geno, l, ld, n_hits, &g))) return rc;
+    if ((rc = stage_block("lmm_score_panel_hits_batch", g, geno, ld))) return rc;
     rc = gemma_hip_lmm_score_panel_hits_batch_d(kind, g_ctx.stage_in.p, l, ld, p_max, hits_d, cap, g_ctx.score_cnt.as<unsigned long long>(),
                                                 best_d, nullptr);
     if (rc) return rc;

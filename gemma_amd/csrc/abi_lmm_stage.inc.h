@@ -1,6 +1,8 @@
 // Part of gemma_hip.hip (ONE translation unit: the parts share the context g_ctx and the helpers of its anonymous namespace, and are
 // included there in this order; round 6: the 3 500-line file cut along its stages for reading -- no behaviour change).
-// This part: the per-SNP stage of LMM::Analyze: setup (lmm_setup*), fixed-lambda tables, Chebyshev series, launch_assoc.
+// This part: the per-SNP stage of LMM::Analyze: the release list of the LMM state (lmm_release), the part every setup shares
+// (lmm_common_setup, lmm_bind: U, eval, UtW, UtY from device pointers, host arrays or the kept U), lmm_setup*, fixed-lambda tables,
+// Chebyshev series, launch_assoc.
 
 // ------------------------------------------------------------------------------ LMM
 // Phenotype slots of a multi setup (Ctx::PhenoSlot): the live members <-> a parked slot
@@ -29,6 +31,32 @@ static void score_release() {
   g_ctx.score_fthr.release(); g_ctx.score_cells.release(); g_ctx.score_hits.release(); g_ctx.score_cnt.release(); g_ctx.score_best.release();
   g_ctx.score_fthr_p = -1.0;
   g_ctx.score_T = 0;
+}
+// Everything an LMM setup or one of its batches owns, and the state flags: gemma_hip_lmm_finish and gemma_hip_shutdown (the
+// streams, events and pinned slots of the pipelines go through pipe_release / xp_release beside it).
+static void lmm_release() {
+  g_ctx.own_U.release(); g_ctx.own_eval.release(); g_ctx.own_Uty.release(); g_ctx.own_UtW.release();
+  g_ctx.UtWt.release(); g_ctx.idx_map.release(); g_ctx.X.release(); g_ctx.UtX.release();
+  g_ctx.stage_in.release(); g_ctx.stage_out.release(); g_ctx.carry.release(); g_ctx.scratch.release();
+  g_ctx.grid_R.release(); g_ctx.grid_F.release(); g_ctx.grid_T.release();
+  g_ctx.table_P.release();
+  g_ctx.cheb_R.release(); g_ctx.cheb_F.release(); g_ctx.cheb_T.release(); g_ctx.cheb_slots.release();
+  g_ctx.cheb_list.release(); g_ctx.cheb_count.release(); g_ctx.cheb_D.release(); g_ctx.cheb_Ck.release();
+  g_ctx.cheb_Gk.release(); g_ctx.cheb_Lk.release(); g_ctx.cheb_iv.release(); g_ctx.cheb_dends.release(); g_ctx.cheb_res.release();
+  g_ctx.i8_Bt.release(); g_ctx.i8_q.release(); g_ctx.i8_qinv.release(); g_ctx.i8_cmax.release(); g_ctx.i8_A.release(); g_ctx.i8_C.release();
+  raster_release();
+  g_ctx.i8_mean.release(); g_ctx.i8_meta.release(); g_ctx.i8_rowsur.release(); g_ctx.i8_colsum.release(); g_ctx.i8_surlist.release();
+  g_ctx.i8_ready = g_ctx.i8_colsum_ready = false;
+  g_ctx.gxe_env.release(); g_ctx.gxe_UtWt.release(); g_ctx.gxe_Z.release(); g_ctx.gxe_UtZ.release(); g_ctx.gxe_flip.release();
+  g_ctx.gxe_ready = false;
+  g_ctx.mv_Yt.release(); g_ctx.mv_out.release(); g_ctx.mv_scratch.release();
+  g_ctx.mv_ready = g_ctx.mv_gxe = false;
+  multi_release();
+  score_release();
+  g_ctx.U = g_ctx.eval = g_ctx.Uty = nullptr;
+  g_ctx.U_even_of = nullptr;
+  g_ctx.U_even.release();
+  g_ctx.lmm_active = false;
 }
 // the single-phenotype entry points after a multi setup: the live slot is nobody's
 #define NEED_SINGLE(who)                                                                                                  \
@@ -85,6 +113,49 @@ static int lmm_common_setup(const gemma_lmm_cfg *cfg) {
   g_ctx.i8_colsum_ready = false;
   g_ctx.gxe_ready = false;
   g_ctx.mv_ready = false;
+  return GEMMA_HIP_OK;
+}
+
+// the kept (U, eval) of the device-resident chain (abi_kept_comm.inc.h): one buffer, eval behind U
+static double *kept_U() { return g_ctx.kept_UE.as<double>(); }
+static double *kept_eval() { return g_ctx.kept_UE.as<double>() + g_ctx.kept_n * g_ctx.kept_n; }
+
+// Where the (U, eval, UtW, UtY) of a setup come from: device pointers the library borrows, host arrays it uploads into own_*, or the
+// kept (U, eval) with host UtW and UtY (U and eval are then not read).
+enum class SetupSrc { Device, Host, Kept };
+
+// The common part of every lmm_*setup* after its own argument checks: lmm_common_setup, then (U, eval, UtW, UtY) onto the device
+// as the source requires, g_ctx.U / g_ctx.eval set.  UtY holds T columns (n x T row-major; T = 1: the single form's Uty).  Returns the
+// device pointers of UtW and UtY for the family's build step.  lmm_active is false from here on: the entry point sets it when its
+// build step is through, and a setup that fails on the way leaves no active state behind.
+static int lmm_bind(const char *who, SetupSrc src, const gemma_lmm_cfg *cfg, const double *U, const double *eval, const double *UtW,
+                    const double *UtY, size_t T, const double **UtW_d, const double **UtY_d) {
+  const int rc = lmm_common_setup(cfg);
+  if (rc) return rc;
+  g_ctx.lmm_active = false;
+  g_ctx.U_even_of = nullptr;
+  if (src == SetupSrc::Device) {
+    g_ctx.U = U;
+    g_ctx.eval = eval;
+    *UtW_d = UtW;
+    *UtY_d = UtY;
+    return GEMMA_HIP_OK;
+  }
+  const size_t n = cfg->n, c = cfg->n_cvt;
+  const bool kept = src == SetupSrc::Kept;
+  if ((!kept && (g_ctx.own_U.reserve(n * n * 8) || g_ctx.own_eval.reserve(n * 8))) || g_ctx.own_Uty.reserve(n * T * 8) ||
+      g_ctx.own_UtW.reserve(n * c * 8))
+    return fail(GEMMA_HIP_ENOMEM, "%s: cannot allocate U and U^T Y (%zu bytes)", who, (kept ? 0 : n * n * 8) + n * T * 8);
+  if (!kept) {
+    HIPCHK(hipMemcpy(g_ctx.own_U.p, U, n * n * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(g_ctx.own_eval.p, eval, n * 8, hipMemcpyHostToDevice));
+  }
+  HIPCHK(hipMemcpy(g_ctx.own_Uty.p, UtY, n * T * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(g_ctx.own_UtW.p, UtW, n * c * 8, hipMemcpyHostToDevice));
+  g_ctx.U = kept ? kept_U() : g_ctx.own_U.as<double>();
+  g_ctx.eval = kept ? kept_eval() : g_ctx.own_eval.as<double>();
+  *UtW_d = g_ctx.own_UtW.as<double>();
+  *UtY_d = g_ctx.own_Uty.as<double>();
   return GEMMA_HIP_OK;
 }
 
@@ -392,45 +463,31 @@ static int make_utwt(const double *UtW_d, hipStream_t s) {
   return make_grid(s);
 }
 
+// the three single-phenotype setups after their argument checks; the host forms return with the setup's work done
+static int single_setup(const char *who, SetupSrc src, const gemma_lmm_cfg *cfg, const double *U, const double *eval,
+                        const double *UtW, const double *Uty, hipStream_t s) {
+  const double *UtW_d, *Uty_d;
+  int rc = lmm_bind(who, src, cfg, U, eval, UtW, Uty, 1, &UtW_d, &Uty_d);
+  if (rc) return rc;
+  g_ctx.Uty = Uty_d;
+  if ((rc = make_utwt(UtW_d, s))) return rc;
+  if (src != SetupSrc::Device) HIPCHK(hipDeviceSynchronize());
+  g_ctx.lmm_active = true;
+  return GEMMA_HIP_OK;
+}
+
 extern "C" int gemma_hip_lmm_setup_d(const gemma_lmm_cfg *cfg, const double *U_d, const double *eval_d,
                                      const double *UtW_d, const double *Uty_d, void *stream) {
   NEED_INIT();
   if (!U_d || !eval_d || !UtW_d || !Uty_d) return fail(GEMMA_HIP_EINVAL, "lmm_setup: null pointer");
-  int rc = lmm_common_setup(cfg);
-  if (rc) return rc;
-  g_ctx.U = U_d;
-  g_ctx.U_even_of = nullptr;
-  g_ctx.eval = eval_d;
-  g_ctx.Uty = Uty_d;
-  rc = make_utwt(UtW_d, S(stream));
-  if (rc) return rc;
-  g_ctx.lmm_active = true;
-  return GEMMA_HIP_OK;
+  return single_setup("lmm_setup", SetupSrc::Device, cfg, U_d, eval_d, UtW_d, Uty_d, S(stream));
 }
 
 extern "C" int gemma_hip_lmm_setup(const gemma_lmm_cfg *cfg, const double *U, const double *eval,
                                    const double *UtW, const double *Uty) {
   NEED_INIT();
   if (!U || !eval || !UtW || !Uty) return fail(GEMMA_HIP_EINVAL, "lmm_setup: null pointer");
-  int rc = lmm_common_setup(cfg);
-  if (rc) return rc;
-  const size_t n = cfg->n, c = cfg->n_cvt;
-  if (g_ctx.own_U.reserve(n * n * 8) || g_ctx.own_eval.reserve(n * 8) || g_ctx.own_Uty.reserve(n * 8) ||
-      g_ctx.own_UtW.reserve(n * c * 8))
-    return fail(GEMMA_HIP_ENOMEM, "lmm_setup: cannot allocate U (%zu bytes)", n * n * 8);
-  HIPCHK(hipMemcpy(g_ctx.own_U.p, U, n * n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(g_ctx.own_eval.p, eval, n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(g_ctx.own_Uty.p, Uty, n * 8, hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(g_ctx.own_UtW.p, UtW, n * c * 8, hipMemcpyHostToDevice));
-  g_ctx.U = g_ctx.own_U.as<double>();
-  g_ctx.U_even_of = nullptr;
-  g_ctx.eval = g_ctx.own_eval.as<double>();
-  g_ctx.Uty = g_ctx.own_Uty.as<double>();
-  rc = make_utwt(g_ctx.own_UtW.as<double>(), 0);
-  if (rc) return rc;
-  HIPCHK(hipDeviceSynchronize());
-  g_ctx.lmm_active = true;
-  return GEMMA_HIP_OK;
+  return single_setup("lmm_setup", SetupSrc::Host, cfg, U, eval, UtW, Uty, nullptr);
 }
 
 extern "C" int gemma_hip_lmm_set_indicator(const int *indicator_idv, size_t ni_total) {

@@ -1,6 +1,6 @@
 // Part of gemma_hip.hip (ONE translation unit: the parts share the context g_ctx and the helpers of its anonymous namespace, and are
 // included there in this order; round 6: the 3 500-line file cut along its stages for reading -- no behaviour change).
-// This part: multivariate LMM ABI (kernels in mvlmm_kernels*.hip).
+// This part: multivariate LMM ABI (kernels in mvlmm_kernels*.hip); the host form of a block is host_batch (abi_host_block.inc.h).
 
 // ---- multivariate LMM: MVLMM::AnalyzeBimbam / AnalyzePlink, src/mvlmm.cpp:2972-3899 (kernels in mvlmm_kernels.hip)
 extern "C" int gemma_hip_mvlmm_launch_(const MvArgs *g, int d, int c, hipStream_t s);
@@ -251,7 +251,7 @@ extern "C" int gemma_hip_mvlmm_batch_d(int kind, const void *geno, size_t l, siz
   NEED_INIT();
   if (!g_ctx.lmm_active || !g_ctx.mv_ready) return fail(GEMMA_HIP_ESTATE, "mvlmm_batch before lmm_setup + mvlmm_set");
   if (l == 0) return GEMMA_HIP_OK;
-  int rc = check_batch_args("mvlmm_batch", kind, geno, l, ld, out_d);
+  int rc = block_geom("mvlmm_batch", kind, g_ctx.cfg.n, true, geno, l, ld, out_d);
   if (rc) return rc;
   hipStream_t s = S(stream);
   if (g_ctx.mv_gxe) return mvlmm_gxe_batch_d(kind, geno, l, ld, out_d, s);
@@ -275,19 +275,8 @@ extern "C" int gemma_hip_mvlmm_batch(int kind, const void *geno, size_t l, size_
   NEED_INIT();
   if (!g_ctx.lmm_active || !g_ctx.mv_ready) return fail(GEMMA_HIP_ESTATE, "mvlmm_batch before lmm_setup + mvlmm_set");
   if (l == 0) return GEMMA_HIP_OK;
-  int rc = check_batch_args("mvlmm_batch", kind, geno, l, ld, out);
-  if (rc) return rc;
-  const size_t n = g_ctx.cfg.n;
-  const size_t per_row = (kind == GEMMA_GENO_PLINK_2BIT && g_ctx.have_map) ? g_ctx.ni_total : n;
-  const size_t need = min_ld_for(kind, per_row, l);
-  const size_t rows = (kind == GEMMA_GENO_F64_IDV_MAJOR) ? n : l;
-  const size_t esz = (kind == GEMMA_GENO_PLINK_2BIT) ? 1 : 8;
-  const size_t bytes_out = l * (size_t)g_ctx.mv_proto.stride * 8;
-  if (g_ctx.stage_in.reserve(rows * ld * esz) || g_ctx.mv_out.reserve(bytes_out))
-    return fail(GEMMA_HIP_ENOMEM, "mvlmm_batch: staging %zu bytes", rows * ld * esz + bytes_out);
-  HIPCHK(hipMemcpy2D(g_ctx.stage_in.p, ld * esz, geno, ld * esz, need * esz, rows, hipMemcpyHostToDevice));
-  rc = gemma_hip_mvlmm_batch_d(kind, g_ctx.stage_in.p, l, ld, g_ctx.mv_out.as<double>(), nullptr);
-  if (rc) return rc;
-  HIPCHK(hipMemcpy(out, g_ctx.mv_out.p, bytes_out, hipMemcpyDeviceToHost));
-  return GEMMA_HIP_OK;
+  return host_batch("mvlmm_batch", kind, geno, l, ld, g_ctx.mv_out, out, l * (size_t)g_ctx.mv_proto.stride * 8,
+                    [&](const void *in_d, void *out_d) {
+                      return gemma_hip_mvlmm_batch_d(kind, in_d, l, ld, static_cast<double *>(out_d), nullptr);
+                    });
 }

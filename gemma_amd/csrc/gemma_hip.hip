@@ -368,6 +368,11 @@ static void raster_release() {
   }
 }
 static void kin_i8_release(); // integer kinship path, defined with kin_begin
+// one release list per state, each beside the entry points that fill it: kinship (abi_kinship.inc.h), LMM (abi_lmm_stage.inc.h), -lm
+// (abi_gxe_lm.inc.h).  A member added to Ctx is released by adding it to its state's list and nowhere else.
+static void kin_release();
+static void lmm_release();
+static void lm_release();
 
 // ------------------------------------------------------------------------------ lifetime
 extern "C" int gemma_hip_abi_version(void) { return GEMMA_HIP_ABI_VERSION; }
@@ -420,28 +425,10 @@ extern "C" void gemma_hip_shutdown(void) {
   if (!g_ctx.inited) return;
   (void)hipDeviceSynchronize();
   for (int s = 0; s < GEMMA_STAGE_COUNT; ++s) prof_collect(s);
-  g_ctx.kin_K.release(); g_ctx.kin_X.release(); g_ctx.kin_stage.release();
+  kin_release();
   g_ctx.qc_G.release(); g_ctx.qc_M.release(); g_ctx.qc_W.release(); g_ctx.qc_O.release();
-  kin_i8_release();
-  g_ctx.own_U.release(); g_ctx.own_eval.release(); g_ctx.own_Uty.release(); g_ctx.own_UtW.release();
-  g_ctx.UtWt.release(); g_ctx.idx_map.release(); g_ctx.X.release(); g_ctx.UtX.release();
-  g_ctx.stage_in.release(); g_ctx.stage_out.release(); g_ctx.carry.release(); g_ctx.scratch.release();
-  g_ctx.i8_Bt.release(); g_ctx.i8_q.release(); g_ctx.i8_qinv.release(); g_ctx.i8_cmax.release(); g_ctx.i8_A.release(); g_ctx.i8_C.release();
-  raster_release();
-  g_ctx.mv_Yt.release(); g_ctx.mv_out.release(); g_ctx.mv_scratch.release(); // shutdown without lmm_finish leaked these
-  g_ctx.mv_ready = g_ctx.mv_gxe = false;
-  g_ctx.i8_mean.release(); g_ctx.i8_meta.release(); g_ctx.i8_rowsur.release(); g_ctx.i8_colsum.release(); g_ctx.i8_surlist.release();
-  g_ctx.i8_ready = g_ctx.i8_colsum_ready = false;
-  g_ctx.table_P.release(); g_ctx.U_even.release();
-  for (auto &p : g_ctx.slots) { p.grid_R.release(); p.grid_F.release(); p.cheb_R.release(); p.cheb_F.release(); p.carry.release(); }
-  g_ctx.slots.clear();
-  g_ctx.multi_Yt.release(); g_ctx.multi_R.release(); g_ctx.multi_T_buf.release();
-  g_ctx.multi_T = 0;
-  g_ctx.score_R.release(); g_ctx.score_Pyy.release(); g_ctx.score_Yt.release(); g_ctx.score_lam.release(); g_ctx.score_bad.release();
-  g_ctx.score_fthr.release(); g_ctx.score_cells.release(); g_ctx.score_hits.release(); g_ctx.score_cnt.release(); g_ctx.score_best.release();
-  g_ctx.score_fthr_p = -1.0;
-  g_ctx.score_T = 0;
-  g_ctx.U_even_of = nullptr;
+  lmm_release(); // every buffer an LMM setup or batch owns: ONE list, beside the members' users (abi_lmm_stage.inc.h)
+  lm_release();
   pipe_release(); // pinned slots, copy stream and events of the pipelined host-block path
   xp_release();
   if (g_ctx.ov_stream) {
@@ -461,7 +448,6 @@ extern "C" void gemma_hip_shutdown(void) {
     g_ctx.kin_copied = g_ctx.kin_ingested = nullptr;
     g_ctx.kin_ingested_valid = false;
   }
-  g_ctx.kin_active = g_ctx.lmm_active = false;
   g_ctx.kept_K.release(); g_ctx.kept_UE.release();
   g_ctx.kept_K_n = g_ctx.kept_n = 0;
   g_ctx.comm.finalize();
@@ -563,6 +549,9 @@ extern "C" int gemma_hip_dgemm(char ta, char tb, size_t M, size_t N, size_t K, d
 // The stages of the C ABI, one file each (textual parts of THIS translation unit -- they share g_ctx; VERDICT r5 item 9: cut along the
 // stages for reading.  A split into separately compiled units needs the argument structs that Ctx holds (AssocArgs, MvArgs, LmArgs,
 // GridGeom, Comm) cut loose from the kernels defined beside them first: every unit would otherwise instantiate every kernel.)
+// abi_host_block.inc.h comes first: the geometry / argument check of a genotype block and the staging of a host block, which every
+// block entry point of the parts below goes through.
+#include "abi_host_block.inc.h"
 #include "abi_kinship.inc.h"
 #include "abi_eigen_qc.inc.h"
 #include "abi_lmm_stage.inc.h"
