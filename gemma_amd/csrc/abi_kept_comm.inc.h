@@ -4,14 +4,6 @@
 // host-block pipeline (its own buffers, streams and events; the geometry from block_geom), the communicator, diagnostics.
 
 // ------------------------------------------------------------------------------ device-resident chain
-namespace {
-__global__ void subselect_kernel(const double *__restrict__ K, long ni_total, const int *__restrict__ map, long n,
-                                 double *__restrict__ G) {
-  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
-  if (c < n) G[r * n + c] = K[(long)map[r] * ni_total + map[c]];
-}
-} // namespace
-
 extern "C" int gemma_hip_kin_end_keep(size_t *ns_used, int allreduce) {
   NEED_INIT();
   if (!g_ctx.kin_active) return fail(GEMMA_HIP_ESTATE, "kin_end before kin_begin");

@@ -14,7 +14,7 @@
 
 #include "../../include/gemma_hip.h"
 #include "tu_common.h"
-#include "dgemm_mfma.hip.h"
+#include "dgemm.h"
 #include "cor.hip.h"
 #include "cor_tu.h"
 
@@ -79,7 +79,6 @@ void cor_release_x() {
 
 void cor_tu_shutdown() {
   cor_release_x();
-  gemm_aux_destroy();
 }
 
 bool cor_active_x() { return g_cor.active; }
@@ -96,7 +95,6 @@ int cor_begin_x(long ni_total, const int *indicator, std::string &msg) {
   }
   TU_CHK(hipDeviceSynchronize());
   g_cor.active = false;
-  gemm_aux_init();
   int rc;
   if ((rc = g_cor.idx.reserve((size_t)n * sizeof(int), "cor", msg))) return rc;
   TU_CHK(hipMemcpy(g_cor.idx.p, idx.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));

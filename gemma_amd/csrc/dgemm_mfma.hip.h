@@ -20,22 +20,12 @@
 //    tiles, rastered in groups of 4 tile-rows so the ~64 blocks an XCD runs at once form a
 //    4x16 patch sharing A/B panels in that XCD's 4 MiB L2 (80 % TCC hit rate at n = 20000).
 //  * SYRK mode (kinship): only tiles with tile_n >= tile_m are launched (triangular grid).
+//
+// The kernels only: dgemm.h declares what the other units call, dgemm_tu.hip holds the launch code and includes this file.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
+#include "dgemm.h"
 
 namespace gemma_hip {
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int GEMM_BM = 128, GEMM_BN = 128, GEMM_BK = 16;
-constexpr int GEMM_LD_KM = 144; // [k][m] image: row stride in doubles
-constexpr int GEMM_LD_MK = 18;  // [m][k] image: row stride in doubles
-constexpr int GEMM_TILE_DOUBLES = 2304; // 16*144 == 128*18
-constexpr int GEMM_THREADS = 256;
 
 struct GemmArgs {
   const double *A;
@@ -314,7 +304,6 @@ __global__ __launch_bounds__(NW * 64, (NW == 8 ? 4 : 2)) void dgemm_mfma_kernel(
 // in the middle of step 2, the barrier sits between steps 2 and 3, and step 3 already reads tile t+1's first
 // fragments.  The global loads of tile t+2 are issued right after that barrier, 3.5 K-steps (>= 3600 cycles of this
 // wave's own MFMA issue) ahead of the ds_write that consumes them.
-#define GEMMA_SB() __builtin_amdgcn_sched_barrier(0)
 template <bool A_KM, bool B_KN>
 __global__ __launch_bounds__(256, 2) void dgemm_mfma_pipe_kernel(GemmArgs g) {
   gemm_take_slice<A_KM, B_KN>(g);
@@ -456,8 +445,6 @@ __global__ __launch_bounds__(256, 2) void dgemm_mfma_pipe_kernel(GemmArgs g) {
 //      [k][m] operands: one k-row (128 doubles = 1 KiB) per instruction, rows still 144 doubles apart;
 //      [m][k] operands: 8 rows x 16 doubles per instruction, unpadded, with the 16-byte chunk index XOR-ed by
 //      (m >> 1) & 7 on the SOURCE address and on the fragment read (conflict-free ds_read_b64 half-waves).
-typedef const __attribute__((address_space(1))) void *gemma_gptr_t;
-typedef __attribute__((address_space(3))) void *gemma_lptr_t;
 
 template <bool A_KM, bool B_KN>
 __global__ __launch_bounds__(256, 2) void dgemm_mfma_glds_kernel(GemmArgs g) {
@@ -642,7 +629,7 @@ __global__ __launch_bounds__(256, 2) void dgemm_mfma_glds_kernel(GemmArgs g) {
 
 // mirror the strict upper triangle into the lower one and scale everything (kinship epilogue:
 // K *= 1/ns_test, GEMMA src/gemma_io.cpp:1570, and the symmetric fill of :1724-1729)
-static __global__ void symm_fill_scale_kernel(double *K, long n, long ld, double scale) {
+__global__ void symm_fill_scale_kernel(double *K, long n, long ld, double scale) {
   __shared__ double tile[32][33];
   // blocks cover the upper-triangular 32x32 tile pairs (bx >= by)
   const int bx = blockIdx.x, by = blockIdx.y;
@@ -663,250 +650,6 @@ static __global__ void symm_fill_scale_kernel(double *K, long n, long ld, double
     const long j = (long)bx * 32 + r, i = (long)by * 32 + tx;
     if (i < n && j < n && j > i) K[j * ld + i] = tile[tx][r];
   }
-}
-
-// Wavefronts per 128x128 block: 4 (2x2 waves of 64x64, 2 waves/SIMD at 2 blocks/CU; default) or 8 (2x4 waves
-// of 64x32, 4 waves/SIMD; GEMMA_HIP_GEMM_WAVES=8).  Measured at M=N=K=20000 (profiles/r01_gemm_variants.txt):
-// the 8-wave form is 1.7 % faster (238.8 vs 242.6 ms) but its blocks drift apart inside an XCD and the L2 hit
-// rate drops from 82 % to 17 % (fabric traffic x4); the 4-wave form keeps the co-scheduled tiles in step.
-static inline int gemm_waves() {
-  static int nw = 0;
-  if (nw == 0) {
-    const char *e = getenv("GEMMA_HIP_GEMM_WAVES");
-    nw = (e && e[0] == '8') ? 8 : 4;
-  }
-  return nw;
-}
-
-// GEMMA_HIP_GEMM_PIPE=0/1/2: interior kernel = register-staged / + software-pipelined fragments / direct-to-LDS with
-// pinned interleaved issue (default; 243 -> 238 -> 219 ms at M = N = K = 20000)
-static inline int gemm_pipe() {
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("GEMMA_HIP_GEMM_PIPE");
-    v = e ? atoi(e) : 2;
-  }
-  return v;
-}
-
-static inline bool gemm_clamp() { // GEMMA_HIP_GEMM_CLAMP=0: ragged strips through the bounds-checked kernel
-  static int v = -1;
-  if (v < 0) {
-    const char *e = getenv("GEMMA_HIP_GEMM_CLAMP");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
-}
-
-template <bool A_KM, bool B_KN, bool FULL>
-static inline hipError_t launch_dgemm_grid(const GemmArgs &g, hipStream_t s) {
-  int nblocks;
-  if (g.syrk_upper)
-    nblocks = g.tiles_m * (g.tiles_m + 1) / 2;
-  else
-    nblocks = g.tiles_m * g.tiles_n;
-  if (nblocks <= 0) return hipSuccess;
-  if (FULL && gemm_pipe() == 2 && !g.square_a)
-    hipLaunchKernelGGL((dgemm_mfma_glds_kernel<A_KM, B_KN>), dim3(nblocks, g.kslices), dim3(256), 0, s, g);
-  else if (FULL && gemm_pipe())
-    hipLaunchKernelGGL((dgemm_mfma_pipe_kernel<A_KM, B_KN>), dim3(nblocks, g.kslices), dim3(256), 0, s, g);
-  else if (gemm_waves() == 8)
-    hipLaunchKernelGGL((dgemm_mfma_kernel<A_KM, B_KN, 8, FULL>), dim3(nblocks, g.kslices), dim3(512), 0, s, g);
-  else
-    hipLaunchKernelGGL((dgemm_mfma_kernel<A_KM, B_KN, 4, FULL>), dim3(nblocks, g.kslices), dim3(256), 0, s, g);
-  return hipGetLastError();
-}
-
-// Optional side stream for the ragged edge strips: they are tiny launches (<= 2 x 157 blocks at n = 20000)
-// that would otherwise run alone after the main grid; on a second stream they fill the main grid's tail.
-struct GemmAux {
-  hipStream_t stream = nullptr;
-  hipEvent_t ready = nullptr, done = nullptr;
-};
-static GemmAux g_gemm_aux;
-static inline void gemm_aux_init() {
-  if (g_gemm_aux.stream) return;
-  const char *e = getenv("GEMMA_HIP_GEMM_SIDE_STREAM"); // "0": keep everything on the caller's stream
-  if (e && e[0] == '0') return;
-  if (hipStreamCreateWithFlags(&g_gemm_aux.stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&g_gemm_aux.ready, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&g_gemm_aux.done, hipEventDisableTiming) != hipSuccess) {
-    (void)hipGetLastError();
-    g_gemm_aux = GemmAux();
-  }
-}
-static inline void gemm_aux_destroy() {
-  if (g_gemm_aux.stream) {
-    (void)hipStreamDestroy(g_gemm_aux.stream);
-    (void)hipEventDestroy(g_gemm_aux.ready);
-    (void)hipEventDestroy(g_gemm_aux.done);
-  }
-  g_gemm_aux = GemmAux();
-}
-
-template <bool A_KM, bool B_KN>
-static inline hipError_t launch_dgemm_t(GemmArgs g, hipStream_t s) {
-  const int Tm = (int)((g.M + GEMM_BM - 1) / GEMM_BM), Tn = (int)((g.N + GEMM_BN - 1) / GEMM_BN);
-  const int Fm = (int)(g.M / GEMM_BM), Fn = (int)(g.N / GEMM_BN); // complete tiles per dimension
-  const bool aligned = ((reinterpret_cast<uintptr_t>(g.A) & 15) == 0) && ((g.lda & 1) == 0) &&
-                       ((reinterpret_cast<uintptr_t>(g.B) & 15) == 0) && ((g.ldb & 1) == 0);
-  hipError_t e;
-  // K tail: the first floor(K / 16) * 16 of K through the fast kernels, the remaining < 16 accumulated on top by the
-  // bounds-checked one (the eigensolver's divide & conquer merges have arbitrary K)
-  if (aligned && g.K > 4 * GEMM_BK && (g.K % GEMM_BK) != 0 && Fm > 0 && Fn > 0 && !g.square_a) {
-    const long K0 = (g.K / GEMM_BK) * GEMM_BK, K1 = g.K - K0;
-    GemmArgs g0 = g;
-    g0.K = K0;
-    if ((e = launch_dgemm_t<A_KM, B_KN>(g0, s)) != hipSuccess) return e;
-    GemmArgs g1 = g;
-    g1.K = K1;
-    g1.A = A_KM ? g.A + K0 * g.lda : g.A + K0;
-    g1.B = B_KN ? g.B + K0 * g.ldb : g.B + K0;
-    g1.beta = 1.0;
-    g1.clamp = 0;
-    g1.tiles_m = Tm; g1.tiles_n = Tn; g1.tm0 = 0; g1.tn0 = 0;
-    if (g.syrk_upper) g1.tiles_n = Tm;
-    return launch_dgemm_grid<A_KM, B_KN, false>(g1, s);
-  }
-  const bool fast = aligned && (g.K % GEMM_BK == 0) && g.K > 0 && Fm > 0 && Fn > 0;
-  if (!fast) { // everything through the bounds-checked instantiation
-    g.tiles_m = Tm; g.tiles_n = Tn; g.tm0 = 0; g.tn0 = 0;
-    return launch_dgemm_grid<A_KM, B_KN, false>(g, s);
-  }
-  const int syrk = g.syrk_upper;
-  g.clamp = 0;
-  // beta == 0: ragged last tile rows / columns are shifted back inside the matrix and ride in the same launch
-  // (bit-identical rewrites of the overlap); the [k][m] operand of a shifted tile must stay 16-byte aligned
-  if (gemm_pipe() >= 2 && !syrk && !g.square_a && g.beta == 0.0 && (Tm > Fm || Tn > Fn) && gemm_clamp() &&
-      (!A_KM || (g.M & 1) == 0) && (!B_KN || (g.N & 1) == 0)) {
-    g.clamp = 1;
-    g.tiles_m = Tm; g.tiles_n = Tn; g.tm0 = 0; g.tn0 = 0;
-    return launch_dgemm_grid<A_KM, B_KN, true>(g, s);
-  }
-  const bool strips = (Tn > Fn) || (Tm > Fm && !syrk);
-  const bool side = strips && g_gemm_aux.stream != nullptr && Fm * Fn >= 512;
-  hipStream_t es = side ? g_gemm_aux.stream : s; // stream of the edge strips
-  if (side) {
-    if ((e = hipEventRecord(g_gemm_aux.ready, s)) != hipSuccess) return e;
-    if ((e = hipStreamWaitEvent(es, g_gemm_aux.ready, 0)) != hipSuccess) return e;
-  }
-  GemmArgs ge = g;
-  ge.syrk_upper = 0;
-  if (side) { // strips first on the side stream, the big grid on the caller's stream
-    if (Tn > Fn) { // ragged right strip: all tile rows (SYRK: tm <= Tn-1 is every row)
-      ge.tiles_m = Tm; ge.tiles_n = 1; ge.tm0 = 0; ge.tn0 = Fn;
-      if ((e = launch_dgemm_grid<A_KM, B_KN, false>(ge, es)) != hipSuccess) return e;
-    }
-    if (Tm > Fm && !syrk) { // ragged bottom strip (complete columns only; the corner went with the right strip)
-      ge.tiles_m = 1; ge.tiles_n = Fn; ge.tm0 = Fm; ge.tn0 = 0;
-      if ((e = launch_dgemm_grid<A_KM, B_KN, false>(ge, es)) != hipSuccess) return e;
-    }
-  }
-  // complete tiles: predicate-free kernel (SYRK: the upper triangle of the Fm x Fm complete tiles)
-  g.tiles_m = Fm; g.tiles_n = Fn; g.tm0 = 0; g.tn0 = 0;
-  e = launch_dgemm_grid<A_KM, B_KN, true>(g, s);
-  if (e != hipSuccess) return e;
-  if (side) {
-    if ((e = hipEventRecord(g_gemm_aux.done, es)) != hipSuccess) return e;
-    return hipStreamWaitEvent(s, g_gemm_aux.done, 0);
-  }
-  if (Tn > Fn) {
-    ge.tiles_m = Tm; ge.tiles_n = 1; ge.tm0 = 0; ge.tn0 = Fn;
-    if ((e = launch_dgemm_grid<A_KM, B_KN, false>(ge, s)) != hipSuccess) return e;
-  }
-  if (Tm > Fm && !syrk) {
-    ge.tiles_m = 1; ge.tiles_n = Fn; ge.tm0 = Fm; ge.tn0 = 0;
-    if ((e = launch_dgemm_grid<A_KM, B_KN, false>(ge, s)) != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-// ta/tb in {'N','T'} with the cblas row-major meaning; mirror (with syrk_upper, M == N): the lower triangle is written too, as the
-// transpose of the upper tiles (GemmArgs::mirror)
-static inline hipError_t launch_dgemm(char ta, char tb, long M, long N, long K, double alpha,
-                                      const double *A, long lda, const double *B, long ldb,
-                                      double beta, double *C, long ldc, bool syrk_upper,
-                                      bool square_a, hipStream_t s, bool mirror = false) {
-  GemmArgs g;
-  g.mirror = (mirror && (syrk_upper ? M == N : M <= N)) ? 1 : 0; // without syrk_upper: a row strip of such an update (tiles (0, j) of C: the
-                                                                 // eigensolver's look-ahead); every tile off the diagonal is also written transposed
-  g.A = A; g.B = B; g.C = C;
-  g.M = M; g.N = N; g.K = K;
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.alpha = alpha; g.beta = beta;
-  g.tiles_m = g.tiles_n = 0;
-  g.tm0 = g.tn0 = 0;
-  g.syrk_upper = syrk_upper ? 1 : 0;
-  g.clamp = 0;
-  g.square_a = square_a ? 1 : 0;
-  {
-    static int abl = -1;
-    if (abl < 0) {
-      const char *e = getenv("GEMMA_HIP_GEMM_ABLATE");
-      abl = e ? atoi(e) : 0;
-    }
-    g.ablate = abl;
-    static int gm = -1;
-    if (gm < 0) {
-      const char *e = getenv("GEMMA_HIP_GEMM_GM");
-      gm = e ? atoi(e) : 0;
-    }
-    g.gm = gm;
-  }
-  const bool tA = (ta == 'T' || ta == 't'), tB = (tb == 'T' || tb == 't');
-  // op(A) = A^T  <=> A stored [k][m]  (KM image);  op(B) = B <=> B stored [k][n] (KN image)
-  if (tA && !tB) return launch_dgemm_t<true, true>(g, s);
-  if (tA && tB) return launch_dgemm_t<true, false>(g, s);
-  if (!tA && !tB) return launch_dgemm_t<false, true>(g, s);
-  return launch_dgemm_t<false, false>(g, s);
-}
-
-// How K is cut for launch_dgemm_ksliced: K0 = the part that is whole K-tiles, `per` = length of a slice (a multiple of the K-tile),
-// return = number of slices: every slice is non-empty ((ns - 1) per < K0 <= ns per) and -- when more than one -- at least four K-tiles
-// long except possibly the last.  1 means "do not slice".  (tests/cpp/raster_slices_check.hip runs this for every K <= 40 000.)
-static inline int gemm_kslice_plan(long K, int want, long *K0, long *per) {
-  *K0 = (K / GEMM_BK) * GEMM_BK;
-  *per = *K0;
-  int ns = want < 1 ? 1 : want;
-  while (ns > 1 && *K0 / ns < 4 * GEMM_BK) --ns;
-  if (ns <= 1 || *K0 == 0) return 1;
-  const long kt = *K0 / GEMM_BK, pt = (kt + ns - 1) / ns; // K-tiles in all, per slice
-  ns = (int)((kt + pt - 1) / pt);
-  *per = pt * GEMM_BK;
-  return ns;
-}
-
-// C_ks (ks = 0 .. *nslices - 1, at C + ks * cslice) = alpha op(A) op(B) over the K range of slice ks, ONE launch per kernel
-// variant (interior tiles / edge strips) with the slice in blockIdx.y; the caller adds the slices.  want = slices asked for; the
-// number used (returned in *nslices) keeps every slice at least four K-tiles long.  A K that is not a multiple of the K-tile
-// leaves its last < 16 columns to one extra bounds-checked launch that accumulates into slice 0.
-static inline hipError_t launch_dgemm_ksliced(char ta, char tb, long M, long N, long K, double alpha, const double *A, long lda,
-                                              const double *B, long ldb, double *C, long ldc, long cslice, int want,
-                                              int *nslices, hipStream_t s) {
-  const bool tA = (ta == 'T' || ta == 't'), tB = (tb == 'T' || tb == 't');
-  long K0, per;
-  const int ns = gemm_kslice_plan(K, want, &K0, &per);
-  const long K1 = K - K0;
-  *nslices = ns;
-  if (ns <= 1) return launch_dgemm(ta, tb, M, N, K, alpha, A, lda, B, ldb, 0.0, C, ldc, false, false, s);
-  GemmArgs g;
-  g.A = A; g.B = B; g.C = C;
-  g.M = M; g.N = N; g.K = K0;
-  g.lda = lda; g.ldb = ldb; g.ldc = ldc;
-  g.alpha = alpha; g.beta = 0.0;
-  g.tiles_m = g.tiles_n = 0;
-  g.tm0 = g.tn0 = 0;
-  g.syrk_upper = 0; g.clamp = 0; g.square_a = 0; g.ablate = 0; g.gm = 0;
-  g.kslices = ns; g.kslice = per; g.cslice = cslice;
-  hipError_t e;
-  // op(A) = A^T  <=> A stored [k][m]  (KM image);  op(B) = B <=> B stored [k][n] (KN image)
-  if (tA && !tB) e = launch_dgemm_t<true, true>(g, s);
-  else if (tA && tB) e = launch_dgemm_t<true, false>(g, s);
-  else if (!tA && !tB) e = launch_dgemm_t<false, true>(g, s);
-  else e = launch_dgemm_t<false, false>(g, s);
-  if (e != hipSuccess || K1 == 0) return e;
-  const double *A1 = tA ? A + K0 * lda : A + K0, *B1 = tB ? B + K0 : B + K0 * ldb;
-  return launch_dgemm(ta, tb, M, N, K1, alpha, A1, lda, B1, ldb, 1.0, C, ldc, false, false, s);
 }
 
 } // namespace gemma_hip

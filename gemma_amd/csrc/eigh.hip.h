@@ -31,7 +31,7 @@
 #include <string>
 #include <vector>
 
-#include "dgemm_mfma.hip.h"
+#include "dgemm.h"
 #include "eigh_tu.h" // EighShard
 
 namespace gemma_hip {

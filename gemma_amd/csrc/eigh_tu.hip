@@ -15,7 +15,6 @@
 namespace gemma_hip {
 
 int eigh_device_x(double *G, long n, double *U, double *eval, hipStream_t s, std::string &msg, const EighShard *sh) {
-  gemm_aux_init();
   return eigh_device(G, n, U, eval, s, msg, sh);
 }
 
@@ -26,7 +25,6 @@ void eigh_last_stages(double *t8) {
 }
 
 void eigh_tu_shutdown() {
-  gemm_aux_destroy();
   eig2_lookahead_destroy();
   eig_pool().keep = false;
   (void)eig_pool().drop_idle();
@@ -63,7 +61,6 @@ size_t eigh_pool_idle_bytes_x() { return eig_pool().idle_bytes(); }
 
 // Householder tridiagonalisation only: G (host, n x n) -> d[n], e[n-1], tau[n], VT (n x n, row j = u_j)
 int dbg_tridiag_x(const double *G, size_t n, double *d, double *e, double *tau, double *VT, std::string &msg) {
-  gemm_aux_init();
   EigWs ws;
   ScopedBuf dG; // device copy of G
   const size_t nn = n * n;
@@ -95,7 +92,6 @@ int dbg_tridiag_x(const double *G, size_t n, double *d, double *e, double *tau, 
 // two-stage reduction only (eigh2.hip.h): G (host, n x n, n even, n >= 384) -> band after stage 1 (n x 129: row j holds
 // B(j .. j+128, j)) and the tridiagonal d[n], e[n-1] after the bulge chase
 int dbg_eigh2_x(const double *G, size_t n, double *band, double *d, double *e, std::string &msg) {
-  gemm_aux_init();
   if (n < 3 * (size_t)E2_B || (n & 1)) {
     msg = "n must be even and >= " + std::to_string(3 * E2_B);
     return GEMMA_HIP_EINVAL;
@@ -128,7 +124,6 @@ int dbg_eigh2_x(const double *G, size_t n, double *band, double *d, double *e, s
 
 // divide-and-conquer on a symmetric tridiagonal (host d[n], e[n-1]) -> w[n] ascending, ZT (n x n, row k = eigenvector k)
 int dbg_stedc_x(const double *d, const double *e, size_t n, double *w, double *ZT, std::string &msg) {
-  gemm_aux_init();
   EigWs ws;
   const size_t nn = n * n;
   double *QA = nullptr, *QB = nullptr;

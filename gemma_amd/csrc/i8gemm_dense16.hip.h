@@ -16,6 +16,8 @@
 // accumulator of a block: lane (c16, q) holds rows 4 q + r, column c16.
 #pragma once
 #include "i8gemm.hip.h"
+#define GEMMA_HIP_KERNEL_BODIES // a unit that includes this file instantiates what it launches: i8gemm_dense16.h leaves out its extern templates
+#include "i8gemm_dense16.h"
 
 namespace gemma_hip {
 

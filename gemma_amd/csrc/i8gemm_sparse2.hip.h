@@ -25,45 +25,17 @@
 #include <algorithm>
 #include <vector>
 #include "i8gemm_sparse.hip.h"
+#define GEMMA_HIP_KERNEL_BODIES // a unit that includes this file instantiates what it launches: i8gemm_sparse2.h leaves out its extern templates
+#include "i8gemm_sparse2.h"
 
 namespace gemma_hip {
 
-constexpr int S2_BM = 256, S2_BN = 128;
-constexpr int S2_AMB = 16384;   // records of a K-tile: 256 rows x 4 chunks x 16 B
-constexpr int S2_STAGE = 32768; // + digit tile 128 columns x 128 B
-constexpr int S2_NST = 4;
 #ifndef S2_ADVANCE
 #define S2_ADVANCE 1 // 0: timing experiment only: every K-tile re-reads the first one (cache-hot operands), results wrong
 #endif
 #ifndef S2_LOOPDMA
 #define S2_LOOPDMA 1 // 0: timing experiment only (scripts/i8_kernel_bench.hip): the in-loop LDS-DMA compiled out, results wrong
 #endif
-
-struct Sparse2Args {
-  const uint4 *AM;  // [tile_m][ktile][row % 256][chunk 2 p + h]: {g2(step 2p, h), g2(step 2p+1, h), idx(step 2p+h), kept bits}
-  const int8_t *Bt; // digit d: N x ldk
-  int *C;           // plane q: (2 lpad) x ldc; rows [0, lpad) = G products, [lpad, 2 lpad) = M products
-  long ldk, ldc, strideB, strideC, m_row0;
-  int tiles_m, tiles_n, nk, gm, fuse, digits;
-  int plane0 = 0; // first plane of this launch (i8gemm_sparse2_r16.hip.h: the 7g6m form launches plane 0 and planes 1.. separately)
-  const int2 *tile_map = nullptr; // (tile_m, tile_n) of workgroup blockIdx.x: the cross-XCD raster of s2_build_raster; nullptr:
-                                  // the per-XCD ranges of round 3 (every XCD sweeps its own tile rows)
-  // Blocks without a missing call (round 6): sparse2_meta_kernel leaves *anymiss = 0 for them and the mask product is identically
-  // zero.  The launch site then queues BOTH forms of the 16-row kernel and each one returns at once unless the flag is its own
-  // (run_if 1: only when *anymiss != 0, 2: only when *anymiss == 0, 0: always) -- the choice is made on the device, so the
-  // asynchronous pipeline needs no read-back, and neither K loop changes.
-  const int *anymiss = nullptr;
-  int run_if = 0;
-  // The epilogue instances of the 16-row kernel (i8gemm_sparse2_r16.hip.h, COMBINE) only: the launch is plane 0, planes
-  // nplanes - 1 .. 1 are complete in C, and U^T x = qinv_j * sum_planes (G + mean_s * m_scale * M) goes to UtX (l x ldx, the
-  // first n columns) instead of plane 0 to C.  Every other kernel ignores these.
-  double *UtX = nullptr;
-  long ldx = 0, l = 0, n = 0;
-  const double *mean = nullptr, *qinv = nullptr;
-  double m_scale = 1.0;
-  int nplanes = 0;
-  int epi_depth = 1; // GEMMA_HIP_I8_EPI_DEPTH: > 1 = the fused forms (nplanes 3, 4) read the planes back four steps ahead, 1 = one step
-};
 // Tried in round 4 and dropped: one digit fewer for the MASK product (the mask product sums only the row's missing calls, so
 // five digits keep its worst-case error at the level of the six-digit genotype product: -1/18 of the matrix instructions).  The
 // lowest digit's pass then runs without the sparse instructions; as a second copy of the K loop it made the register allocator
@@ -75,7 +47,7 @@ struct Sparse2Args {
 // packed bytes g | m << 4 (lpad x ldk, lpad a multiple of 256) -> records; one thread per (row, K-tile, chunk)
 __global__ __launch_bounds__(256) void sparse2_meta_kernel(const int8_t *__restrict__ A, long lpad, long ldk,
                                                            uint4 *__restrict__ AM, int *__restrict__ row_surplus,
-                                                           int *anymiss = nullptr /* set to 1 when the block holds a missing call */) {
+                                                           int *anymiss) {
   const long nk = ldk / I8_BK;
   const long id = (long)blockIdx.x * 256 + threadIdx.x;
   if (id >= lpad * nk * 4) return;
@@ -135,51 +107,6 @@ __device__ __forceinline__ i32x4 s2_expand(int bits) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) v[i] = (int)((u >> i) & 0x01010101u);
   return v;
-}
-
-// Cross-XCD raster (round 4).  Workgroup b runs on XCD b % 8 and an XCD takes its workgroups in order, 32 at a time (one per
-// CU: 128 KiB of LDS each).  Round 3 gave every XCD its own contiguous range of tiles -- eight disjoint sweeps: each record
-// panel (2.56 MB per tile row) comes from HBM once per 4-column step of its XCD (39 times per plane) and each digit panel once per
-// 8-row group (10 times), 71 GB per launch behind the L2s.  Here the eight XCDs work on ONE super-patch of rb x 8 tile rows by
-// (8 / rb) x 4 tile columns at a time (XCD x: row block x % rb, column block x / rb; its 32 tiles rows inside, columns outside as
-// before, so the per-XCD L2 patch is unchanged) and the super-patches sweep the columns of a band of rb x 8 tile rows before the
-// next band starts: the band's record panels (rb x 20 MB at n = 20 000) stay in the 256 MiB Infinity Cache for the whole
-// sweep and a digit panel is fetched from HBM once per band and shared by the rb XCDs that need it at the same time.  HBM reads
-// per launch: records once per plane (1.2 GB), digits once per band (24 / rb GB) instead of 71 GB; what the L2s request is
-// unchanged.  Ragged bands / column steps give the XCDs sequences of different lengths: tiles are moved from the tails of the
-// long ones to the short ones until every XCD has exactly the number of workgroups the hardware will hand it.
-static inline void s2_build_raster(int tiles_m, int tiles_n, int rb, std::vector<int2> &map, int PR = 8) {
-  const int NX = 8, PC = 32 / PR; // PR x PC = the 32 tiles an XCD works on at a time (8 x 4 unless an experiment says otherwise)
-  if (rb != 1 && rb != 2 && rb != 4 && rb != 8) rb = 2;
-  const int cbs = NX / rb; // column blocks per super-patch
-  std::vector<std::vector<int2>> seq(NX);
-  for (int band0 = 0, band = 0; band0 < tiles_m; band0 += rb * PR, ++band)
-    for (int col0 = 0; col0 < tiles_n; col0 += cbs * PC)
-      for (int xx = 0; xx < NX; ++xx) {
-        const int x = (xx + band) % NX; // the XCDs that get the short blocks of a ragged last column step change from band to band
-        const int r0 = band0 + (xx % rb) * PR, c0 = col0 + (xx / rb) * PC;
-        const int nr = std::min(PR, std::min(tiles_m, band0 + rb * PR) - r0), nc = std::min(PC, std::min(tiles_n, col0 + cbs * PC) - c0);
-        if (nr <= 0 || nc <= 0) continue;
-        for (int c = 0; c < nc; ++c)
-          for (int r = 0; r < nr; ++r) seq[x].push_back(make_int2(r0 + r, c0 + c));
-      }
-  const int total = tiles_m * tiles_n;
-  std::vector<int> want(NX);
-  for (int x = 0; x < NX; ++x) want[x] = total / NX + (x < total % NX ? 1 : 0);
-  std::vector<int2> spare;
-  for (int x = 0; x < NX; ++x)
-    while ((int)seq[x].size() > want[x]) {
-      spare.push_back(seq[x].back());
-      seq[x].pop_back();
-    }
-  for (int x = 0; x < NX; ++x)
-    while ((int)seq[x].size() < want[x]) {
-      seq[x].push_back(spare.back());
-      spare.pop_back();
-    }
-  map.assign((size_t)total, make_int2(0, 0));
-  for (int x = 0; x < NX; ++x)
-    for (int o = 0; o < want[x]; ++o) map[(size_t)o * NX + x] = seq[x][o];
 }
 
 // NI: 32-row blocks per wavefront.  NI = 2: wavefronts 4 (rows) x 2 (columns), 2 x 2 blocks each (the first form of the kernel).
@@ -453,14 +380,5 @@ __global__ __launch_bounds__(512, 2) void i8gemm_sparse2_kernel_t(Sparse2Args g)
       }
     }
 }
-
-// the shipped form: wavefronts 8 x 1 (54.4-55.0 ms against 56.5 for 4 x 2 in the same session, profiles/r03_i8_sparse_ablation.txt)
-#ifndef S2_DEFAULT_RASTER
-#define S2_DEFAULT_RASTER 1 // row blocks of the cross-XCD super-patch (0: the per-XCD ranges of round 3)
-#endif
-#ifndef S2_DEFAULT_NI
-#define S2_DEFAULT_NI 1
-#endif
-static constexpr auto i8gemm_sparse2_kernel = i8gemm_sparse2_kernel_t<S2_DEFAULT_NI>;
 
 } // namespace gemma_hip

@@ -25,19 +25,13 @@
 #pragma once
 #include <type_traits>
 #include "i8gemm_sparse2.hip.h"
+#include "i8gemm_sparse2_r16.h"
 
 #ifndef S2_R16_PREP_SPREAD
 #define S2_R16_PREP_SPREAD 0
 #endif
 // timing experiments only (scripts/i8_kernel_bench.hip, round 6 power table): the sparse (mask) / the dense (genotype) matrix
 // instructions compiled out -- results wrong, everything else of the loop (LDS reads, LDS-DMA, operand preparation) unchanged
-// LDS stages of the K pipeline (S2_STAGE = 32 KiB each): LDS-DMA runs S2_R16_NST - 1 K-tiles ahead.  4 = rounds 3-5; 5 fills the
-// CU's 160 KiB exactly: 128 instead of 96 KiB of operands in flight per CU.  Round 6: the loop's data side is bound by
-// (bytes in flight) / (latency of an L2 miss served across the fabric) -- profiles/r06_power_table.txt: with the dense matrix
-// instructions compiled out the same loop still takes 29 ms for its 382 GB of LDS-DMA = 53 GB/s per CU = 96 KiB per ~1.8 us.
-#ifndef S2_R16_NST
-#define S2_R16_NST 4
-#endif
 #ifndef S2_R16_ABL_NO_S
 #define S2_R16_ABL_NO_S 0
 #endif
@@ -46,9 +40,6 @@
 #endif
 
 namespace gemma_hip {
-
-constexpr int S2_R16_LDS = S2_R16_NST * S2_STAGE; // dynamic LDS of a launch
-static_assert(S2_R16_LDS >= 16 * 512 * 16, "the epilogue parks 16 x 16 bytes per lane of the mask accumulators in the launch's LDS");
 
 // WITH_S = false: the genotype product alone (round 6, the "7g6m" form: the lowest of seven digits is multiplied with the genotypes
 // only -- its mask term is below the rounding of the other six): no sparse instruction, no mask accumulators, no M rows

@@ -4,32 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#define GEMMA_HIP_KERNEL_BODIES // a unit that includes this file instantiates what it launches: ingest.h leaves out its extern templates
+#include "ingest.h"
 
 namespace gemma_hip {
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
-// PLINK 2-bit code -> genotype (GEMMA src/lmm.cpp:1797-1812; src/gemma_io.cpp:1665-1682):
-// v = b0 + 2*b1 : 0 -> 2, 2 -> 1, 3 -> 0, 1 -> missing
-__device__ __forceinline__ double plink_value(unsigned v, bool &missing) {
-  missing = (v == 1u);
-  return (v == 0u) ? 2.0 : (v == 2u) ? 1.0 : 0.0;
-}
-
-struct IngestArgs {
-  const void *src;    // f64 (ld doubles per SNP) or bytes (ld bytes per SNP)
-  long ld;
-  long l;
-  const int *idx_map; // PLINK: position in ni_total of analysed individual j (nullptr = identity)
-  int n;              // individuals written per SNP
-  double *dst;        // l x ldo, SNP-major
-  long ldo;
-  int k_mode;         // kinship only: 1 centred, 2 standardised
-};
 
 // LMM ingest: mean-impute only, no centring (GEMMA src/lmm.cpp:1590-1618, :1819-1827).
 template <bool PLINK>
@@ -70,19 +48,6 @@ __global__ __launch_bounds__(256) void ingest_lmm_kernel(IngestArgs g) {
     d[i] = miss ? mean : v;
   }
 }
-
-// GXE ingest (GEMMA src/lmm.cpp:2316-2361 BIMBAM, :2487-2536 PLINK): mean-impute, recode 2 - x when x_mean > 1,
-// and also write z = x . env; flip[s] records the recoding (beta changes sign, :2403 / :2584).
-struct IngestGxeArgs {
-  const void *src;
-  long ld, l;
-  const int *idx_map;
-  int n;
-  const double *env; // n
-  double *X, *Z;     // l x ldo each
-  long ldo;
-  int *flip;
-};
 template <bool PLINK>
 __global__ __launch_bounds__(256) void ingest_gxe_kernel(IngestGxeArgs g) {
   const int lane = threadIdx.x & 63;
@@ -261,11 +226,6 @@ __global__ void zero_small_eval_kernel(double *eval, long n, double *trace) {
     *trace = t / (double)n;
   }
 }
-
-// AnalyzePlink's stale beta/se when CalcRLWald was skipped (GEMMA src/lmm.cpp:1725,1870):
-// a failed SNP (NaN logl_H1, a_mode 1) reports the beta/se of the nearest preceding SNP that
-// did run CalcRLWald; carry_in covers the previous batch, carry_out receives the batch's last.
-struct SumStatRaw { double v[8]; };
 __global__ void plink_carry_kernel(SumStatRaw *out, long l, const double *carry_in,
                                    double *carry_out) {
   const long s = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -280,6 +240,13 @@ __global__ void plink_carry_kernel(SumStatRaw *out, long l, const double *carry_
     out[s].v[1] = e;
   }
   if (s == l - 1) { carry_out[0] = b; carry_out[1] = e; }
+}
+
+// the analysed individuals' rows and columns of the kept kinship: G (n x n) = K[map][map] (device-resident chain, abi_kept_comm.inc.h)
+__global__ void subselect_kernel(const double *__restrict__ K, long ni_total, const int *__restrict__ map, long n,
+                                 double *__restrict__ G) {
+  const long c = (long)blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y;
+  if (c < n) G[r * n + c] = K[(long)map[r] * ni_total + map[c]];
 }
 
 } // namespace gemma_hip

@@ -19,12 +19,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "ingest.hip.h"
+#define GEMMA_HIP_KERNEL_BODIES // a unit that includes this file instantiates what it launches: kin_i8.h leaves out its extern templates
+#include "kin_i8.h"
 
 namespace gemma_hip {
-
-constexpr int KI8_SEG = 4096;  // individuals i per block of the correction kernel (16 per thread)
-constexpr int KI8_LIST = 4096; // SNPs listed per pass (LDS); a block walks the SNP axis in ranges of this many rows
 
 // A (l x ldk, SNP-major, byte = g | m << 4) -> At (individual-major, byte as A) and Gt (individual-major, byte = g):
 // rows i < n_rows_out (zero beyond n), ldl bytes per row (zero beyond l)
@@ -57,17 +55,6 @@ __global__ void kin_i8_accum_kernel(const int *__restrict__ C, long ldc, long n,
   const long iend = ((long)blockIdx.x + 1) * 256 < n ? ((long)blockIdx.x + 1) * 256 : n;
   for (long i = blockIdx.y; i < iend; i += gridDim.y) acc[i * n + j] += (double)C[i * ldc + j];
 }
-
-struct KinCorrArgs {
-  const int8_t *A;   // l x ldk, SNP-major packed (g | m << 4)
-  const int8_t *At;  // individual-major packed, ldl bytes per row
-  const double *mean; // l
-  long l, ldk, ldl, n;
-  double *S;     // n x n, row j: S[j][i]
-  double *a;     // n
-  double *smu2;  // 1
-  const int *lists_ok; // device flag of kin_i8_scan_kernel (nullptr: always run)
-};
 
 // grid (n individuals j, ceil(n / KI8_SEG) ranges of i), 256 threads
 __global__ __launch_bounds__(256) void kin_i8_corr_kernel(KinCorrArgs g) {
@@ -235,17 +222,6 @@ __global__ __launch_bounds__(256) void kin_i8_count_kernel(const int8_t *__restr
   for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off, 64);
   if (lane == 0) cnt[r] = c;
 }
-
-// exclusive scans of the two count arrays (one block of 1024 threads), the decision whether the lists fit, sum mu^2
-struct KinScanArgs {
-  const int *cntS, *cntJ;
-  int *offS, *offJ; // l + 1, n + 1
-  long l, n;
-  long cap;         // entries either list buffer holds
-  int *ok;          // out: 1 = lists are valid
-  const double *mean;
-  double *smu2;     // += sum mu_s^2 when ok
-};
 __device__ __forceinline__ long ki8_block_scan_1024(long v, long *sh /* 16 */, long &total) {
   // exclusive prefix of v over the 1024 threads of the block; total = the sum
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -382,21 +358,6 @@ __global__ __launch_bounds__(256) void kin_i8_sub_kernel(const int *__restrict__
   }
   sub[id] = lo;
 }
-
-constexpr double KI8_FIX = 17592186044416.0; // 2^44: fixed point of the both-missing term
-struct KinCorr2Args {
-  const unsigned *A2; // l x ld2 dwords, ld2 = 256 nseg
-  long ld2;
-  const double *mean;
-  long n;
-  const int *offJ, *listJ, *offS, *listS, *sub;
-  int nseg;
-  const double *cj;
-  double *S; // n x n, row j: S[j][i]
-  const int *ok;
-  int dbg_skip_pairs; // timing experiments only (GEMMA_HIP_KIN_DBG=1): the both-missing term left out, results wrong
-  int dbg_skip_main;  // (GEMMA_HIP_KIN_DBG=2): the genotype term left out
-};
 // grid (n individuals j, ceil(n / KI8_SEG) ranges of i), 256 threads: thread t owns i = i0 + 256 q + t, q = 0 .. 15 (one dword of A2)
 __global__ __launch_bounds__(256) void kin_i8_corr2_kernel(KinCorr2Args g) {
   __shared__ unsigned long long trow[KI8_SEG];

@@ -7,23 +7,9 @@
 #include <math.h>
 
 #include "lmm_assoc.hip.h"
+#include "lm_assoc.h"
 
 namespace gemma_hip {
-
-constexpr int LM_CMAX = 16;
-
-struct LmArgs {
-  const double *X; // l x ld, SNP-major, imputed
-  long ld, l;
-  const double *Wt;   // c x n
-  const double *y;    // n
-  const double *WtWi; // c x c
-  const double *Wty;  // c
-  double yPwy;
-  int n, c, test_mode; // test_mode = a_mode - 50
-  double lnbeta_half_df;
-  SumStat *out;
-};
 
 __global__ __launch_bounds__(256) void lm_assoc_kernel(LmArgs g) {
   __shared__ double swtx[4][LM_CMAX];

@@ -6,11 +6,10 @@
 #pragma once
 #include "lmm_assoc.hip.h"
 #include "lmm_score_panel.hip.h"
+#define GEMMA_HIP_KERNEL_BODIES // a unit that includes this file instantiates what it launches: lmm_null_panel.h leaves out its extern templates
+#include "lmm_null_panel.h"
 
 namespace gemma_hip {
-
-constexpr int NP_WAVES = 4;     // wavefronts (phenotypes) per workgroup of the FixedC and GenericC forms; the last workgroup is ragged
-constexpr int NP_CMAX = SP_CMAX; // covariates of the optional beta / se(beta) output
 
 template <int CP>
 __global__ __launch_bounds__(64 * NP_WAVES) void lmm_null_panel_kernel(AssocArgs g, const double *__restrict__ Yt, int T,
@@ -53,9 +52,6 @@ __device__ __forceinline__ double rounded(double v) {
   asm volatile("" : "+v"(v));
   return v;
 }
-struct NullFit8 {
-  double l_mle_null, logl_mle_H0, l_remle_null, logl_remle_H0, pve, pve_se, vg_remle, ve_remle;
-};
 __global__ __launch_bounds__(256) void null_panel_derive_kernel(const NullOut *__restrict__ in, int T, double trace_G, double df,
                                                                NullFit8 *__restrict__ fit) {
   const int t = (int)blockIdx.x * 256 + (int)threadIdx.x;

@@ -15,7 +15,7 @@
 #include "../../include/gemma_hip.h"
 #include "tu_common.h"
 #include "host_linalg.h"
-#include "dgemm_mfma.hip.h"
+#include "dgemm.h"
 #include "mqs.hip.h"
 #include "ci.hip.h"
 #include "mqs_tu.h"
@@ -101,7 +101,6 @@ void mqs_release_x() {
 void mqs_tu_shutdown() {
   mqs_release_x();
   ci_release_x();
-  gemm_aux_destroy();
 }
 
 bool mqs_active_x() { return g_mqs.active; }
@@ -143,7 +142,6 @@ int mqs_begin_x(long ni_total, const int *indicator, int n_vc, const double *W, 
     g_mqs.A.release(); g_mqs.idx.release(); g_mqs.Wt.release(); g_mqs.Wi.release();
     g_mqs.haveA = false;
   }
-  gemm_aux_init();
   const long ld = (n + 1) & ~1L;
   g_mqs.n = n;
   g_mqs.ni_total = ni_total;
@@ -446,7 +444,6 @@ int ci_begin_x(long ni_total, const int *indicator, int n_vc, std::string &msg) 
   }
   TU_CHK(hipDeviceSynchronize());
   ci_release_x();
-  gemm_aux_init();
   const long words = (ni_total + 15) / 16;
   std::vector<unsigned> am((size_t)words, 0u);
   for (int p : idx) am[(size_t)(p >> 4)] |= 1u << (2 * (p & 15));

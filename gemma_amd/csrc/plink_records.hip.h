@@ -16,6 +16,7 @@
 #include <stdint.h>
 #if defined(__HIPCC__)
 #include "i8gemm_sparse2.hip.h"
+#include "plink_records.h"
 #define PR_HD __host__ __device__ __forceinline__
 #else
 #define PR_HD inline
@@ -113,17 +114,6 @@ PR_HD int pr_record(Word word, long kt, int c, long n, unsigned w[4], int *tot, 
 }
 
 #if defined(__HIPCC__)
-struct PlinkRecordsArgs {
-  const unsigned char *src; // l rows of ld bytes, four calls a byte
-  long ld, l, lpad;         // lpad: a multiple of S2_BM; rows l .. lpad are written as padding
-  int n;
-  long ldk;                 // a multiple of I8_BK
-  uint4 *AM;                // [tile_m][ktile][row % 256][chunk]
-  int *row_surplus;         // lpad counters, each written here
-  int *anymiss;             // nullptr, or the block's any-missing flag (zeroed by the caller)
-  double *mean;             // l
-};
-
 // the .bed word of calls 16 k .. 16 k + 15 of a row of nbytes bytes; bytes behind the row read as 0
 __device__ __forceinline__ unsigned pr_load(const unsigned char *bs, long k, long nbytes, bool aligned) {
   const long o = 4 * k;

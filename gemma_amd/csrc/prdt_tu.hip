@@ -15,7 +15,7 @@
 
 #include "../../include/gemma_hip.h"
 #include "tu_common.h"
-#include "dgemm_mfma.hip.h"
+#include "dgemm.h"
 #include "eigh_tu.h"
 #include "geno_mv.hip.h"
 #include "spd_inv.hip.h"
@@ -88,11 +88,6 @@ struct PrdtState {
   DevBuf y, work, stage_in, stage_w, used, dense;
 } g_pd;
 
-bool g_aux = false;
-void aux_init() {
-  if (!g_aux) gemm_aux_init();
-  g_aux = true;
-}
 
 // r_full of the current groups (zeros at the other individuals and in the padding)
 int ridge_scatter(std::string &msg) {
@@ -203,7 +198,6 @@ int ridge_set_r_x(long n, const double *r, double scale, std::string &msg) {
 int ridge_setup_x(long n, const double *U, long ldu, const double *eval, bool ue_device, const double *Uty, bool uty_device, double lambda,
                   long ns_test, double *bv_out, hipStream_t s, std::string &msg) {
   g_rg.ready = false;
-  aux_init();
   // dense: [U copy n x ldc | eval n | Uty n | B n x 2 | C n x 2]
   const long ldc = ue_device ? 0 : ((n + 1) & ~1L);
   int rc = g_rg.dense.reserve((size_t)(n * ldc + 6 * n) * 8, "prdt", msg);
@@ -335,7 +329,6 @@ int prdt_add_x(int geno_kind, const void *geno, long l, long ld, bool device, co
 }
 
 int prdt_add_bv_x(const double *G, long ni_total, long ldg, bool device, const double *u_hat, hipStream_t s, std::string &msg) {
-  aux_init();
   Groups &gr = g_pd.grp;
   const long no = gr.n_a, nf = gr.n_b;
   if (no == 0 || nf == 0) return GEMMA_HIP_OK; // nothing to predict from or for
@@ -491,7 +484,6 @@ int prdt_mv_sub_x(const double *Gd, long ldg, const int *pos, long n, double *ou
 
 int prdt_mv_apply_x(long ni, long d, const double *G, long ldg, int g_where, const int *ind, const double *W, long c, const double *Y,
                     const double *Vg, const double *Ve, const double *B, double *y_miss, long *bad_pivot, hipStream_t s, std::string &msg) {
-  aux_init();
   MvLists l;
   l.set(ind, ni, d);
   const long N = (long)l.oi.size(), M = (long)l.mi.size();
@@ -567,7 +559,6 @@ int prdt_mv_dbg_assemble_x(long ni, long d, const double *Gc_host, const int *in
 // tests and the probe: A x = r by the factor + solve path.  Device form: A (n x n, lda; upper triangle read, the factor left in
 // place) and x (r in, the solution out) on the device; host form: both on the host, A dense and not changed.
 int prdt_mv_dbg_solve_x(double *A, long n, long lda, double *x, bool device, long *bad_pivot, hipStream_t s, std::string &msg) {
-  aux_init();
   if (device) return spd_factor_solve_device(A, n, lda, x, nullptr, bad_pivot, g_mv.spd, "spd_solve", s, msg);
   const long ld = (n + 1) & ~1L;
   int rc;
@@ -584,8 +575,6 @@ void prdt_tu_shutdown() {
   ridge_finish_x();
   prdt_release();
   prdt_mv_release_x();
-  if (g_aux) gemm_aux_destroy();
-  g_aux = false;
 }
 
 } // namespace gemma_hip

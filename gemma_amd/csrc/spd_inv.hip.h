@@ -22,7 +22,7 @@
 #include <string>
 #include <vector>
 
-#include "dgemm_mfma.hip.h"
+#include "dgemm.h"
 
 namespace gemma_hip {
 

@@ -168,7 +168,6 @@ double vector_var(const std::vector<double> &v) { // VectorVar, src/mathfunc.cpp
 } // namespace
 
 int spd_inverse_x(double *A, long n, long lda, double *logdet, long *bad_pivot, hipStream_t s, std::string &msg) {
-  gemm_aux_init();
   const bool inplace = (lda % 2) == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0;
   if (inplace) return spd_inverse_device(A, n, lda, logdet, bad_pivot, g_vc.spd, s, msg);
   const long ld = (n + 1) & ~1L; // odd leading dimension: through an aligned copy
@@ -199,13 +198,11 @@ void vc_tu_shutdown() {
   for (auto &e : g_vc.ev)
     if (e) (void)hipEventDestroy(e);
   for (auto &e : g_vc.ev) e = nullptr;
-  gemm_aux_destroy();
 }
 
 int vc_setup_x(long n, int n_vc, const double *const *K, long ldk, bool device, const double *W, int c, const double *y,
                std::string &msg) {
   vc_release_x();
-  gemm_aux_init();
   if (!g_vc.ev[0])
     for (auto &e : g_vc.ev) TU_CHK(hipEventCreate(&e));
   g_vc.n = n;
