@@ -1,5 +1,5 @@
 // Part of gemma_hip.hip (ONE translation unit: the parts share the context g_ctx and the helpers of its anonymous namespace, and are
-// included there in this order; round 6: the 3 500-line file cut along its stages for reading -- no behaviour change).
+// included there in this order).
 // This part: GXE, host-pointer batch, dbg_utx, the linear model (-lm) with its release list (lm_release), the null model, lmm_finish.
 
 // ---- GXE variants: LMM::AnalyzeBimbamGXE / AnalyzePlinkGXE, src/lmm.cpp:2283-2608

@@ -1,5 +1,5 @@
 // Part of gemma_hip.hip (ONE translation unit: the parts share the context g_ctx and the helpers of its anonymous namespace, and are
-// included there in this order; round 6: the 3 500-line file cut along its stages for reading -- no behaviour change).
+// included there in this order).
 // This part: device-resident chain (kin_end_keep -> eigh_kept_K -> lmm_setup_kept: single_setup of abi_lmm_stage.inc.h on the kept U), pinned
 // host-block pipeline (its own buffers, streams and events; the geometry from block_geom), the communicator, diagnostics.
 

@@ -1,5 +1,5 @@
 // Part of gemma_hip.hip (ONE translation unit: the parts share the context g_ctx and the helpers of its anonymous namespace, and are
-// included there in this order; round 6: the 3 500-line file cut along its stages for reading -- no behaviour change).
+// included there in this order).
 // This part: kinship: PARAM::CalcKin -> BimbamKin / PlinkKin (gemma_hip_kin_begin / kin_add / kin_end), the exact-integer path of hard calls,
 // the release list of the kinship state (kin_release).  Blocks are checked by block_geom (abi_host_block.inc.h).
 

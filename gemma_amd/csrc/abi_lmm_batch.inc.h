@@ -1,5 +1,5 @@
 // Part of gemma_hip.hip (ONE translation unit: the parts share the context g_ctx and the helpers of its anonymous namespace, and are
-// included there in this order; round 6: the 3 500-line file cut along its stages for reading -- no behaviour change).
+// included there in this order).
 // This part: batch entry points: the fp64 ingest (ingest_f64), compute_utx, the two-block pipeline, gemma_hip_lmm_batch_d, -gene.
 
 // ---- stream / buffer plumbing of gemma_hip_lmm_batch_pipe_d (the two-block pipeline, described where that entry point is defined)
@@ -172,15 +172,8 @@ static int compute_utx(int kind, const void *geno, size_t l, size_t ld, int path
 // (product 55.7, combine 2.8, per-SNP stage 3.2); four chunks on two streams 64.2 ms -- the product takes 61.1 ms with the side
 // stream's kernels among its workgroups (every CU slot and every watt they take is the product's), the per-SNP stage 10.5 ms;
 // two chunks 63.3, eight 64.0.  The chip is at its power limit under the product alone, so concurrency is a zero-sum game
-// here.  The path stays behind GEMMA_HIP_OVERLAP=1 (GEMMA_HIP_OVERLAP_CHUNKS, default 4), off by default, with its test.
-static int overlap_chunks(size_t l) {
-  if (!g_ctx.knobs.overlap) return 1;
-  if (utx_i8_mode() != 1 || i8_sparse_mode() != 2) return 1;
-  int q = g_ctx.knobs.overlap_chunks;
-  q = std::max(1, std::min(q, 16));
-  while (q > 1 && l < (size_t)q * 2 * S2_BM) --q; // at least two tile rows per chunk
-  return q;
-}
+// here.  The path stays behind GEMMA_HIP_OVERLAP=1 (GEMMA_HIP_OVERLAP_CHUNKS, default 4), off by default, with its test; i8_chunks
+// (i8_plan.h) says into how many pieces a block is cut.
 static int overlap_init() {
   if (g_ctx.ov_stream) return GEMMA_HIP_OK;
   HIPCHK(hipStreamCreateWithFlags(&g_ctx.ov_stream, hipStreamNonBlocking));
@@ -197,10 +190,10 @@ static int lmm_batch_plink_chunked(const void *geno, size_t l, size_t ld, gemma_
   double *UtX = g_ctx.UtX.as<double>();
   g_ctx.last_utx_path = 1;
   I8Dims d;
-  const bool direct = i8_plink_direct(); // the side stream's surplus kernels then read geno: it is the caller's until this call's
-                                         // work is done, and s waits for the side stream below
-  if ((rc = i8_begin(l, &d, s, true, !direct))) return rc;
-  if ((rc = i8_plink_left(geno, l, ld, d, s, direct))) return rc;
+  // the direct form is allowed: the side stream's surplus kernels then read geno, which is the caller's until this call's work is
+  // done, and s waits for the side stream below
+  if ((rc = i8_begin(l, &d, s, true, true))) return rc;
+  if ((rc = i8_plink_left(geno, l, ld, d, s))) return rc;
   const size_t per = round_up((l + chunks - 1) / chunks, (size_t)S2_BM);
   hipStream_t side = g_ctx.ov_stream;
   int c = 0;
@@ -223,7 +216,7 @@ static int lmm_batch_plink_chunked(const void *geno, size_t l, size_t ld, gemma_
 // ---- two blocks in flight on a CU partition (round 5) -----------------------------------------------------------------------
 // A step of the PLINK path is the int8 product (50 ms at n = B = 20 000: matrix pipe, power) followed by the digit combine and the
 // per-SNP stage (5.6 ms: HBM and latency, the matrix pipe idle).  Side by side on ALL CUs they only take each other's slots and watts
-// (round 3: 62.7 -> 64.2 ms, overlap_chunks above).  This entry point puts them on a PARTITION of the CUs
+// (round 3: 62.7 -> 64.2 ms, lmm_batch_plink_chunked above).  This entry point puts them on a PARTITION of the CUs
 // (hipExtStreamCreateWithCUMask): block i + 1's ingest, records and product on stream P (all but GEMMA_HIP_PIPE_CUS CUs, the same
 // number taken out of every XCD) while block i's combine and per-SNP stage run on stream Q (those CUs):
 //   caller's stream s --in_ready--> P: [wait post_done(i - 1: same buffer set)] ingest, records, product --prod_done(i)--> Q: combine,
@@ -252,7 +245,7 @@ extern "C" int gemma_hip_lmm_batch_pipe_d(int kind, const void *geno, size_t l, 
   int rc = block_geom("lmm_batch_pipe", kind, g_ctx.cfg.n, true, geno, l, ld, out_d);
   if (rc) return rc;
   hipStream_t s = S(stream);
-  if (kind != GEMMA_GENO_PLINK_2BIT || utx_i8_mode() != 1 || i8_sparse_mode() != 2) {
+  if (!i8_pipe_eligible(g_ctx.knobs.i8, kind)) {
     // nothing to pipeline on this path: the plain batch, behind whatever is still in flight
     if ((rc = xp_flush(s))) return rc;
     return gemma_hip_lmm_batch_d(kind, geno, l, ld, out_d, stream);
@@ -285,10 +278,11 @@ extern "C" int gemma_hip_lmm_batch_pipe_d(int kind, const void *geno, size_t l, 
   I8Dims d;
   // the separate combine stays here: ONE g_ctx.UtX serves both blocks in flight, and this block's product must not write it while
   // the block before is read from it on Q
-  if ((rc = i8_begin(l, &d, x.P, false))) return xp_abort(rc);
-  // The byte matrix stays here whatever GEMMA_HIP_I8_DIRECT says: the caller may overwrite geno as soon as ingest_done has passed,
-  // long before this block's surplus kernels run on Q -- they need a copy of the missing pattern, and the bytes are one
-  if ((rc = i8_plink_left(geno, l, ld, d, x.P, false, x.ingest_done))) return xp_abort(rc);
+  if ((rc = i8_begin(l, &d, x.P, false, false))) return xp_abort(rc);
+  // The byte matrix stays here whatever GEMMA_HIP_I8_DIRECT says (allow_direct = false): the caller may overwrite geno as soon as
+  // ingest_done has passed, long before this block's surplus kernels run on Q -- they need a copy of the missing pattern, and the
+  // bytes are one
+  if ((rc = i8_plink_left(geno, l, ld, d, x.P, x.ingest_done))) return xp_abort(rc);
   x.ingest_valid = true;
   if ((rc = i8_gemm_rows(d, 0, d.lpad, x.P))) return xp_abort(rc);
   HIPCHK(hipEventRecord(x.prod_done[slot], x.P));
@@ -315,7 +309,7 @@ extern "C" int gemma_hip_lmm_batch_d(int kind, const void *geno, size_t l, size_
   hipStream_t s = S(stream);
   if ((rc = xp_flush(s))) return rc; // blocks of gemma_hip_lmm_batch_pipe_d still in flight share this call's buffers
   if (kind == GEMMA_GENO_PLINK_2BIT) {
-    const int chunks = overlap_chunks(l);
+    const int chunks = i8_chunks(g_ctx.knobs.i8, l);
     if (chunks > 1) return lmm_batch_plink_chunked(geno, l, ld, out_d, chunks, s);
   }
   double *UtX;

@@ -1,5 +1,5 @@
 // Part of gemma_hip.hip (ONE translation unit: the parts share the context g_ctx and the helpers of its anonymous namespace, and are
-// included there in this order; round 6: the 3 500-line file cut along its stages for reading -- no behaviour change).
+// included there in this order).
 // This part: the per-SNP stage of LMM::Analyze: the release list of the LMM state (lmm_release), the part every setup shares
 // (lmm_common_setup, lmm_bind: U, eval, UtW, UtY from device pointers, host arrays or the kept U), lmm_setup*, fixed-lambda tables,
 // Chebyshev series, launch_assoc.
@@ -613,7 +613,7 @@ extern "C" int gemma_hip_lmm_assoc_d(const double *UtX_d, size_t l, size_t ld_ut
 // GEMMA_HIP_UTX_I8: 1 (default) = hard-call batches (PLINK 2-bit; fp64 input whose rows hold only 0/1/2 and one
 // missing / imputed value) go through the exact int8-digit product (i8gemm.hip.h), 0 = always the fp64 MFMA GEMM.
 // Real-valued dosages always take the fp64 GEMM.
-static int utx_i8_mode() { return g_ctx.knobs.utx_i8; }
+static int utx_i8_mode() { return g_ctx.knobs.i8.utx_i8; }
 
 // which matrix kernel the product of the batch launched (gemma_hip_dbg_last_utx_kernel): bench.py labels its roofline from this,
 // not from the environment

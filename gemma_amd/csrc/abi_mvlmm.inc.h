@@ -1,5 +1,5 @@
 // Part of gemma_hip.hip (ONE translation unit: the parts share the context g_ctx and the helpers of its anonymous namespace, and are
-// included there in this order; round 6: the 3 500-line file cut along its stages for reading -- no behaviour change).
+// included there in this order).
 // This part: multivariate LMM ABI (kernels in mvlmm_kernels*.hip); the host form of a block is host_batch (abi_host_block.inc.h).
 
 // ---- multivariate LMM: MVLMM::AnalyzeBimbam / AnalyzePlink, src/mvlmm.cpp:2972-3899 (kernels in mvlmm_kernels.hip)

@@ -37,6 +37,7 @@
 #include "mvlmm.hip.h"
 #include "comm.hip.h"
 #include "kin_i8.h"
+#include "i8_plan.h"
 
 using namespace gemma_hip;
 
@@ -53,23 +54,11 @@ struct StageProf {
 // libc's lock; round 4 had three of them on every records-kernel launch).  Tests and bench legs that flip a switch between
 // two batches of one setup call gemma_hip_reload_env().
 struct Knobs {
-  int utx_i8 = 1;          // GEMMA_HIP_UTX_I8: 1 = hard-call batches through the exact int8-digit product, 0 = always the fp64 GEMM
+  I8Switches i8;           // the switches the form of the int8 U^T x depends on (i8_plan.h)
   int i8_digits = 0;       // GEMMA_HIP_I8_DIGITS: 6 | 7 forces the digit count (0: by n)
-  int i8_sparse = 2;       // GEMMA_HIP_I8_SPARSE: 0 dense mask product, 1 sparse MFMA on byte genotypes, 2 records kernel
-  int i8_fuse = 1;         // GEMMA_HIP_I8_FUSE: 0 = one int32 plane per digit
-  int i8_gm = 0;           // GEMMA_HIP_I8_GM: tile rows per L2 patch of the non-rastered launch
-  int i8_raster = S2_DEFAULT_RASTER; // GEMMA_HIP_I8_RASTER
-  int i8_rows = 16;        // GEMMA_HIP_I8_ROWS: 32 = the records kernel on the 32-row matrix instructions
   int i8_scale_max = 1;    // GEMMA_HIP_I8_SCALE: "pow2" = columns of U scaled by a power of two (rounds 1-5); default: by their exact maximum
-  int i8_mdrop = 0;        // GEMMA_HIP_I8_FORM=7g6m: seven digits for the genotype product, the mask product on the upper six
-  int i8_complete = 1;     // GEMMA_HIP_I8_COMPLETE: 0 = blocks without a missing call take the mask product like any other block
-  int i8_epilogue = 1;     // GEMMA_HIP_I8_EPILOGUE: 0 = every digit plane to memory and the digit combine as a pass of its own
-  int i8_epi_depth = 4;    // GEMMA_HIP_I8_EPI_DEPTH: 1 = the epilogue of the records kernel reads the planes back one step ahead (round 7)
-  int i8_direct = 1;       // GEMMA_HIP_I8_DIRECT: 0 = PLINK blocks reach the records through the byte matrix (ingest_i8_kernel + sparse2_meta_kernel)
   int dosage_i8 = 1;       // GEMMA_HIP_UTX_DOSAGE_I8
   int dosage_rows = 16;    // GEMMA_HIP_DOSAGE_ROWS: 32 = the dosage planes on the 32-row dense kernel (rounds 3-4)
-  int overlap = 0;         // GEMMA_HIP_OVERLAP
-  int overlap_chunks = 4;  // GEMMA_HIP_OVERLAP_CHUNKS
   int table_v2 = 1;        // GEMMA_HIP_TABLE_V2
   int table_pf = 0;        // GEMMA_HIP_TABLE_PF
   int multi_table = 1;     // GEMMA_HIP_MULTI_TABLE: 0 = gemma_hip_lmm_multi_batch computes every phenotype's fixed-lambda table on its own
@@ -84,34 +73,34 @@ struct Knobs {
     return (e && *e) ? atoi(e) : dflt;
   }
   void load() {
-    utx_i8 = geti("GEMMA_HIP_UTX_I8", 1);
+    i8.utx_i8 = geti("GEMMA_HIP_UTX_I8", 1);
     const int dg = geti("GEMMA_HIP_I8_DIGITS", 0);
     i8_digits = (dg == 6 || dg == 7) ? dg : 0;
     const char *es = getenv("GEMMA_HIP_I8_SPARSE");
-    i8_sparse = (es && es[0] >= '0' && es[0] <= '2') ? es[0] - '0' : 2;
+    i8.sparse = (es && es[0] >= '0' && es[0] <= '2') ? es[0] - '0' : 2;
     const char *ef = getenv("GEMMA_HIP_I8_FUSE");
-    i8_fuse = (ef && ef[0] == '0') ? 0 : 1;
-    i8_gm = geti("GEMMA_HIP_I8_GM", 0);
-    i8_raster = geti("GEMMA_HIP_I8_RASTER", S2_DEFAULT_RASTER);
-    i8_rows = geti("GEMMA_HIP_I8_ROWS", 16) == 32 ? 32 : 16;
+    i8.fuse = (ef && ef[0] == '0') ? 0 : 1;
+    i8.gm = geti("GEMMA_HIP_I8_GM", 0);
+    i8.raster = geti("GEMMA_HIP_I8_RASTER", S2_DEFAULT_RASTER);
+    i8.rows = geti("GEMMA_HIP_I8_ROWS", 16) == 32 ? 32 : 16;
     const char *esc = getenv("GEMMA_HIP_I8_SCALE");
     i8_scale_max = (esc && strcmp(esc, "pow2") == 0) ? 0 : 1;
     const char *efm = getenv("GEMMA_HIP_I8_FORM");
-    i8_mdrop = (efm && strcmp(efm, "7g6m") == 0) ? 1 : 0;
-    if (i8_mdrop) i8_digits = 7;
+    i8.mdrop = (efm && strcmp(efm, "7g6m") == 0) ? 1 : 0;
+    if (i8.mdrop) i8_digits = 7;
     const char *ecp = getenv("GEMMA_HIP_I8_COMPLETE");
-    i8_complete = (ecp && ecp[0] == '0') ? 0 : 1;
+    i8.complete = (ecp && ecp[0] == '0') ? 0 : 1;
     const char *eep = getenv("GEMMA_HIP_I8_EPILOGUE");
-    i8_epilogue = (eep && eep[0] == '0') ? 0 : 1;
-    i8_epi_depth = geti("GEMMA_HIP_I8_EPI_DEPTH", 4) <= 1 ? 1 : 4;
+    i8.epilogue = (eep && eep[0] == '0') ? 0 : 1;
+    i8.epi_depth = geti("GEMMA_HIP_I8_EPI_DEPTH", 4) <= 1 ? 1 : 4;
     const char *edr = getenv("GEMMA_HIP_I8_DIRECT");
-    i8_direct = (edr && edr[0] == '0') ? 0 : 1;
+    i8.direct = (edr && edr[0] == '0') ? 0 : 1;
     const char *ed = getenv("GEMMA_HIP_UTX_DOSAGE_I8");
     dosage_i8 = (ed && ed[0] == '0') ? 0 : 1;
     dosage_rows = geti("GEMMA_HIP_DOSAGE_ROWS", 16) == 32 ? 32 : 16;
     const char *eo = getenv("GEMMA_HIP_OVERLAP");
-    overlap = (eo && eo[0] == '1') ? 1 : 0;
-    overlap_chunks = geti("GEMMA_HIP_OVERLAP_CHUNKS", 4);
+    i8.overlap = (eo && eo[0] == '1') ? 1 : 0;
+    i8.chunks = geti("GEMMA_HIP_OVERLAP_CHUNKS", 4);
     const char *et = getenv("GEMMA_HIP_TABLE_V2");
     table_v2 = (et && et[0] == '0') ? 0 : 1;
     const char *ep = getenv("GEMMA_HIP_TABLE_PF");
