@@ -40,6 +40,8 @@ SYMBOLS = [
     "gemma_hip_lmm_score_panel_setup", "gemma_hip_lmm_score_panel_setup_d", "gemma_hip_lmm_score_panel_setup_kept",
     "gemma_hip_lmm_score_panel_batch", "gemma_hip_lmm_score_panel_batch_d", "gemma_hip_lmm_score_panel_assoc_d",
     "gemma_hip_lmm_score_panel_hits_batch", "gemma_hip_lmm_score_panel_hits_batch_d", "gemma_hip_lmm_score_panel_hits_assoc_d",
+    "gemma_hip_lmm_score_panel_refine_setup", "gemma_hip_lmm_score_panel_refine_setup_d", "gemma_hip_lmm_score_panel_refine_assoc_d",
+    "gemma_hip_lmm_score_panel_refine_last_d", "gemma_hip_lmm_score_panel_hits_refine_batch",
     "gemma_hip_lmm_null_panel", "gemma_hip_lmm_null_panel_d",
 ]
 LMM_MULTI_MAX = 64
@@ -216,6 +218,11 @@ def lib():
     L.gemma_hip_lmm_score_panel_hits_batch.argtypes = [ci, vp, sz, sz, C.c_double, vp, sz, vp, vp]
     L.gemma_hip_lmm_score_panel_hits_batch_d.argtypes = [ci, vp, sz, sz, C.c_double, vp, sz, vp, vp, vp]
     L.gemma_hip_lmm_score_panel_hits_assoc_d.argtypes = [dp, sz, sz, C.c_double, vp, sz, vp, vp, vp]
+    L.gemma_hip_lmm_score_panel_refine_setup.argtypes = [dp, dp]
+    L.gemma_hip_lmm_score_panel_refine_setup_d.argtypes = [dp, dp, vp]
+    L.gemma_hip_lmm_score_panel_refine_assoc_d.argtypes = [dp, sz, sz, vp, sz, vp, vp]
+    L.gemma_hip_lmm_score_panel_refine_last_d.argtypes = [vp, sz, vp, vp]
+    L.gemma_hip_lmm_score_panel_hits_refine_batch.argtypes = [ci, vp, sz, sz, C.c_double, vp, sz, vp, vp, vp]
     L.gemma_hip_lmm_null_panel.argtypes = [sz, sz, sz, dp, dp, dp, cd, cd, sz, cd, vp, dp, dp]
     L.gemma_hip_lmm_null_panel_d.argtypes = [sz, sz, sz, dp, dp, dp, cd, cd, sz, cd, vp, dp, dp, vp]
     L.gemma_hip_dbg_i8_digits.argtypes = [sz, C.POINTER(ci)]

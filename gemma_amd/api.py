@@ -743,21 +743,91 @@ class LMM:
         hits = ScoreHitsDev(snp[order], pheno[order], raw[:, 1:].contiguous().view(torch.float64)[order])
         return hits, ScoreBestDev(best[:, :3].contiguous().view(torch.float64), best[:, 3].clone())
 
-    def batch_score_panel_hits(self, geno, geno_kind, p_max, cap=None):
+    # -- the refinement of the hits: each pair's own lambda-hats, Wald and LRT (gemma_hip_lmm_score_panel_refine_*) --
+    def setup_score_refine(self, UtY, logl_mle_H0):
+        """After setup_score_panel: keeps what the refinement of hit pairs needs, a transposed copy of UtY (n x T) and the T
+        logl_mle_H0 of the null fits (CalcLambdaNullPanel).  numpy arrays are uploaded, a torch device UtY is read in place."""
+        T = self.n_ph
+        logl = np.ascontiguousarray(logl_mle_H0, dtype=np.float64).ravel()
+        if logl.size != T or UtY.shape[1] != T:
+            raise ValueError("LMM.setup_score_refine: %d null values and %d columns for %d phenotypes" % (logl.size, UtY.shape[1], T))
+        if _is_torch(UtY):
+            UtY = UtY.contiguous()
+            rc = L.lib().gemma_hip_lmm_score_panel_refine_setup_d(C.c_void_p(UtY.data_ptr()), _ptr(logl), _stream())
+        else:
+            UtY = np.ascontiguousarray(UtY, dtype=np.float64)
+            rc = L.lib().gemma_hip_lmm_score_panel_refine_setup(_ptr(UtY), _ptr(logl))
+        L.check(rc, "LMM.setup_score_refine")
+
+    @staticmethod
+    def _pairs_dev(hits, device):
+        """ScoreHitsDev or an (m, 2) integer tensor of (snp, pheno) -> (m, 4) int64: gemma_score_hit entries with the key filled in"""
+        import torch
+        if isinstance(hits, ScoreHitsDev):
+            snp, pheno = hits.snp, hits.pheno
+        else:
+            hits = torch.as_tensor(hits, device=device)
+            if hits.dim() != 2 or hits.shape[1] != 2 or hits.dtype.is_floating_point:
+                raise ValueError("LMM refinement: pairs are a ScoreHitsDev or an (m, 2) integer tensor of (snp, pheno)")
+            snp, pheno = hits[:, 0], hits[:, 1]
+        snp, pheno = snp.to(device=device, dtype=torch.int64), pheno.to(device=device, dtype=torch.int64)
+        if len(snp) and (int(snp.min()) < 0 or int(pheno.min()) < 0 or int(snp.max()) > 0xffffffff or int(pheno.max()) > 0xffffffff):
+            raise ValueError("LMM refinement: snp and pheno are unsigned 32-bit indices")
+        raw = torch.zeros((len(snp), 4), dtype=torch.int64, device=device)
+        raw[:, 0] = snp | (pheno << 32)  # snp in the low, pheno in the high 32 bits
+        return raw
+
+    def assoc_score_refine(self, UtX, hits):
+        """The `-lmm 4` records of the pairs in `hits` (ScoreHitsDev, or an (m, 2) integer tensor of (snp, pheno)) on a
+        device-resident SNP-major UtX (torch) -> (m, 8) device tensor in SUMSTAT order, row i for pair i.  A pair outside the block
+        or the panel gets NaN."""
+        import torch
+        raw = self._pairs_dev(hits, UtX.device)
+        out = torch.empty((raw.shape[0], 8), dtype=torch.float64, device=UtX.device)
+        L.check(L.lib().gemma_hip_lmm_score_panel_refine_assoc_d(C.c_void_p(UtX.data_ptr()), UtX.shape[0], _tld(UtX),
+                                                                 C.c_void_p(raw.data_ptr()), raw.shape[0], C.c_void_p(out.data_ptr()),
+                                                                 _stream()), "LMM.assoc_score_refine")
+        return out
+
+    def refine_last(self, hits, device="cuda"):
+        """assoc_score_refine on the U^T x of the most recent batch_score_panel / batch_score_panel_hits of this setup."""
+        import torch
+        if isinstance(hits, ScoreHitsDev):
+            device = hits.snp.device
+        elif _is_torch(hits):
+            device = hits.device if hits.is_cuda else device
+        raw = self._pairs_dev(hits, device)
+        out = torch.empty((raw.shape[0], 8), dtype=torch.float64, device=raw.device)
+        L.check(L.lib().gemma_hip_lmm_score_panel_refine_last_d(C.c_void_p(raw.data_ptr()), raw.shape[0], C.c_void_p(out.data_ptr()),
+                                                                _stream()), "LMM.refine_last")
+        return out
+
+    def batch_score_panel_hits(self, geno, geno_kind, p_max, cap=None, refine=False):
         """One block of SNPs -> (hits, best).  numpy in: hits is a SCORE_HIT_DTYPE array of every pair with p_score <= p_max, sorted
         by (pheno, snp), snp the row inside the block; best a (T,) SCORE_BEST_DTYPE array (snp -1, NaN: no pair).  torch in:
         ScoreHitsDev(snp, pheno, stats (m, 3)) and ScoreBestDev(stats (T, 3), snp) of device tensors, sorted the same way.  cap: the
-        size of the first list; a block with more hits is run again with a list that holds them."""
+        size of the first list; a block with more hits is run again with a list that holds them.
+        refine=True (after setup_score_refine) -> (hits, best, refined): the `-lmm 4` record of every hit, aligned with hits -- a
+        SUMSTAT_DTYPE array (numpy in) or an (m, 8) device tensor (torch in)."""
         T = self.n_ph
         p_max = float(p_max)
         l, ld = _block_dims(geno, geno_kind)
         if _is_torch(geno):
             gp, st = C.c_void_p(geno.data_ptr()), _stream()
-            return self._hits_dev(lambda raw, cap_, cnt, best: L.lib().gemma_hip_lmm_score_panel_hits_batch_d(
+            hits, best = self._hits_dev(lambda raw, cap_, cnt, best: L.lib().gemma_hip_lmm_score_panel_hits_batch_d(
                 geno_kind, gp, l, ld, p_max, raw, cap_, cnt, best, st), l, p_max, cap, geno.device)
+            return (hits, best, self.refine_last(hits)) if refine else (hits, best)
         cap = self._hits_cap(l, p_max, cap)
         best = np.zeros(T, dtype=SCORE_BEST_DTYPE)
         cnt = C.c_ulonglong(0)
+        while refine:
+            hits, refined = np.zeros(cap, dtype=SCORE_HIT_DTYPE), np.zeros(cap, dtype=SUMSTAT_DTYPE)
+            L.check(L.lib().gemma_hip_lmm_score_panel_hits_refine_batch(
+                geno_kind, _ptr(geno), l, ld, p_max, _ptr(hits) if cap else None, cap, C.cast(C.byref(cnt), C.c_void_p), _ptr(best),
+                _ptr(refined) if cap else None), "LMM.batch_score_panel_hits")
+            if cnt.value <= cap:
+                return hits[:cnt.value], best, refined[:cnt.value]
+            cap = int(cnt.value)
         while True:
             hits = np.zeros(cap, dtype=SCORE_HIT_DTYPE)
             L.check(L.lib().gemma_hip_lmm_score_panel_hits_batch(geno_kind, _ptr(geno), l, ld, p_max, _ptr(hits) if cap else None, cap,
@@ -774,10 +844,12 @@ class LMM:
             xp, l, ld, p_max, raw, cap_, cnt, best, st), l, p_max, cap, UtX.device)
 
     def AnalyzeScorePanelHits(self, U, eval_, UtW, UtY, geno, geno_kind=L.GENO_F64_SNP_MAJOR, p_max=1e-5, indicator_idv=None,
-                              l_mle_null=None, batch=LMM_BATCH_SIZE):
+                              l_mle_null=None, batch=LMM_BATCH_SIZE, refine=False, logl_mle_H0=None):
         """AnalyzeScorePanel without the (T, p) records: one pass over the genotypes -> (hits, best) as batch_score_panel_hits gives
         them, with snp the index over the whole scan (block offset + row); best is reduced over the blocks (the smallest p_score,
-        the smaller snp among equals, NaN never).  Nulls are fitted as AnalyzeScorePanel fits them."""
+        the smaller snp among equals, NaN never).  Nulls are fitted as AnalyzeScorePanel fits them.
+        refine=True -> (hits, best, refined): the `-lmm 4` record of every hit (its own lambda-hats, Wald, LRT), aligned with hits;
+        logl_mle_H0 are the T null log-likelihoods, fitted with the lambdas where either is missing."""
         if self.a_mode != 3:
             raise ValueError("LMM.AnalyzeScorePanelHits: a_mode %d (the score panel is a_mode 3)" % self.a_mode)
         tor = _is_torch(U)
@@ -788,9 +860,15 @@ class LMM:
             if tor:
                 raise ValueError("LMM.AnalyzeScorePanelHits: device inputs need l_mle_null")
             l_mle_null = CalcLambdaNullPanel(eval_, UtW, UtY, self.l_min, self.l_max, self.n_region)["l_mle_null"].copy()
+        if refine and logl_mle_H0 is None:
+            if tor:
+                raise ValueError("LMM.AnalyzeScorePanelHits: device inputs need logl_mle_H0")
+            logl_mle_H0 = CalcLambdaNullPanel(eval_, UtW, UtY, self.l_min, self.l_max, self.n_region)["logl_mle_H0"].copy()
         outs = _scan(lambda: self.setup_score_panel(U, eval_, UtW, UtY, l_mle_null), self.set_indicator, self.finish, indicator_idv, geno,
-                     batch, lambda s0, blk: (s0,) + self.batch_score_panel_hits(blk, geno_kind, p_max))
-        parts, bests = [(s0, h) for s0, h, _ in outs], [(s0, b) for s0, _, b in outs]
+                     batch, lambda s0, blk: (s0,) + self.batch_score_panel_hits(blk, geno_kind, p_max, refine=refine),
+                     prepare=(lambda: self.setup_score_refine(UtY, logl_mle_H0)) if refine else None)
+        parts, bests = [(s0, o[0]) for s0, *o in outs], [(s0, o[1]) for s0, *o in outs]
+        refs = [o[2] for _, *o in outs] if refine else None
         if tor:
             import torch
             dev = U.device
@@ -799,9 +877,11 @@ class LMM:
                                     torch.cat([h.stats for _, h in parts]))
                 order = torch.argsort((hits.pheno << 32) | hits.snp)
                 hits = ScoreHitsDev(hits.snp[order], hits.pheno[order], hits.stats[order])
+                refined = torch.cat(refs)[order] if refine else None
             else:
                 hits = ScoreHitsDev(torch.empty(0, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
                                     torch.empty((0, 3), dtype=torch.float64, device=dev))
+                refined = torch.empty((0, 8), dtype=torch.float64, device=dev)
             stats = torch.full((T, 3), float("nan"), dtype=torch.float64, device=dev)
             snp = torch.full((T,), -1, dtype=torch.int64, device=dev)
             for s0, b in bests:
@@ -815,9 +895,14 @@ class LMM:
             hits = np.concatenate([h for _, h in parts]) if parts else np.zeros(0, dtype=SCORE_HIT_DTYPE)
             off = np.concatenate([np.full(len(h), s0, dtype=np.uint32) for s0, h in parts]) if parts else np.zeros(0, dtype=np.uint32)
             hits["snp"] += off
-            hits = hits[np.lexsort((hits["snp"], hits["pheno"]))]
+            order = np.lexsort((hits["snp"], hits["pheno"]))
+            hits = hits[order]
+            refined = (np.concatenate(refs) if refs else np.zeros(0, dtype=SUMSTAT_DTYPE))[order] if refine else None
             best = reduce_score_best(bests, T)
         self.scoreHits, self.scoreBest = hits, best
+        if refine:
+            self.scoreRefined = refined
+            return hits, best, refined
         return hits, best
 
     def AnalyzeBimbam(self, U, eval_, UtW, Uty, X_snpmajor_nan):

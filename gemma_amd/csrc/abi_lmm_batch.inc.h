@@ -121,6 +121,7 @@ static int compute_utx(int kind, const void *geno, size_t l, size_t ld, int path
     int rcf = xp_flush(s); // blocks of gemma_hip_lmm_batch_pipe_d still in flight share this call's buffers
     if (rcf) return rcf;
   }
+  g_ctx.last_UtX = nullptr; // the block gemma_hip_lmm_score_panel_refine_last_d remembers is overwritten from here on
   const size_t n = g_ctx.cfg.n;
   const size_t ldx = (n + 1) & ~(size_t)1;
   const bool want_i8 = (path < 0 ? utx_i8_mode() == 1 : path == 1);
@@ -186,6 +187,7 @@ static int lmm_batch_plink_chunked(const void *geno, size_t l, size_t ld, gemma_
   const size_t ldx = (n + 1) & ~(size_t)1;
   int rc = overlap_init();
   if (rc) return rc;
+  g_ctx.last_UtX = nullptr;
   if (g_ctx.UtX.reserve(l * ldx * 8)) return fail(GEMMA_HIP_ENOMEM, "lmm_batch: cannot allocate %zu bytes", l * ldx * 8);
   double *UtX = g_ctx.UtX.as<double>();
   g_ctx.last_utx_path = 1;
@@ -257,6 +259,7 @@ extern "C" int gemma_hip_lmm_batch_pipe_d(int kind, const void *geno, size_t l, 
   const size_t ldx = (n + 1) & ~(size_t)1;
   // allocations first (a growing buffer is freed and re-allocated: hipFree waits for the device, which is what an in-flight reader
   // of the old buffer needs)
+  g_ctx.last_UtX = nullptr;
   if (g_ctx.UtX.reserve(l * ldx * 8)) return fail(GEMMA_HIP_ENOMEM, "lmm_batch_pipe: cannot allocate %zu bytes", l * ldx * 8);
   // The header's contract: the previous block's genotype buffer may be overwritten by work queued on `stream` AFTER this call.  Its
   // ingest runs on P, possibly still behind the product before it -- so the caller's stream is put behind that ingest here (ADVICE r5:
@@ -331,6 +334,7 @@ extern "C" int gemma_hip_lmm_gene_batch_d(const double *Y_d, size_t l, size_t ld
   hipStream_t s = S(stream);
   const size_t ldx = (n + 1) & ~(size_t)1;
   if (int rcf = xp_flush(S(stream))) return rcf; // blocks of the two-block pipeline still in flight share these buffers
+  g_ctx.last_UtX = nullptr;
   if (g_ctx.UtX.reserve(l * ldx * 8)) return fail(GEMMA_HIP_ENOMEM, "lmm_gene_batch: %zu bytes", l * ldx * 8);
   double *UtY = g_ctx.UtX.as<double>();
   {

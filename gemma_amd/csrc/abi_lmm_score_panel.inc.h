@@ -122,6 +122,13 @@ static int launch_score_panel(const double *UtX, size_t l, size_t ld, gemma_scor
   return GEMMA_HIP_OK;
 }
 
+// the block whose U^T x stays in g_ctx.UtX behind a batch: gemma_hip_lmm_score_panel_refine_last_d (abi_lmm_score_refine.inc.h)
+static void score_remember(const double *UtX, size_t l, size_t ldx) {
+  g_ctx.last_UtX = UtX;
+  g_ctx.last_l = l;
+  g_ctx.last_ldx = ldx;
+}
+
 #define NEED_SCORE(who)                                                                                                        \
   do {                                                                                                                         \
     if (!g_ctx.lmm_active || !g_ctx.score_T) return fail(GEMMA_HIP_ESTATE, who " before gemma_hip_lmm_score_panel_setup");      \
@@ -149,7 +156,9 @@ extern "C" int gemma_hip_lmm_score_panel_batch_d(int kind, const void *geno, siz
   double *UtX;
   size_t ldx;
   if ((rc = compute_utx(kind, geno, l, ld, -1, &UtX, &ldx, s))) return rc;
-  return launch_score_panel(UtX, l, ldx, out_d, s);
+  if ((rc = launch_score_panel(UtX, l, ldx, out_d, s))) return rc;
+  score_remember(UtX, l, ldx);
+  return GEMMA_HIP_OK;
 }
 
 extern "C" int gemma_hip_lmm_score_panel_batch(int kind, const void *geno, size_t l, size_t ld, gemma_score_rec *out) {
@@ -253,7 +262,9 @@ extern "C" int gemma_hip_lmm_score_panel_hits_batch_d(int kind, const void *geno
   double *UtX;
   size_t ldx;
   if ((rc = compute_utx(kind, geno, l, ld, -1, &UtX, &ldx, s))) return rc;
-  return launch_score_hits(UtX, l, ldx, p_max, hits_d, cap, n_hits_d, best_d, s);
+  if ((rc = launch_score_hits(UtX, l, ldx, p_max, hits_d, cap, n_hits_d, best_d, s))) return rc;
+  score_remember(UtX, l, ldx);
+  return GEMMA_HIP_OK;
 }
 
 extern "C" int gemma_hip_lmm_score_panel_hits_batch(int kind, const void *geno, size_t l, size_t ld, double p_max,

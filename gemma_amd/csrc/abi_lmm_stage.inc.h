@@ -31,6 +31,9 @@ static void score_release() {
   g_ctx.score_fthr.release(); g_ctx.score_cells.release(); g_ctx.score_hits.release(); g_ctx.score_cnt.release(); g_ctx.score_best.release();
   g_ctx.score_fthr_p = -1.0;
   g_ctx.score_T = 0;
+  g_ctx.refine_Yt.release(); g_ctx.refine_logl.release(); g_ctx.refine_out.release();
+  g_ctx.refine_ready = false;
+  g_ctx.last_UtX = nullptr;
 }
 // Everything an LMM setup or one of its batches owns, and the state flags: gemma_hip_lmm_finish and gemma_hip_shutdown (the
 // streams, events and pinned slots of the pipelines go through pipe_release / xp_release beside it).

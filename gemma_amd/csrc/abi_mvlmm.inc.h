@@ -205,6 +205,7 @@ static int mvlmm_gxe_batch_d(int kind, const void *geno, size_t l, size_t ld, do
   const size_t n = g_ctx.cfg.n, c = g_ctx.cfg.n_cvt;
   const size_t ldx = (n + 1) & ~(size_t)1;
   if (int rcf = xp_flush(s)) return rcf; // blocks of the two-block pipeline still in flight share these buffers
+  g_ctx.last_UtX = nullptr;
   if (g_ctx.X.reserve(l * ldx * 8) || g_ctx.UtX.reserve(l * ldx * 8) || g_ctx.gxe_Z.reserve(l * ldx * 8) ||
       g_ctx.gxe_UtZ.reserve(l * ldx * 8) || g_ctx.gxe_flip.reserve(l * sizeof(int)))
     return fail(GEMMA_HIP_ENOMEM, "mvlmm_batch (gxe): cannot allocate 4 x %zu bytes", l * ldx * 8);

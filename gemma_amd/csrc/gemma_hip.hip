@@ -27,6 +27,7 @@
 #include "lmm_grid.h"
 #include "lmm_score_panel.h"
 #include "lmm_null_panel.h"
+#include "lmm_pair.h"
 #include "i8gemm.h"
 #include "i8gemm_sparse.h"
 #include "i8gemm_sparse2.h"
@@ -249,6 +250,13 @@ struct Ctx {
   DevBuf score_fthr, score_cells, score_hits, score_cnt, score_best;
   double score_fthr_p = -1.0;      // p_max the threshold was made for (-1: none)
   hipStream_t score_fthr_s = nullptr; // ... and the stream it was made on (another stream makes its own: no order between the two)
+  // the refinement of a score panel's hit pairs (gemma_hip_lmm_score_panel_refine_*): Wald / LRT of (SNP, phenotype) pairs, lmm_pair.hip.h
+  bool refine_ready = false;       // gemma_hip_lmm_score_panel_refine_setup done for this score-panel setup
+  DevBuf refine_Yt, refine_logl;   // its own T x n transposed U^T Y; logl_mle_H0 per phenotype (l_mle_null is score_lam)
+  DevBuf refine_out;               // the host form's records
+  AssocArgs refine_proto;          // a_mode 4, BIMBAM NaN rule, the cfg's grid, no tables
+  const double *last_UtX = nullptr; // the U^T x of the most recent score-panel block (nullptr: none, or overwritten since: compute_utx)
+  size_t last_l = 0, last_ldx = 0;
 
   // linear model (-lm) state
   bool lm_active = false;
@@ -552,6 +560,7 @@ extern "C" int gemma_hip_dgemm(char ta, char tb, size_t M, size_t N, size_t K, d
 #include "abi_kept_comm.inc.h"
 #include "abi_lmm_multi.inc.h"
 #include "abi_lmm_score_panel.inc.h"
+#include "abi_lmm_score_refine.inc.h"
 #include "abi_lmm_null_panel.inc.h"
 #include "abi_vc.inc.h"
 #include "abi_prdt.inc.h"

@@ -333,6 +333,37 @@ int gemma_hip_lmm_score_panel_hits_assoc_d(const double *UtX_d, size_t l, size_t
                                            gemma_score_hit *hits_d, size_t cap, unsigned long long *n_hits_d, gemma_score_best *best_d,
                                            void *stream);
 
+/* The refinement of the hits: each pair's own lambda-hats, the Wald test and the likelihood-ratio test -- the `-lmm 4` columns of
+ * (SNP, phenotype) -- for a list of pairs, one wavefront per pair, every evaluation streaming the pair's two rows (a scattered list
+ * has no fixed-lambda table to share).  The contract: for every pair, the eight fields of gemma_hip_lmm_score_panel_refine_assoc_d
+ * are byte-equal to row `snp` of gemma_hip_lmm_setup_d with a_mode 4, the same cfg, plink_nan_rule 0, column `pheno` of UtY and
+ * l_mle_null[pheno] / logl_mle_H0[pheno], followed by gemma_hip_lmm_assoc_d on the same UtX, with GEMMA_HIP_ASSOC_GRID=0 in the
+ * environment of that setup.  p_score, beta and se of a refined record are those of the `-lmm 4` body, not copies of the hit; a
+ * failed lambda search follows the BIMBAM rule (NaN beta, se, p_wald: a pair has no previous SNP).
+ *   refine_setup   after a score-panel setup: keeps what the refinement needs, a T x n transposed U^T Y of its own (the score-panel
+ *                  setup still releases its copy) and the T logl_mle_H0; l_min, l_max and n_region are the setup's cfg, l_mle_null
+ *                  the setup's own.  A copy that does not fit: GEMMA_HIP_ENOMEM with the byte count.  Both forms return with UtY and
+ *                  logl_mle_H0 read.  gemma_hip_lmm_finish and a new setup take the refinement state down with the score panel.
+ *   pairs / m      gemma_score_hit entries of which only snp and pheno are read: a hits list can be passed straight in.  A pair
+ *                  with snp >= l or pheno >= T gets an all-NaN record and no memory access; m == 0 returns GEMMA_HIP_OK and touches
+ *                  nothing.  out[i] belongs to pairs[i]; the order and repetitions of the list are the caller's.
+ *   refine_last_d  the same on the U^T x of the most recent score-panel batch (records or hits form) of this setup.
+ *   hits_refine_batch  the host form of a block: the hits form plus one gemma_sumstat per returned hit, refined[i] for hits[i] after
+ *                  the sort; where n_hits > cap, refined is unspecified as the list is.  Only this form synchronises; the _d forms
+ *                  queue their work on `stream`.
+ * GEMMA_HIP_ESTATE: any of these before a score-panel setup; refine_assoc_d, refine_last_d or hits_refine_batch before refine_setup;
+ * refine_last_d with no score-panel block since the setup, or after any entry point that has overwritten the U^T x buffer
+ * (gemma_hip_dbg_utx, for one).  GEMMA_HIP_EINVAL: a null pointer with m > 0 (cap > 0 for refined), ld_utx < n. */
+int gemma_hip_lmm_score_panel_refine_setup(const double *UtY /* n x T row-major, host */, const double *logl_mle_H0 /* T, host */);
+int gemma_hip_lmm_score_panel_refine_setup_d(const double *UtY_d, const double *logl_mle_H0 /* host */, void *stream);
+/* records of m pairs on a caller-made U^T x (as ..._hits_assoc_d takes it) */
+int gemma_hip_lmm_score_panel_refine_assoc_d(const double *UtX_d, size_t l, size_t ld_utx, const gemma_score_hit *pairs_d, size_t m,
+                                             gemma_sumstat *out_d, void *stream);
+int gemma_hip_lmm_score_panel_refine_last_d(const gemma_score_hit *pairs_d, size_t m, gemma_sumstat *out_d, void *stream);
+int gemma_hip_lmm_score_panel_hits_refine_batch(int geno_kind, const void *geno, size_t l, size_t ld, double p_max,
+                                                gemma_score_hit *hits, size_t cap, unsigned long long *n_hits,
+                                                gemma_score_best *best, gemma_sumstat *refined /* cap records */);
+
 /* ---- null fits of a whole panel: what gemma_hip_lmm_null gives for one column of U^T Y, for every column ------------------- */
 /* The nulls the panel setups above are handed (l_mle_null, logl_mle_H0) and each trait's own result -- heritability, vg / ve, the
  * covariate effects (the reference prints them in its log, src/gemma.cpp:3402-3430) -- in one launch per chunk of columns, one

@@ -863,6 +863,11 @@ public:
   // NaN never; snp -1: none.
   std::vector<gemma_score_hit> scoreHits;
   std::vector<gemma_score_best> scoreBest;
+  // refine_hits = true before a hits scan: scoreRefined[i] is the `-lmm 4` record of scoreHits[i] -- the pair's own lambda-hats, the
+  // Wald and the likelihood-ratio test (gemma_hip_lmm_score_panel_hits_refine_batch); needs logl_mle_H0_multi beside
+  // l_mle_null_multi (CalcNullMulti fills both)
+  bool refine_hits = false;
+  std::vector<gemma_sumstat> scoreRefined;
 
   void AnalyzePlinkScorePanelHits(const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY, double p_max) {
     const std::string file_bed = file_bfile + ".bed";
@@ -1015,12 +1020,18 @@ private:
   }
   std::vector<gemma_score_hit> hits_buf_;
   std::vector<gemma_score_best> best_buf_;
+  std::vector<gemma_sumstat> refined_buf_;
   size_t hits_done_ = 0; // analysed SNPs of the blocks so far
   void setup_score_hits(const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY) {
     const size_t T = setup_score_panel(U, eval, UtW, UtY);
+    if (refine_hits) {
+      if (logl_mle_H0_multi.size() != T) throw HipError(GEMMA_HIP_EINVAL, "LMM: logl_mle_H0_multi needs one value per phenotype");
+      enforce_hip(gemma_hip_lmm_score_panel_refine_setup(UtY->data, logl_mle_H0_multi.data()), "LMM::AnalyzeScorePanelHits (refine)");
+    }
     const double nan = std::numeric_limits<double>::quiet_NaN();
     const gemma_score_best none = {nan, nan, nan, -1};
     scoreHits.clear();
+    scoreRefined.clear();
     scoreBest.assign(T, none);
     best_buf_.resize(T);
     if (hits_buf_.empty()) hits_buf_.resize(4096);
@@ -1030,11 +1041,19 @@ private:
     if (l == 0) return;
     unsigned long long nh = 0;
     for (;;) { // a block with more hits than the list holds is run again with a list that holds them
-      enforce_hip(gemma_hip_lmm_score_panel_hits_batch(kind, geno, l, ld, p_max, hits_buf_.data(), hits_buf_.size(), &nh, best_buf_.data()),
-                  "batch_compute (score panel hits)");
+      if (refine_hits) {
+        refined_buf_.resize(hits_buf_.size());
+        enforce_hip(gemma_hip_lmm_score_panel_hits_refine_batch(kind, geno, l, ld, p_max, hits_buf_.data(), hits_buf_.size(), &nh,
+                                                                best_buf_.data(), refined_buf_.data()),
+                    "batch_compute (score panel hits, refined)");
+      } else {
+        enforce_hip(gemma_hip_lmm_score_panel_hits_batch(kind, geno, l, ld, p_max, hits_buf_.data(), hits_buf_.size(), &nh, best_buf_.data()),
+                    "batch_compute (score panel hits)");
+      }
       if (nh <= hits_buf_.size()) break;
       hits_buf_.resize((size_t)nh);
     }
+    if (refine_hits) scoreRefined.insert(scoreRefined.end(), refined_buf_.begin(), refined_buf_.begin() + (size_t)nh);
     for (size_t k = 0; k < (size_t)nh; ++k) {
       gemma_score_hit h = hits_buf_[k];
       h.snp += (uint32_t)hits_done_;
@@ -1051,9 +1070,21 @@ private:
   }
   void finish_score_hits() {
     finish();
-    std::stable_sort(scoreHits.begin(), scoreHits.end(), [](const gemma_score_hit &x, const gemma_score_hit &y) {
+    const auto before = [](const gemma_score_hit &x, const gemma_score_hit &y) {
       return x.pheno != y.pheno ? x.pheno < y.pheno : x.snp < y.snp;
-    });
+    };
+    if (refine_hits) { // the records follow their hits
+      std::vector<size_t> order(scoreHits.size());
+      for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+      std::stable_sort(order.begin(), order.end(), [&](size_t i, size_t j) { return before(scoreHits[i], scoreHits[j]); });
+      std::vector<gemma_score_hit> h(order.size());
+      std::vector<gemma_sumstat> r(order.size());
+      for (size_t i = 0; i < order.size(); ++i) { h[i] = scoreHits[order[i]]; r[i] = scoreRefined[order[i]]; }
+      scoreHits.swap(h);
+      scoreRefined.swap(r);
+      return;
+    }
+    std::stable_sort(scoreHits.begin(), scoreHits.end(), before);
   }
   // batch_compute, src/lmm.cpp:1513-1564
   void batch_compute(int kind, const void *geno, size_t l, size_t ld, std::vector<gemma_sumstat> &out) {
