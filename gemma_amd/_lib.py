@@ -18,7 +18,7 @@ SYMBOLS = [
     "gemma_hip_lm_finish", "gemma_hip_profile_enable",
     "gemma_hip_profile_read", "gemma_hip_dbg_tridiag", "gemma_hip_dbg_stedc", "gemma_hip_dbg_eigh2", "gemma_hip_dbg_utx", "gemma_hip_lmm_gene_batch", "gemma_hip_lmm_gene_batch_d", "gemma_hip_lmm_set_env",
     "gemma_hip_lmm_gxe_batch", "gemma_hip_lmm_gxe_batch_d",
-    "gemma_hip_mvlmm_null", "gemma_hip_mvlmm_set", "gemma_hip_mvlmm_batch", "gemma_hip_mvlmm_batch_d",
+    "gemma_hip_mvlmm_null", "gemma_hip_mvlmm_set", "gemma_hip_mvlmm_batch", "gemma_hip_mvlmm_batch_d", "gemma_hip_dbg_last_mvlmm_kernel",
     "gemma_hip_kin_end_keep", "gemma_hip_kept_K_get", "gemma_hip_eigh_kept_K", "gemma_hip_eigh_keep", "gemma_hip_kept_n",
     "gemma_hip_kept_bcast", "gemma_hip_kept_U_get", "gemma_hip_calc_utx_kept", "gemma_hip_lmm_setup_kept", "gemma_hip_kept_release",
     "gemma_hip_comm_unique_id", "gemma_hip_comm_init", "gemma_hip_comm_info", "gemma_hip_comm_bcast_d",
@@ -117,6 +117,9 @@ class MvOpt(C.Structure):
                 ("p_nr", C.c_double), ("crt", C.c_size_t), ("gxe", C.c_size_t)]
 
 
+MV_KERNEL_NONE, MV_KERNEL_FIXED, MV_KERNEL_RUN_TIME = range(3)  # GEMMA_MV_KERNEL_*
+
+
 class GemmaHipError(RuntimeError):
     def __init__(self, code, where, detail):
         self.code = code
@@ -184,6 +187,7 @@ def lib():
     L.gemma_hip_mvlmm_set.argtypes = [sz, dp, C.POINTER(MvNull), C.POINTER(MvOpt)]
     L.gemma_hip_mvlmm_batch.argtypes = [ci, vp, sz, sz, dp]
     L.gemma_hip_mvlmm_batch_d.argtypes = [ci, vp, sz, sz, dp, vp]
+    L.gemma_hip_dbg_last_mvlmm_kernel.argtypes = [ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     L.gemma_hip_lmm_finish.argtypes = [C.POINTER(cd), C.POINTER(cd)]
     L.gemma_hip_lm_setup.argtypes = [ci, sz, sz, dp, dp]
     L.gemma_hip_lm_batch.argtypes = [ci, vp, sz, sz, vp]

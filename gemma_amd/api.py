@@ -138,6 +138,13 @@ def last_utx_kernel():
             "launches": k.launches, "name": k.name.decode()}
 
 
+def last_mvlmm_kernel(which):
+    """(form, d, rows) of the last multivariate per-SNP launch (which = 0) / null fit (1): form is L.MV_KERNEL_FIXED or _RUN_TIME."""
+    f, d, r = C.c_int(), C.c_int(), C.c_int()
+    L.check(L.lib().gemma_hip_dbg_last_mvlmm_kernel(which, C.byref(f), C.byref(d), C.byref(r)), "dbg_last_mvlmm_kernel")
+    return f.value, d.value, r.value
+
+
 def last_block_missing():
     """gemma_hip_dbg_last_block_missing: 1 / 0 = the last records product's block held / did not hold a missing call (a block without
     one takes the genotype product alone); -1 = the complete-block form is off or no such product ran."""

@@ -13,8 +13,9 @@ extern "C" int gemma_hip_mvlmm_null_launch_rt_(const MvNullArgs *a, hipStream_t 
 // c = covariates of the model the caller names; extra = the rows of X on top of them (1: the SNP; 3: env, SNP, interaction)
 static int mv_check_dims(const char *who, size_t d, size_t c, size_t extra = 1) {
   if (d < 1 || d > (size_t)MV_DMAX) return fail(GEMMA_HIP_EINVAL, "%s: %zu phenotypes not supported (1..%d)", who, d, MV_DMAX);
-  // fixed kernels: d <= 5 with up to 3 covariates, d <= 3 with up to 6 (mvlmm_kernels*.hip); everything else up to MV_DMAX phenotypes
-  // and MV_CMAX rows of X runs on the run-time kernel (mvlmm_kernels_rt.hip)
+  // fixed per-SNP kernels: d <= 7 with up to 3 covariates, d <= 3 with up to 6, d = 8 with one; fixed null fits: d <= 5 with up to 3
+  // covariates, d <= 3 with up to 6 (mvlmm_kernels*.hip); everything else up to MV_DMAX phenotypes and MV_CMAX rows of X runs on the
+  // run-time kernel (mvlmm_kernels_rt.hip).  gemma_hip_dbg_last_mvlmm_kernel reports which form a launch took.
   const size_t cmax = (size_t)MV_CMAX - extra;
   if (c < 1 || c > cmax)
     return fail(GEMMA_HIP_EINVAL, "%s: %zu covariates not supported (1..%zu)", who, c, cmax);
@@ -83,6 +84,7 @@ extern "C" int gemma_hip_mvlmm_null(size_t n, size_t n_cvt, size_t d, const doub
     Vg0[i * d + i] = o8[6];
     Ve0[i * d + i] = o8[7];
   }
+  int fit_form = GEMMA_MV_KERNEL_NONE; // of the last run_fit
   auto run_fit = [&](size_t dd, const double *Yt_dev, const double *vg0, const double *ve0, double *host_out) -> int {
     MvNullArgs a;
     memset(&a, 0, sizeof a);
@@ -100,6 +102,7 @@ extern "C" int gemma_hip_mvlmm_null(size_t n, size_t n_cvt, size_t d, const doub
     }
     a.out = d_out.as<double>();
     int lrc = mv_force_rt() ? -1 : gemma_hip_mvlmm_null_launch_(&a, (int)dd, (int)c, 0);
+    fit_form = lrc < 0 ? GEMMA_MV_KERNEL_RUN_TIME : GEMMA_MV_KERNEL_FIXED;
     if (lrc < 0) { // no fixed kernel for this shape
       a.g.d = (int)dd;
       a.g.c = (int)c;
@@ -125,7 +128,9 @@ extern "C" int gemma_hip_mvlmm_null(size_t n, size_t n_cvt, size_t d, const doub
         Ve0[i * d + j] = Ve0[j * d + i] = res[4 + 1]; // Ve_sub(0, 1)
       }
   }
-  if ((rc = run_fit(d, d_Yt.as<double>(), Vg0.data(), Ve0.data(), res.data()))) return rc;
+  rc = run_fit(d, d_Yt.as<double>(), Vg0.data(), Ve0.data(), res.data());
+  g_ctx.mv_last[1] = {fit_form, (int)d, (int)c};
+  if (rc) return rc;
   memset(out, 0, sizeof *out);
   const size_t blk = 2 * d * d + d * c + 1;
   for (size_t i = 0; i < d * d; ++i) {
@@ -185,6 +190,7 @@ extern "C" int gemma_hip_mvlmm_set(size_t d, const double *UtY, const gemma_mvlm
 // launches the per-SNP kernel: the fixed instance of (d, rows) if there is one, else the run-time kernel
 static int mv_launch(MvArgs &a, size_t d, size_t rows, hipStream_t s) {
   int lrc = (a.UtX2 || mv_force_rt()) ? -1 : gemma_hip_mvlmm_launch_(&a, (int)d, (int)rows, s);
+  g_ctx.mv_last[0] = {lrc < 0 ? GEMMA_MV_KERNEL_RUN_TIME : GEMMA_MV_KERNEL_FIXED, (int)d, (int)rows};
   if (lrc < 0) {
     a.d = (int)d;
     a.c = (int)rows;
@@ -280,4 +286,12 @@ extern "C" int gemma_hip_mvlmm_batch(int kind, const void *geno, size_t l, size_
                     [&](const void *in_d, void *out_d) {
                       return gemma_hip_mvlmm_batch_d(kind, in_d, l, ld, static_cast<double *>(out_d), nullptr);
                     });
+}
+
+extern "C" int gemma_hip_dbg_last_mvlmm_kernel(int which, int *form, int *d, int *rows) {
+  if (which != 0 && which != 1) return fail(GEMMA_HIP_EINVAL, "dbg_last_mvlmm_kernel: which %d (0: per-SNP, 1: null fit)", which);
+  if (form) *form = g_ctx.mv_last[which].form;
+  if (d) *d = g_ctx.mv_last[which].d;
+  if (rows) *rows = g_ctx.mv_last[which].rows;
+  return GEMMA_HIP_OK;
 }

@@ -196,6 +196,9 @@ struct Ctx {
   bool mv_ready = false, mv_gxe = false;
   size_t mv_d = 0;
   MvArgs mv_proto;
+  struct MvLast {
+    int form = 0, d = 0, rows = 0;
+  } mv_last[2]; // the kernel of the last per-SNP launch [0] / the last d-variate null fit [1] (gemma_hip_dbg_last_mvlmm_kernel)
   DevBuf i8_Bt, i8_q, i8_qinv, i8_cmax, i8_A, i8_C, i8_mean; // exact int8-digit U^T x (i8gemm.hip.h)
   unsigned long long cheb_qmask = 0; // bit k: tabulated interval k is in Q form (ends at or below lambda = 1e-3)
   // (tile_m, tile_n) per workgroup of the records kernel: the cross-XCD raster (i8gemm_sparse2.hip.h).  One map per launch shape,

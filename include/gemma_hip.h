@@ -389,8 +389,8 @@ int gemma_hip_lmm_null_panel_d(size_t n, size_t n_cvt, size_t T, const double *e
 /* ---- multivariate LMM (-lmm 1..4 -n a b c ...) ------------------------------------ */
 /* MVLMM::AnalyzeBimbam / AnalyzePlink, src/mvlmm.cpp:2972-3416 / :3418-3899, and with opt->gxe the interaction test of
  * AnalyzeBimbamGXE / AnalyzePlinkGXE (:3970-4414 / :4416-4870).  d phenotypes (1..GEMMA_MV_DMAX), n_cvt covariates with
- * n_cvt + 1 <= GEMMA_MV_CMAX rows of X (gxe: n_cvt + 3): register-resident kernels for d <= 5 with up to 3 covariates and d <= 3
- * with up to 6, one run-time-shaped kernel (slower) for every other shape and for gxe.  opt->crt = 1 applies the Edgeworth
+ * n_cvt + 1 <= GEMMA_MV_CMAX rows of X (gxe: n_cvt + 3): register-resident kernels for d <= 7 with up to 3 covariates, d <= 3
+ * with up to 6 and d = 8 with one, one run-time-shaped kernel (slower) for every other shape and for gxe.  opt->crt = 1 applies the Edgeworth
  * correction (CalcCRT / PCRT, :2054-2358 / :2952-2970) as -crt does.
  * gemma_mvlmm_null holds what the null-model block (:3056-3208) leaves behind: V_g, V_e (d x d row-major, leading
  * dimension d), B (d x n_cvt) and the log-likelihood, for the REMLE and the MLE fit. */
@@ -425,6 +425,12 @@ int gemma_hip_mvlmm_set(size_t d, const double *UtY, const gemma_mvlmm_null *nul
  * v = d (d + 1) / 2 (upper triangles, row by row) -- out holds l x (d + 3 v + 3) doubles. */
 int gemma_hip_mvlmm_batch(int geno_kind, const void *geno, size_t l, size_t ld, double *out);
 int gemma_hip_mvlmm_batch_d(int geno_kind, const void *geno_d, size_t l, size_t ld, double *out_d, void *stream);
+/* Which multivariate kernel the library launched last, recorded where a missing fixed instance falls back to the run-time kernel.
+ * which 0: the last per-SNP launch (mvlmm_batch*); 1: the last d-variate null fit of mvlmm_null (not its pairwise two-trait
+ * fits).  *form: GEMMA_MV_KERNEL_*; *d: phenotypes; *rows: rows of X of that launch (per-SNP: covariates + the SNP [+ env and
+ * the interaction row]; null fit: covariates).  Any of the three pointers may be null. */
+enum { GEMMA_MV_KERNEL_NONE = 0, GEMMA_MV_KERNEL_FIXED = 1, GEMMA_MV_KERNEL_RUN_TIME = 2 };
+int gemma_hip_dbg_last_mvlmm_kernel(int which, int *form, int *d, int *rows);
 
 /* ---- linear model without a random effect (-lm 1..4) ----------------------- */
 /* LM::AnalyzeBimbam / AnalyzePlink, src/lm.cpp:382-640 (CalcvPv :224-263, LmCalcP :266-287): per SNP ordinary

@@ -55,6 +55,7 @@ extern "C" int mvh_batch2(int d, int c, const MvArgs *g, int fixed) {
   CASE(1, 3) CASE(2, 3) CASE(3, 3) CASE(4, 3) CASE(5, 3)
   CASE(1, 4) CASE(2, 4) CASE(3, 4) CASE(4, 4) CASE(5, 4)
   CASE(1, 5) CASE(2, 5) CASE(3, 5) CASE(1, 6) CASE(2, 6) CASE(3, 6) CASE(1, 7) CASE(2, 7) CASE(3, 7)
+  CASE(6, 2) CASE(6, 3) CASE(6, 4) CASE(7, 2) CASE(7, 3) CASE(7, 4) CASE(8, 2)
 #undef CASE
   return 1;
 }

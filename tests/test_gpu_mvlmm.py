@@ -136,9 +136,11 @@ def test_run_time_kernel_equals_the_fixed_kernel(gpu_api, oracle, monkeypatch, n
 @pytest.mark.parametrize("n,d,cw,p,seed,a_mode,crt", [(500, 6, 1, 24, 31, 4, 0), (420, 4, 5, 24, 32, 4, 1), (380, 2, 9, 32, 33, 4, 0),
                                                       (600, 7, 2, 12, 34, 1, 0), (450, 5, 4, 16, 35, 3, 1), (640, 8, 1, 8, 36, 1, 0)])
 def test_analyze_beyond_the_fixed_kernels(gpu_api, oracle, n, d, cw, p, seed, a_mode, crt):
-    """Shapes no fixed kernel is built for (d > 5; more than three covariates with d = 4, 5; more than six with d <= 3): the
-    reference takes any (src/mvlmm.cpp:2972-3416); here the run-time kernel does, null block included (d > 4: pairwise
-    two-trait initialisation)."""
+    """Shapes beyond d <= 5 with up to three covariates and d <= 3 with up to six: the reference takes any
+    (src/mvlmm.cpp:2972-3416).  The null block of all six runs on the run-time kernel (d > 4: pairwise two-trait initialisation).
+    Per SNP (4, 5), (2, 9) and (5, 4) do too; (6, 1), (7, 2) and (8, 1) have had fixed per-SNP kernels since this test was written
+    (d = 6, 7 with up to three covariates, d = 8 with one).  tests/test_gpu_mvlmm_instances.py compares the run-time kernel with
+    the oracle at d > 5."""
     c = make_case(n, d, cw, p, seed)
     null, ref = _oracle_run(oracle, c, a_mode, X=c["G"], crt=crt, p_nr=0.5)
     mv = gpu_api.MVLMM(a_mode=a_mode, crt=crt, p_nr=0.5)
