@@ -43,6 +43,7 @@ SYMBOLS = [
     "gemma_hip_lmm_score_panel_refine_setup", "gemma_hip_lmm_score_panel_refine_setup_d", "gemma_hip_lmm_score_panel_refine_assoc_d",
     "gemma_hip_lmm_score_panel_refine_last_d", "gemma_hip_lmm_score_panel_hits_refine_batch",
     "gemma_hip_lmm_null_panel", "gemma_hip_lmm_null_panel_d",
+    "gemma_hip_mvlmm_null_se", "gemma_hip_mvlmm_null_pairs", "gemma_hip_mvlmm_null_pairs_d",
 ]
 LMM_MULTI_MAX = 64
 COMM_ID_BYTES = 128
@@ -117,6 +118,24 @@ class MvOpt(C.Structure):
                 ("p_nr", C.c_double), ("crt", C.c_size_t), ("gxe", C.c_size_t)]
 
 
+class MvNullSe(C.Structure):
+    """gemma_mvlmm_null_se: the variances behind the null block's standard errors -- VVg, VVe (v = d (d + 1) / 2, upper triangle row
+    by row) and VB (d x n_cvt) for the REMLE and the MLE fit"""
+    _fields_ = [("VVg_remle", C.c_double * 36), ("VVe_remle", C.c_double * 36), ("VB_remle", C.c_double * 96),
+                ("VVg_mle", C.c_double * 36), ("VVe_mle", C.c_double * 36), ("VB_mle", C.c_double * 96)]
+
+
+class MvPairBlock(C.Structure):
+    """gemma_mvpair_block: one two-trait fit, entries 00, 01, 11"""
+    _fields_ = [("Vg", C.c_double * 3), ("Ve", C.c_double * 3), ("VVg", C.c_double * 3), ("VVe", C.c_double * 3)] + \
+               [(k, C.c_double) for k in ("rg", "var_rg", "re", "var_re", "logl")]
+
+
+class MvPairFit(C.Structure):
+    """gemma_mvpair_fit: the REMLE and the MLE fit of one pair of traits"""
+    _fields_ = [("i", C.c_int), ("j", C.c_int), ("status", C.c_int), ("pad", C.c_int), ("remle", MvPairBlock), ("mle", MvPairBlock)]
+
+
 MV_KERNEL_NONE, MV_KERNEL_FIXED, MV_KERNEL_RUN_TIME = range(3)  # GEMMA_MV_KERNEL_*
 
 
@@ -185,6 +204,10 @@ def lib():
     L.gemma_hip_lmm_gene_batch_d.argtypes = [dp, sz, sz, vp, vp]
     L.gemma_hip_mvlmm_null.argtypes = [sz, sz, sz, dp, dp, dp, cd, cd, sz, C.POINTER(MvOpt), C.POINTER(MvNull)]
     L.gemma_hip_mvlmm_set.argtypes = [sz, dp, C.POINTER(MvNull), C.POINTER(MvOpt)]
+    L.gemma_hip_mvlmm_null_se.argtypes = [sz, sz, sz, dp, dp, dp, cd, cd, sz, C.POINTER(MvOpt), C.POINTER(MvNull), C.POINTER(MvNullSe)]
+    ip = C.POINTER(C.c_int)
+    L.gemma_hip_mvlmm_null_pairs.argtypes = [sz, sz, sz, dp, dp, dp, ip, sz, cd, cd, sz, C.POINTER(MvOpt), C.POINTER(MvPairFit), dp, dp]
+    L.gemma_hip_mvlmm_null_pairs_d.argtypes = [sz, sz, sz, vp, vp, vp, vp, sz, cd, cd, sz, C.POINTER(MvOpt), vp, vp, vp, vp]
     L.gemma_hip_mvlmm_batch.argtypes = [ci, vp, sz, sz, dp]
     L.gemma_hip_mvlmm_batch_d.argtypes = [ci, vp, sz, sz, dp, vp]
     L.gemma_hip_dbg_last_mvlmm_kernel.argtypes = [ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]

@@ -31,6 +31,10 @@ SCORE_HIT_DTYPE = np.dtype([("snp", "u4"), ("pheno", "u4"), ("beta", "f8"), ("se
 SCORE_BEST_DTYPE = np.dtype([("beta", "f8"), ("se", "f8"), ("p_score", "f8"), ("snp", "i8")])  # gemma_score_best
 NULL_DTYPE = np.dtype([(k, "f8") for k in ("l_mle_null", "logl_mle_H0", "l_remle_null", "logl_remle_H0", "pve", "pve_se", "vg_remle",
                                              "ve_remle")])  # gemma_null_fit
+_MVPAIR_BLOCK = [("Vg", "f8", 3), ("Ve", "f8", 3), ("VVg", "f8", 3), ("VVe", "f8", 3)] + \
+    [(k, "f8") for k in ("rg", "var_rg", "re", "var_re", "logl")]
+MVPAIR_DTYPE = np.dtype([("i", "i4"), ("j", "i4"), ("status", "i4"), ("pad", "i4"), ("remle", _MVPAIR_BLOCK),
+                         ("mle", _MVPAIR_BLOCK)])  # gemma_mvpair_fit
 LMM_BATCH_SIZE = 20000  # src/lmm.h:33
 K_BATCH_SIZE = 20000  # src/param.h:32
 
@@ -451,6 +455,74 @@ def CalcLambdaNullPanel(eval_, UtW, UtY, l_min=1e-5, l_max=1e5, n_region=10, tra
                                              _ptr(fit), _ptr(beta) if want_beta else None, _ptr(se) if want_beta else None),
             "CalcLambdaNullPanel")
     return (fit, beta, se) if want_beta else fit
+
+
+def CalcMvNullPairs(eval_, UtW, UtY, pairs=None, opt=None, want_beta=False, l_min=1e-5, l_max=1e5, n_region=10):
+    """The two-trait null fit of every listed pair of columns of UtY (n x T), one wavefront per pair: per pair what
+    MVLMM.fit_null gives on the two columns (Vg, Ve, logl, B in the same bits), the variances VVg / VVe behind se(Vg) / se(Ve), and
+    the genetic / residual correlations with their delta-method variances.  pairs: (m, 2) ints with i < j, or None for all i < j row
+    by row.  opt: an L.MvOpt (None: the PARAM defaults).  numpy in: a (m,) MVPAIR_DTYPE array; torch device tensors in: a (m, 36)
+    float64 device tensor whose rows are the same records (view them with .cpu().numpy().view(MVPAIR_DTYPE)).  want_beta: also B and
+    VB, (m, 2, 2, c): pass (REMLE, MLE), trait, covariate."""
+    popt = C.byref(opt) if opt is not None else None
+    if _is_torch(UtY):
+        import torch
+        for name, t in (("eval", eval_), ("UtW", UtW), ("UtY", UtY)):
+            if not _is_torch(t) or t.dtype != torch.float64 or not t.is_cuda:
+                raise TypeError("CalcMvNullPairs: %s must be a float64 device tensor" % name)
+        n = UtY.shape[0]
+        if UtW.dim() == 1:
+            UtW = UtW.reshape(-1, 1)
+        UtW, UtY, eval_ = UtW.contiguous(), UtY.contiguous(), eval_.contiguous()
+        _tld(UtW), _tld(UtY)  # 2-D row-major
+        if eval_.dim() != 1 or eval_.shape[0] != n or UtW.shape[0] != n:
+            raise ValueError("CalcMvNullPairs: eval (%d), UtW (%d rows) and UtY (%d rows) disagree" % (eval_.shape[0], UtW.shape[0], n))
+        T, c = UtY.shape[1], UtW.shape[1]
+        if pairs is not None:
+            pairs = torch.as_tensor(pairs, dtype=torch.int32, device=UtY.device).reshape(-1, 2).contiguous()
+        m = T * (T - 1) // 2 if pairs is None else pairs.shape[0]
+        fit = torch.empty((m, MVPAIR_DTYPE.itemsize // 8), dtype=torch.float64, device=UtY.device)
+        B = torch.empty((m, 2, 2, c), dtype=torch.float64, device=UtY.device) if want_beta else None
+        VB = torch.empty((m, 2, 2, c), dtype=torch.float64, device=UtY.device) if want_beta else None
+        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        L.check(L.lib().gemma_hip_mvlmm_null_pairs_d(n, c, T, vp(eval_), vp(UtW), vp(UtY), vp(pairs), 0 if pairs is None else m,
+                                                     l_min, l_max, n_region, popt, vp(fit), vp(B), vp(VB), _stream()),
+                "CalcMvNullPairs")
+        return (fit, B, VB) if want_beta else fit
+    n = len(eval_)
+    UtW = np.ascontiguousarray(UtW, dtype=np.float64).reshape(n, -1)
+    UtY_c = np.ascontiguousarray(UtY, dtype=np.float64).reshape(n, -1)
+    ev_c = _np64(np.ascontiguousarray(eval_, dtype=np.float64), "eval")
+    c, T = UtW.shape[1], UtY_c.shape[1]
+    if ev_c.ndim != 1 or UtW.shape[0] != n or UtY_c.shape[0] != n:
+        raise ValueError("CalcMvNullPairs: eval (%d), UtW and UtY disagree in their rows" % n)
+    if pairs is not None:
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    m = T * (T - 1) // 2 if pairs is None else pairs.shape[0]
+    fit = np.zeros(m, dtype=MVPAIR_DTYPE)
+    B = np.zeros((m, 2, 2, c)) if want_beta else None
+    VB = np.zeros((m, 2, 2, c)) if want_beta else None
+    L.check(L.lib().gemma_hip_mvlmm_null_pairs(n, c, T, _ptr(ev_c), _ptr(UtW), _ptr(UtY_c),
+                                               pairs.ctypes.data_as(C.POINTER(C.c_int)) if pairs is not None else None,
+                                               0 if pairs is None else m, l_min, l_max, n_region, popt,
+                                               fit.ctypes.data_as(C.POINTER(L.MvPairFit)), _ptr(B) if want_beta else None,
+                                               _ptr(VB) if want_beta else None), "CalcMvNullPairs")
+    return (fit, B, VB) if want_beta else fit
+
+
+def mv_pair_matrices(fit, T, block="remle"):
+    """A CalcMvNullPairs result (MVPAIR_DTYPE) -> the T x T matrices rg, re and their standard errors se_rg, se_re (sqrt of the
+    delta-method variances, NaN where negative): unit diagonals (se 0), NaN for a pair that is not in `fit`."""
+    out = {k: np.full((T, T), np.nan) for k in ("rg", "re", "se_rg", "se_re")}
+    for k in ("rg", "re"):
+        np.fill_diagonal(out[k], 1.0)
+        np.fill_diagonal(out["se_" + k], 0.0)
+    i, j, b = fit["i"], fit["j"], fit[block]
+    with np.errstate(invalid="ignore"):
+        for k in ("rg", "re"):
+            out[k][i, j] = out[k][j, i] = b[k]
+            out["se_" + k][i, j] = out["se_" + k][j, i] = np.sqrt(b["var_" + k])
+    return out
 
 
 # ----------------------------------------------------------------------------- B4
@@ -1026,22 +1098,35 @@ class MVLMM:
     def _opt(self, gxe=0):
         return L.MvOpt(self.em_iter, self.nr_iter, self.em_prec, self.nr_prec, self.p_nr, self.crt, gxe)
 
-    def fit_null(self, eval_, UtW, UtY):
+    def fit_null(self, eval_, UtW, UtY, want_se=False):
         """The null block (src/mvlmm.cpp:3056-3208) -> dict with Vg/Ve/B/logl for 'remle' and 'mle'; also fills the
-        members WriteFiles' callers read (Vg_remle_null, ..., logl_mle_H0)."""
+        members WriteFiles' callers read (Vg_remle_null, ..., logl_mle_H0).  want_se: the same fit (the same bits) through
+        gemma_hip_mvlmm_null_se, and the dict also holds the VARIANCES VVg_*, VVe_* (v = d (d + 1) / 2, upper triangle row by row)
+        and VB_* (d x c) whose safe_sqrt the reference prints as se(Vg), se(Ve) and se(B) (:3106-3128)."""
         UtY = np.ascontiguousarray(UtY, dtype=np.float64)
         n, d = UtY.shape
         UtW = np.ascontiguousarray(UtW, dtype=np.float64).reshape(n, -1)
         c = UtW.shape[1]
         ev = np.ascontiguousarray(eval_, dtype=np.float64)
         nf, opt = L.MvNull(), self._opt()
-        L.check(L.lib().gemma_hip_mvlmm_null(n, c, d, _ptr(ev), _ptr(UtW), _ptr(UtY), self.l_min, self.l_max,
-                                             self.n_region, C.byref(opt), C.byref(nf)), "MVLMM.fit_null")
+        if want_se:
+            se = L.MvNullSe()
+            L.check(L.lib().gemma_hip_mvlmm_null_se(n, c, d, _ptr(ev), _ptr(UtW), _ptr(UtY), self.l_min, self.l_max,
+                                                    self.n_region, C.byref(opt), C.byref(nf), C.byref(se)), "MVLMM.fit_null")
+        else:
+            L.check(L.lib().gemma_hip_mvlmm_null(n, c, d, _ptr(ev), _ptr(UtW), _ptr(UtY), self.l_min, self.l_max,
+                                                 self.n_region, C.byref(opt), C.byref(nf)), "MVLMM.fit_null")
         self._null_struct = nf
         g = lambda a, r, k: np.array(a[:r * k]).reshape(r, k)
         self.null = {"Vg_remle": g(nf.Vg_remle, d, d), "Ve_remle": g(nf.Ve_remle, d, d), "B_remle": g(nf.B_remle, d, c),
                      "logl_remle": nf.logl_remle_H0, "Vg_mle": g(nf.Vg_mle, d, d), "Ve_mle": g(nf.Ve_mle, d, d),
                      "B_mle": g(nf.B_mle, d, c), "logl_mle": nf.logl_mle_H0}
+        if want_se:
+            v = d * (d + 1) // 2
+            for tag in ("remle", "mle"):
+                self.null["VVg_" + tag] = np.array(getattr(se, "VVg_" + tag)[:v])
+                self.null["VVe_" + tag] = np.array(getattr(se, "VVe_" + tag)[:v])
+                self.null["VB_" + tag] = g(getattr(se, "VB_" + tag), d, c)
         self.logl_remle_H0, self.logl_mle_H0 = nf.logl_remle_H0, nf.logl_mle_H0
         return self.null
 

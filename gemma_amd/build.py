@@ -25,6 +25,8 @@ SOURCES = [
     "mvlmm_kernels_d6.hip",   # six phenotypes, fixed form (two wavefronts per workgroup)
     "mvlmm_kernels_d7.hip",   # seven phenotypes (one wavefront per workgroup)
     "mvlmm_kernels_d8.hip",   # eight phenotypes, one covariate
+    "mvlmm_kernels_pair.hip",     # two-trait null fits of a whole panel: one wavefront per pair of traits
+    "mvlmm_kernels_null_se.hip",  # the fixed null fits with the variance epilogue (VVg, VVe, VB)
 ]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 

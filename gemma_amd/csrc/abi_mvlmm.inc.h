@@ -9,6 +9,7 @@ extern "C" int gemma_hip_mvlmm_null_launch_(const MvNullArgs *a, int d, int c, h
 extern "C" size_t gemma_hip_mvlmm_rt_scratch_(int d, int c);
 extern "C" int gemma_hip_mvlmm_launch_rt_(const MvArgs *g, unsigned grid, hipStream_t s);
 extern "C" int gemma_hip_mvlmm_null_launch_rt_(const MvNullArgs *a, hipStream_t s);
+// mvlmm_pair.h: the null fits with the variance epilogue (gemma_hip_mvlmm_null_se_launch_ / _rt_) and the pair panel's launchers
 
 // c = covariates of the model the caller names; extra = the rows of X on top of them (1: the SNP; 3: env, SNP, interaction)
 static int mv_check_dims(const char *who, size_t d, size_t c, size_t extra = 1) {
@@ -48,9 +49,10 @@ static int mv_upload_transposed(const double *src, size_t rows, size_t cols, Dev
   return GEMMA_HIP_OK;
 }
 
-extern "C" int gemma_hip_mvlmm_null(size_t n, size_t n_cvt, size_t d, const double *eval, const double *UtW,
-                                    const double *UtY, double l_min, double l_max, size_t n_region,
-                                    const gemma_mvlmm_opt *opt, gemma_mvlmm_null *out) {
+// The body of gemma_hip_mvlmm_null and gemma_hip_mvlmm_null_se (abi_mvlmm_pairs.inc.h).  se != nullptr: the d-variate fit runs on the
+// instance with the variance epilogue (MvNullSe) -- the same fit body, the same bits in `out`.
+static int mv_null_body(size_t n, size_t n_cvt, size_t d, const double *eval, const double *UtW, const double *UtY, double l_min,
+                        double l_max, size_t n_region, const gemma_mvlmm_opt *opt, gemma_mvlmm_null *out, gemma_mvlmm_null_se *se) {
   NEED_INIT();
   g_ctx.knobs.load();
   if (!eval || !UtW || !UtY || !out) return fail(GEMMA_HIP_EINVAL, "mvlmm_null: null pointer");
@@ -66,12 +68,14 @@ extern "C" int gemma_hip_mvlmm_null(size_t n, size_t n_cvt, size_t d, const doub
     ~Rel() { for (DevBuf *x : b) x->release(); }
   } rel{{&d_eval, &d_Wt, &d_Yt, &d_Ypair, &d_out}};
   constexpr size_t RES_MAX = 2 * (2 * MV_DMAX * MV_DMAX + MV_BMAX + 1);
-  DevBuf d_scr;
+  constexpr size_t SE_MAX = 2 * (size_t)mv_null_se_doubles(MV_DMAX, MV_CMAX);
+  DevBuf d_scr, d_se;
   struct Rel2 {
-    DevBuf *b;
-    ~Rel2() { b->release(); }
-  } rel2{&d_scr};
-  if (d_eval.reserve(n * 8) || d_out.reserve(RES_MAX * 8)) return fail(GEMMA_HIP_ENOMEM, "mvlmm_null: buffers");
+    DevBuf *b[2];
+    ~Rel2() { for (DevBuf *x : b) x->release(); }
+  } rel2{{&d_scr, &d_se}};
+  if (d_eval.reserve(n * 8) || d_out.reserve(RES_MAX * 8) || (se && d_se.reserve(SE_MAX * 8)))
+    return fail(GEMMA_HIP_ENOMEM, "mvlmm_null: buffers");
   HIPCHK(hipMemcpy(d_eval.p, eval, n * 8, hipMemcpyHostToDevice));
   if ((rc = mv_upload_transposed(UtW, n, c, d_Wt)) || (rc = mv_upload_transposed(UtY, n, d, d_Yt))) return rc;
   // MphInitial :2780-2797: the diagonals from one univariate REML fit per trait
@@ -85,7 +89,8 @@ extern "C" int gemma_hip_mvlmm_null(size_t n, size_t n_cvt, size_t d, const doub
     Ve0[i * d + i] = o8[7];
   }
   int fit_form = GEMMA_MV_KERNEL_NONE; // of the last run_fit
-  auto run_fit = [&](size_t dd, const double *Yt_dev, const double *vg0, const double *ve0, double *host_out) -> int {
+  // se_dev: the MvNullSe block of this fit, or nullptr (the pairwise starts of d > 4 never take it)
+  auto run_fit = [&](size_t dd, const double *Yt_dev, const double *vg0, const double *ve0, double *host_out, double *se_dev) -> int {
     MvNullArgs a;
     memset(&a, 0, sizeof a);
     a.g.n = (int)n;
@@ -101,14 +106,16 @@ extern "C" int gemma_hip_mvlmm_null(size_t n, size_t n_cvt, size_t d, const doub
       a.Ve0[i] = ve0[i];
     }
     a.out = d_out.as<double>();
-    int lrc = mv_force_rt() ? -1 : gemma_hip_mvlmm_null_launch_(&a, (int)dd, (int)c, 0);
+    int lrc = mv_force_rt() ? -1
+              : se_dev      ? gemma_hip_mvlmm_null_se_launch_(&a, (int)dd, (int)c, se_dev, 0)
+                            : gemma_hip_mvlmm_null_launch_(&a, (int)dd, (int)c, 0);
     fit_form = lrc < 0 ? GEMMA_MV_KERNEL_RUN_TIME : GEMMA_MV_KERNEL_FIXED;
     if (lrc < 0) { // no fixed kernel for this shape
       a.g.d = (int)dd;
       a.g.c = (int)c;
       if (d_scr.reserve(gemma_hip_mvlmm_rt_scratch_((int)dd, (int)c) * 8)) return fail(GEMMA_HIP_ENOMEM, "mvlmm_null: scratch");
       a.g.scratch = d_scr.as<double>();
-      lrc = gemma_hip_mvlmm_null_launch_rt_(&a, 0);
+      lrc = se_dev ? gemma_hip_mvlmm_null_se_launch_rt_(&a, se_dev, 0) : gemma_hip_mvlmm_null_launch_rt_(&a, 0);
     }
     if (lrc) return fail(GEMMA_HIP_ERUNTIME, "mvlmm_null launch: %s", hipGetErrorString((hipError_t)lrc));
     HIPCHK(hipDeviceSynchronize());
@@ -123,12 +130,12 @@ extern "C" int gemma_hip_mvlmm_null(size_t n, size_t n_cvt, size_t d, const doub
         HIPCHK(hipMemcpy(d_Ypair.p, d_Yt.as<double>() + i * n, n * 8, hipMemcpyDeviceToDevice));
         HIPCHK(hipMemcpy(d_Ypair.as<double>() + n, d_Yt.as<double>() + j * n, n * 8, hipMemcpyDeviceToDevice));
         const double vg2[4] = {Vg0[i * d + i], 0, 0, Vg0[j * d + j]}, ve2[4] = {Ve0[i * d + i], 0, 0, Ve0[j * d + j]};
-        if ((rc = run_fit(2, d_Ypair.as<double>(), vg2, ve2, res.data()))) return rc;
+        if ((rc = run_fit(2, d_Ypair.as<double>(), vg2, ve2, res.data(), nullptr))) return rc;
         Vg0[i * d + j] = Vg0[j * d + i] = res[1];     // Vg_sub(0, 1) of the REMLE block
         Ve0[i * d + j] = Ve0[j * d + i] = res[4 + 1]; // Ve_sub(0, 1)
       }
   }
-  rc = run_fit(d, d_Yt.as<double>(), Vg0.data(), Ve0.data(), res.data());
+  rc = run_fit(d, d_Yt.as<double>(), Vg0.data(), Ve0.data(), res.data(), se ? d_se.as<double>() : nullptr);
   g_ctx.mv_last[1] = {fit_form, (int)d, (int)c};
   if (rc) return rc;
   memset(out, 0, sizeof *out);
@@ -145,7 +152,29 @@ extern "C" int gemma_hip_mvlmm_null(size_t n, size_t n_cvt, size_t d, const doub
   }
   out->logl_remle_H0 = res[2 * d * d + d * c];
   out->logl_mle_H0 = res[blk + 2 * d * d + d * c];
+  if (se) {
+    const size_t v = d * (d + 1) / 2, seb = (size_t)mv_null_se_doubles((int)d, (int)c);
+    std::vector<double> sv(2 * seb);
+    HIPCHK(hipMemcpy(sv.data(), d_se.p, 2 * seb * 8, hipMemcpyDeviceToHost));
+    memset(se, 0, sizeof *se);
+    for (size_t i = 0; i < v; ++i) {
+      se->VVg_remle[i] = sv[i];
+      se->VVe_remle[i] = sv[v + i];
+      se->VVg_mle[i] = sv[seb + i];
+      se->VVe_mle[i] = sv[seb + v + i];
+    }
+    for (size_t i = 0; i < d * c; ++i) {
+      se->VB_remle[i] = sv[2 * v + i];
+      se->VB_mle[i] = sv[seb + 2 * v + i];
+    }
+  }
   return GEMMA_HIP_OK;
+}
+
+extern "C" int gemma_hip_mvlmm_null(size_t n, size_t n_cvt, size_t d, const double *eval, const double *UtW,
+                                    const double *UtY, double l_min, double l_max, size_t n_region,
+                                    const gemma_mvlmm_opt *opt, gemma_mvlmm_null *out) {
+  return mv_null_body(n, n_cvt, d, eval, UtW, UtY, l_min, l_max, n_region, opt, out, nullptr);
 }
 
 extern "C" int gemma_hip_mvlmm_set(size_t d, const double *UtY, const gemma_mvlmm_null *nf, const gemma_mvlmm_opt *opt) {

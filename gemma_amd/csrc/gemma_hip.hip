@@ -36,6 +36,7 @@
 #include "i8gemm_dense16.h"
 #include "qc.h"
 #include "mvlmm.hip.h"
+#include "mvlmm_pair.h"
 #include "comm.hip.h"
 #include "kin_i8.h"
 #include "i8_plan.h"
@@ -565,6 +566,7 @@ extern "C" int gemma_hip_dgemm(char ta, char tb, size_t M, size_t N, size_t K, d
 #include "abi_lmm_score_panel.inc.h"
 #include "abi_lmm_score_refine.inc.h"
 #include "abi_lmm_null_panel.inc.h"
+#include "abi_mvlmm_pairs.inc.h"
 #include "abi_vc.inc.h"
 #include "abi_prdt.inc.h"
 #include "abi_mqs.inc.h"

@@ -1277,15 +1277,24 @@ template <int DT, int CT, class Lanes> struct MvNr {
 // One SNP: the body of the loop at src/mvlmm.cpp:3287-3374 (with -crt: PCRT on the SNPs that reach MphNR).  nr: callable (reml) -> logl_H1 that refines
 // Vg, Ve by Newton-Raphson, or a no-op returning NaN when the stage is not compiled in.
 // B = GLS estimate of the fixed effects at (Vg, Ve): what MphCalcBeta (:835-935) leaves in B
-template <int DT, int CT, class Lanes>
+// VB (optional, d x c like B): the diagonal of MphCalcBeta's Vbeta (:893-920), whose square roots are se_B.  Covariate j's d x d
+// block of Qi is diagonal in the rotated basis (entry l: Qi_l[j][j]), so UltVeh^T Qi_block UltVeh has the diagonal
+// VB[a][j] = sum_l UltVeh[l][a]^2 Qi_l[j][j].
+// WITH_VB is a template argument, not a test of the pointer: without it the statements below are never instantiated and the
+// existing callers compile to what they were.
+template <int DT, int CT, class Lanes, bool WITH_VB = false>
 MV_HD void mv_gls_B(const MvArgs &g, const MvRt &rt, const double *__restrict__ x, const double (&Vg)[MV_DD], const double (&Ve)[MV_DD],
-                    double (&B)[MV_DC]) {
+                    double (&B)[MV_DC], double *VB = nullptr) {
   MV_SHAPE(rt);
   MvBasis<DT> bs;
   MvMoments<DT, CT> m;
   bs.build(Vg, Ve, D);
   mv_pass_moments<DT, CT, Lanes>(g, rt, x, bs, m);
   double bl[DK * CK];
+  if constexpr (WITH_VB) {
+#pragma unroll
+    for (int i = 0; i < D * C; ++i) VB[i] = 0.0;
+  }
 #pragma unroll
   for (int l = 0; l < D; ++l) {
     double Ql[CK * CK], Qi[CK * CK];
@@ -1297,6 +1306,12 @@ MV_HD void mv_gls_B(const MvArgs &g, const MvRt &rt, const double *__restrict__ 
 #pragma unroll
       for (int b = 0; b < C; ++b) s += Qi[a * C + b] * m.xHiy[l * C + b];
       bl[l * C + a] = s;
+    }
+    if constexpr (WITH_VB) {
+#pragma unroll
+      for (int a = 0; a < D; ++a)
+#pragma unroll
+        for (int j = 0; j < C; ++j) VB[a * C + j] += bs.UltVeh[l * D + a] * bs.UltVeh[l * D + a] * Qi[j * C + j];
     }
   }
 #pragma unroll
@@ -1484,8 +1499,26 @@ struct MvNullArgs {
   // run-time instance: g.d, g.c = the phenotypes and the covariates of THIS fit (c counts the last covariate, which plays the x row)
 };
 
+// Extra outputs of a null fit (gemma_hip_mvlmm_null_se, the pair panel): what the reference's null block leaves in VVg_*_null,
+// VVe_*_null and se_beta_*_null (:3074-3093, :3140-3159), as variances.  p: 2 x mv_null_se_doubles(d, c), REMLE then MLE block:
+//   VV[2 v]   the diagonal of -H^-1, MphNR's variance matrix (:2742-2744), V_g entries (GetIndex order) then V_e at offset v;
+//             H is the Hessian of MphNR's LAST CalcDev call (what the reference reports), not one re-evaluated at the final point
+//   VB[d c]   the diagonal of MphCalcBeta's Vbeta (mv_gls_B)
+//   Vcov[18]  d = 2 only: the 3 x 3 V_g block and the 3 x 3 V_e block of -H^-1 (the correlations' delta method needs them)
+// MvNullNoSe (the default argument of mv_null_fit): nothing more is computed or stored, and -- the choice being one of TYPE -- the
+// epilogue is never instantiated for the existing callers, which compile to what they were.
+struct MvNullSe {
+  static constexpr bool ON = true;
+  double *p = nullptr;
+};
+struct MvNullNoSe {
+  static constexpr bool ON = false;
+};
+constexpr int mv_null_se_doubles(int d, int c) { return d * (d + 1) + d * c + (d == 2 ? 18 : 0); }
+
 // EM + NR for REML, then for ML starting from the REML fit; one "lane group" does the whole fit
-template <int DT, int CT, class Lanes> MV_HD void mv_null_fit(const MvNullArgs &a, double *scratch) {
+template <int DT, int CT, class Lanes, class Se = MvNullNoSe>
+MV_HD void mv_null_fit(const MvNullArgs &a, double *scratch, [[maybe_unused]] Se se = Se()) {
   const MvArgs &g = a.g;
   MvRt rt;
   rt.d = g.d;
@@ -1508,7 +1541,29 @@ template <int DT, int CT, class Lanes> MV_HD void mv_null_fit(const MvNullArgs &
     const bool reml = pass == 0;
     mv_em_sel<DT, CT, Lanes>(g, rt, x, reml, a.em_iter, a.em_prec, lndet_xxt, XXti, Vg, Ve, B);
     const double logl = nr(reml, lndet_xxt, Vg, Ve);
-    mv_gls_B<DT, CT, Lanes>(g, rt, x, Vg, Ve, B);
+    if constexpr (Se::ON) {
+      double VB[DK * CK];
+      // lds[HINV] as MphNR's last CalcDev left it: mv_gls_B below does not touch the scratch, but take the values first all the same
+      double *o = se.p + pass * mv_null_se_doubles(D, C);
+      if (Lanes::lane() == 0) {
+        const double *Hi = scratch + nr.sc.HINV;
+        const bool have = g.nr_iter > 0; // no CalcDev call, no Hessian
+        for (int q = 0; q < H2; ++q) o[q] = have ? -Hi[q * H2 + q] : 0.0 / 0.0;
+        if (D == 2)
+          for (int blk = 0; blk < 2; ++blk)
+            for (int v1 = 0; v1 < 3; ++v1)
+              for (int v2 = 0; v2 < 3; ++v2)
+                o[H2 + D * C + blk * 9 + v1 * 3 + v2] = have ? -Hi[(blk * 3 + v1) * H2 + blk * 3 + v2] : 0.0 / 0.0;
+      }
+      mv_lane_fence();
+      mv_gls_B<DT, CT, Lanes, true>(g, rt, x, Vg, Ve, B, VB);
+      if (Lanes::lane() == 0) {
+#pragma unroll
+        for (int i = 0; i < D * C; ++i) o[H2 + i] = VB[i];
+      }
+    } else {
+      mv_gls_B<DT, CT, Lanes>(g, rt, x, Vg, Ve, B);
+    }
     if (Lanes::lane() == 0) {
       double *o = a.out + pass * BLK;
 #pragma unroll

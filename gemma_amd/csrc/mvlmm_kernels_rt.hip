@@ -28,6 +28,13 @@ __global__ __launch_bounds__(64) void mvlmm_rt_kernel(MvArgs g) {
 
 __global__ __launch_bounds__(64) void mvlmm_null_rt_kernel(MvNullArgs a) { mv_null_fit<0, 0, MvWaveLanes>(a, a.g.scratch); }
 
+// the same with the variance epilogue (gemma_hip_mvlmm_null_se): se_out holds 2 x mv_null_se_doubles(d, c)
+__global__ __launch_bounds__(64) void mvlmm_null_rt_se_kernel(MvNullArgs a, double *se_out) {
+  MvNullSe se;
+  se.p = se_out;
+  mv_null_fit<0, 0, MvWaveLanes>(a, a.g.scratch, se);
+}
+
 } // namespace gemma_hip
 
 // doubles of Newton-Raphson scratch one workgroup needs
@@ -40,5 +47,9 @@ extern "C" int gemma_hip_mvlmm_launch_rt_(const MvArgs *g, unsigned grid, hipStr
 }
 extern "C" int gemma_hip_mvlmm_null_launch_rt_(const MvNullArgs *a, hipStream_t s) {
   hipLaunchKernelGGL(mvlmm_null_rt_kernel, dim3(1), dim3(64), 0, s, *a);
+  return (int)hipGetLastError();
+}
+extern "C" int gemma_hip_mvlmm_null_se_launch_rt_(const MvNullArgs *a, double *se, hipStream_t s) {
+  hipLaunchKernelGGL(mvlmm_null_rt_se_kernel, dim3(1), dim3(64), 0, s, *a, se);
   return (int)hipGetLastError();
 }

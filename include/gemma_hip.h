@@ -432,6 +432,44 @@ int gemma_hip_mvlmm_batch_d(int geno_kind, const void *geno_d, size_t l, size_t 
 enum { GEMMA_MV_KERNEL_NONE = 0, GEMMA_MV_KERNEL_FIXED = 1, GEMMA_MV_KERNEL_RUN_TIME = 2 };
 int gemma_hip_dbg_last_mvlmm_kernel(int which, int *form, int *d, int *rows);
 
+/* ---- the null block's standard errors, and two-trait null fits of a whole panel -------------------------------------------- */
+/* gemma_hip_mvlmm_null_se: gemma_hip_mvlmm_null -- the same computation, the same bits in `out`, the same report through
+ * gemma_hip_dbg_last_mvlmm_kernel(1, ...) -- plus what the reference's null block leaves in VVg_*_null, VVe_*_null and
+ * se_beta_*_null (src/mvlmm.cpp:3074-3093, :3140-3159), as VARIANCES (the reference prints safe_sqrt of them, :3110 / :918):
+ * VVg / VVe [v], v = d (d + 1) / 2 in GetIndex order (upper triangle row by row): the diagonal of MphNR's variance matrix -H^-1
+ * (:2742-2744), H being the Hessian of MphNR's last CalcDev call; VB [d x n_cvt]: the diagonal of MphCalcBeta's Vbeta (:835-921). */
+typedef struct {
+  double VVg_remle[GEMMA_MV_DMAX * (GEMMA_MV_DMAX + 1) / 2], VVe_remle[GEMMA_MV_DMAX * (GEMMA_MV_DMAX + 1) / 2],
+      VB_remle[GEMMA_MV_DMAX * GEMMA_MV_CMAX];
+  double VVg_mle[GEMMA_MV_DMAX * (GEMMA_MV_DMAX + 1) / 2], VVe_mle[GEMMA_MV_DMAX * (GEMMA_MV_DMAX + 1) / 2],
+      VB_mle[GEMMA_MV_DMAX * GEMMA_MV_CMAX];
+} gemma_mvlmm_null_se;
+int gemma_hip_mvlmm_null_se(size_t n, size_t n_cvt, size_t d, const double *eval, const double *UtW, const double *UtY,
+                            double l_min, double l_max, size_t n_region, const gemma_mvlmm_opt *opt, gemma_mvlmm_null *out,
+                            gemma_mvlmm_null_se *se);
+/* gemma_hip_mvlmm_null_pairs: for every listed pair (i, j), i < j, of the T columns of UtY (n x T row-major) the two-trait null fit
+ * gemma_hip_mvlmm_null(d = 2) gives on columns i and j -- Vg, Ve, logl and B in the same bits -- with the variances above and the
+ * genetic / residual correlations: one wavefront per pair, every pair of a chunk in one launch.  Entries are ordered 00, 01, 11.
+ * rg = Vg01 / sqrt(Vg00 Vg11), var_rg by the delta method from the 3 x 3 V_g block of -H^-1 (re / var_re likewise; the library's
+ * own, the reference prints none); a non-finite or non-positive diagonal gives NaN.  status 0: ok; 1: some field of the pair is not
+ * finite (the call still succeeds, other pairs are untouched).  pairs: 2 m ints (i0, j0, i1, j1, ...), or NULL for all i < j row by
+ * row (m then 0 or T (T - 1) / 2; fit holds T (T - 1) / 2).  B / VB: NULL (both), or m x 2 x 2 x n_cvt (pass REMLE / MLE, trait,
+ * covariate).  The univariate starts of all T columns come from one null-panel launch; the pairs are walked in chunks sized from
+ * the free device memory (16 n bytes of gathered rows per pair; GEMMA_HIP_MVPAIR_CHUNK=<pairs>, read at the call, forces the size;
+ * a chunk that does not fit returns GEMMA_HIP_ENOMEM with the byte count).  Stateless: no LMM setup is needed or disturbed.
+ * GEMMA_HIP_EINVAL: a null pointer (other than pairs, and B with VB), one of B / VB without the other, T < 2, m == 0 with pairs
+ * given, m neither 0 nor T (T - 1) / 2 without, a pair with i >= j or j >= T, n <= n_cvt + 1, n_cvt outside 1..6 (the fixed
+ * two-trait instances).  The _d form takes device pointers throughout (pairs included), queues its work on `stream` and
+ * synchronises it before it returns; it copies the list back (8 bytes per pair) to check it before anything is launched. */
+typedef struct { double Vg[3], Ve[3], VVg[3], VVe[3], rg, var_rg, re, var_re, logl; } gemma_mvpair_block; /* 00, 01, 11 */
+typedef struct { int i, j, status, pad; gemma_mvpair_block remle, mle; } gemma_mvpair_fit;
+int gemma_hip_mvlmm_null_pairs(size_t n, size_t n_cvt, size_t T, const double *eval, const double *UtW, const double *UtY,
+                               const int *pairs, size_t m, double l_min, double l_max, size_t n_region, const gemma_mvlmm_opt *opt,
+                               gemma_mvpair_fit *fit, double *B, double *VB);
+int gemma_hip_mvlmm_null_pairs_d(size_t n, size_t n_cvt, size_t T, const double *eval_d, const double *UtW_d, const double *UtY_d,
+                                 const int *pairs_d, size_t m, double l_min, double l_max, size_t n_region,
+                                 const gemma_mvlmm_opt *opt, gemma_mvpair_fit *fit_d, double *B_d, double *VB_d, void *stream);
+
 /* ---- linear model without a random effect (-lm 1..4) ----------------------- */
 /* LM::AnalyzeBimbam / AnalyzePlink, src/lm.cpp:382-640 (CalcvPv :224-263, LmCalcP :266-287): per SNP ordinary
  * regression of y on (W, x); a_mode 51 Wald, 52 LRT, 53 score, 54 all (src/gemma.h:39-43).  W (n x n_cvt) and y are

@@ -522,6 +522,33 @@ inline std::vector<NullModel> CalcLambdaNullPanel(const Vector *eval, const Matr
   return out;
 }
 
+// The two-trait null fits of a panel (gemma_hip_mvlmm_null_pairs): element q is the fit of pair q -- pairs (i0, j0, i1, j1, ...) with
+// i < j, or empty for all i < j row by row.  Per pair the bits of gemma_hip_mvlmm_null(d = 2) on the two columns, the variances of
+// V_g / V_e and the genetic / residual correlations with their delta-method variances.  B / VB: m x 2 x 2 x n_cvt (pass, trait,
+// covariate), both or neither.
+inline std::vector<gemma_mvpair_fit> CalcMvNullPairs(const Vector *eval, const Matrix *UtW, const Matrix *UtY,
+                                                     const std::vector<int> &pairs = {}, double l_min = 1e-5, double l_max = 1e5,
+                                                     size_t n_region = 10, const gemma_mvlmm_opt *opt = nullptr,
+                                                     std::vector<double> *B = nullptr, std::vector<double> *VB = nullptr) {
+  const size_t T = UtY->size2, c = UtW->size2;
+  if (UtW->tda != UtW->size2 || UtY->tda != UtY->size2 || eval->stride != 1)
+    throw HipError(GEMMA_HIP_EINVAL, "CalcMvNullPairs: contiguous inputs");
+  if (UtY->size1 != UtW->size1 || eval->size != UtW->size1)
+    throw HipError(GEMMA_HIP_EINVAL, "CalcMvNullPairs: eval, UtW and UtY disagree in their rows");
+  if ((B == nullptr) != (VB == nullptr) || pairs.size() % 2) throw HipError(GEMMA_HIP_EINVAL, "CalcMvNullPairs: B with VB; pairs as (i, j)");
+  const size_t m = pairs.empty() ? T * (T - 1) / 2 : pairs.size() / 2;
+  std::vector<gemma_mvpair_fit> fit(m);
+  if (B) {
+    B->assign(m * 4 * c, 0.0);
+    VB->assign(m * 4 * c, 0.0);
+  }
+  enforce_hip(gemma_hip_mvlmm_null_pairs(UtW->size1, c, T, eval->data, UtW->data, UtY->data, pairs.empty() ? nullptr : pairs.data(),
+                                         pairs.empty() ? 0 : m, l_min, l_max, n_region, opt, fit.data(), B ? B->data() : nullptr,
+                                         VB ? VB->data() : nullptr),
+              "CalcMvNullPairs");
+  return fit;
+}
+
 // class LMM, src/lmm.h:49-125 -- the members CopyFromParam fills (src/lmm.cpp:56-90) and the drivers
 class LMM {
 public:
@@ -1223,6 +1250,10 @@ public:
   size_t ni_total = 0, ni_test = 0, n_cvt = 1, n_ph = 0;
   double logl_remle_H0 = 0.0, logl_mle_H0 = 0.0, time_UtX = 0.0, time_opt = 0.0;
   gemma_mvlmm_null null_fit;
+  // CalcNullSe fills what CopyToParam hands to PARAM (src/mvlmm.cpp:97-110, filled at :3074-3093 / :3140-3159): V_g, V_e as upper
+  // triangles and their VARIANCES VVg / VVe (the log prints safe_sqrt of them, :3110), B and se_B = safe_sqrt(VB)
+  std::vector<double> Vg_remle_null, Ve_remle_null, Vg_mle_null, Ve_mle_null, VVg_remle_null, VVe_remle_null, VVg_mle_null, VVe_mle_null,
+      beta_remle_null, se_beta_remle_null, beta_mle_null, se_beta_mle_null;
   std::vector<int> indicator_idv, indicator_snp;
   std::vector<SNPINFO> snpInfo;
   std::vector<double> sumStat;
@@ -1234,6 +1265,22 @@ public:
     return keep;
   }
   size_t stride() const { return n_ph + 3 * (n_ph * (n_ph + 1) / 2) + 3; }
+
+  // The null block alone with its standard errors (gemma_hip_mvlmm_null_se): null_fit in the bits the Analyze* drivers compute, and
+  // the twelve *_null vectors above.  UtW: the covariates of the null fit (with the U^T env column for the interaction test).
+  void CalcNullSe(const Vector *eval, const Matrix *UtW, const Matrix *UtY) {
+    if (UtW->tda != UtW->size2 || UtY->tda != UtY->size2 || eval->stride != 1)
+      throw HipError(GEMMA_HIP_EINVAL, "MVLMM: contiguous UtW/UtY/eval required");
+    n_ph = UtY->size2;
+    const gemma_mvlmm_opt opt = {em_iter, nr_iter, em_prec, nr_prec, p_nr, crt, 0};
+    gemma_mvlmm_null_se se;
+    enforce_hip(gemma_hip_mvlmm_null_se(UtY->size1, UtW->size2, n_ph, eval->data, UtW->data, UtY->data, l_min, l_max, n_region, &opt,
+                                        &null_fit, &se),
+                "MVLMM (null model, se)");
+    logl_remle_H0 = null_fit.logl_remle_H0;
+    logl_mle_H0 = null_fit.logl_mle_H0;
+    fill_null_members(se, UtW->size2);
+  }
 
   // UtY: ni_test x n_ph row-major (the gsl_matrix the reference passes)
   void AnalyzePlink(const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY) {
@@ -1362,6 +1409,36 @@ public:
   }
 
 private:
+  static double safe_sqrt_(double d) { // src/mathfunc.cpp:122-131
+    double d1 = d;
+    if (d < 0.001) d1 = std::fabs(d);
+    return d1 < 0.0 ? std::nan("") : std::sqrt(d1);
+  }
+  // :3074-3093 ('R') and :3140-3159 ('L'): the upper triangles row by row, then B and se_B row by row (c covariates of the null fit)
+  void fill_null_members(const gemma_mvlmm_null_se &se, size_t c) {
+    const size_t d = n_ph;
+    auto fill = [&](const double *Vg, const double *Ve, const double *B, const double *VVg, const double *VVe, const double *VB,
+                    std::vector<double> &vg, std::vector<double> &ve, std::vector<double> &vvg, std::vector<double> &vve,
+                    std::vector<double> &beta, std::vector<double> &se_beta) {
+      vg.clear(); ve.clear(); vvg.clear(); vve.clear(); beta.clear(); se_beta.clear();
+      size_t v = 0;
+      for (size_t i = 0; i < d; ++i)
+        for (size_t j = i; j < d; ++j, ++v) {
+          vg.push_back(Vg[i * d + j]);
+          ve.push_back(Ve[i * d + j]);
+          vvg.push_back(VVg[v]);
+          vve.push_back(VVe[v]);
+        }
+      for (size_t i = 0; i < d * c; ++i) {
+        beta.push_back(B[i]);
+        se_beta.push_back(safe_sqrt_(VB[i]));
+      }
+    };
+    fill(null_fit.Vg_remle, null_fit.Ve_remle, null_fit.B_remle, se.VVg_remle, se.VVe_remle, se.VB_remle, Vg_remle_null, Ve_remle_null,
+         VVg_remle_null, VVe_remle_null, beta_remle_null, se_beta_remle_null);
+    fill(null_fit.Vg_mle, null_fit.Ve_mle, null_fit.B_mle, se.VVg_mle, se.VVe_mle, se.VB_mle, Vg_mle_null, Ve_mle_null, VVg_mle_null,
+         VVe_mle_null, beta_mle_null, se_beta_mle_null);
+  }
   // the null block (src/mvlmm.cpp:3056-3208) and the per-SNP loop's state
   // UtWe, env: the interaction test (the null model then has UtWe's covariates)
   void setup(const Matrix *U, const Vector *eval, const Matrix *UtW, const Matrix *UtY, int plink, const Matrix *UtWe = nullptr,
