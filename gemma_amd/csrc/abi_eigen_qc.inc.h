@@ -21,15 +21,12 @@ extern "C" int gemma_hip_center_d(double *G, size_t n, void *stream) {
 extern "C" int gemma_hip_center(double *G, size_t n) {
   NEED_INIT();
   if (!G || n == 0) return fail(GEMMA_HIP_EINVAL, "center: empty matrix");
-  DevBuf d;
+  ScopedBuf d;
   if (d.reserve(n * n * 8)) return fail(GEMMA_HIP_ENOMEM, "center: %zu bytes", n * n * 8);
-  hipError_t e = hipMemcpy(d.p, G, n * n * 8, hipMemcpyHostToDevice);
-  int rc = GEMMA_HIP_OK;
-  if (e == hipSuccess) rc = gemma_hip_center_d(d.as<double>(), n, nullptr);
-  if (e == hipSuccess && rc == GEMMA_HIP_OK) e = hipMemcpy(G, d.p, n * n * 8, hipMemcpyDeviceToHost);
-  d.release();
-  if (e != hipSuccess) return fail(GEMMA_HIP_ERUNTIME, "center: %s", hipGetErrorString(e));
-  return rc;
+  HIPCHK(hipMemcpy(d.p, G, n * n * 8, hipMemcpyHostToDevice));
+  if (int rc = gemma_hip_center_d(d.as<double>(), n, nullptr)) return rc;
+  HIPCHK(hipMemcpy(G, d.p, n * n * 8, hipMemcpyDeviceToHost));
+  return GEMMA_HIP_OK;
 }
 
 // The communicator's two collectives as the eigensolver's unit sees them (eigh_tu.h: EighShard)
@@ -126,19 +123,14 @@ extern "C" int gemma_hip_dbg_eigh_last(double *t8) {
 extern "C" int gemma_hip_eigh(double *G, size_t n, double *U, double *eval, double *trace_G) {
   NEED_INIT();
   if (!G || !U || !eval || n == 0) return fail(GEMMA_HIP_EINVAL, "eigh: null/empty argument");
-  DevBuf dG, dU, dE;
-  if (dG.reserve(n * n * 8) || dU.reserve(n * n * 8) || dE.reserve(n * 8)) {
-    dG.release(); dU.release(); dE.release();
+  ScopedBuf dG, dU, dE;
+  if (dG.reserve(n * n * 8) || dU.reserve(n * n * 8) || dE.reserve(n * 8))
     return fail(GEMMA_HIP_ENOMEM, "eigh: cannot allocate 2 x %zu bytes", n * n * 8);
-  }
-  int rc = GEMMA_HIP_OK;
-  hipError_t e = hipMemcpy(dG.p, G, n * n * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) rc = gemma_hip_eigh_d(dG.as<double>(), n, dU.as<double>(), dE.as<double>(), trace_G, nullptr);
-  if (e == hipSuccess && rc == GEMMA_HIP_OK) e = hipMemcpy(U, dU.p, n * n * 8, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && rc == GEMMA_HIP_OK) e = hipMemcpy(eval, dE.p, n * 8, hipMemcpyDeviceToHost);
-  dG.release(); dU.release(); dE.release();
-  if (e != hipSuccess) return fail(GEMMA_HIP_ERUNTIME, "eigh: %s", hipGetErrorString(e));
-  return rc;
+  HIPCHK(hipMemcpy(dG.p, G, n * n * 8, hipMemcpyHostToDevice));
+  if (int rc = gemma_hip_eigh_d(dG.as<double>(), n, dU.as<double>(), dE.as<double>(), trace_G, nullptr)) return rc;
+  HIPCHK(hipMemcpy(U, dU.p, n * n * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(eval, dE.p, n * 8, hipMemcpyDeviceToHost));
+  return GEMMA_HIP_OK;
 }
 
 // ---- diagnostics for the eigensolver stages (used by tests/test_gpu_eigh.py); bodies in eigh_tu.hip ----
@@ -201,9 +193,8 @@ extern "C" int gemma_hip_snp_qc(int kind, const void *geno, size_t l, size_t ld,
   const size_t esz = (kind == GEMMA_GENO_PLINK_2BIT) ? 1 : 8;
   const size_t ncol = QC_NSTAT + n_cvt;
   DevBuf &dG = g_ctx.qc_G, &dM = g_ctx.qc_M, &dW = g_ctx.qc_W, &dO = g_ctx.qc_O; // kept for the next block of the pass
-  auto cleanup = [&]() { dG.release(); dM.release(); dW.release(); dO.release(); };
   if (dG.reserve(l * ld * esz) || dM.reserve(n * sizeof(int)) || dW.reserve(Wt.size() * 8) || dO.reserve(l * ncol * 8)) {
-    cleanup();
+    qc_release();
     return fail(GEMMA_HIP_ENOMEM, "snp_qc: allocation");
   }
   hipError_t e = hipMemcpy2D(dG.p, ld * esz, geno, ld * esz, need * esz, l, hipMemcpyHostToDevice);
@@ -223,8 +214,8 @@ extern "C" int gemma_hip_snp_qc(int kind, const void *geno, size_t l, size_t ld,
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(stats.data(), dO.p, stats.size() * 8, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) {
-    cleanup();
+  if (e != hipSuccess) { // the kept buffers of the pass go with a failed block
+    qc_release();
     return fail(GEMMA_HIP_ERUNTIME, "snp_qc: %s", hipGetErrorString(e));
   }
   QcCfgHost q = {cfg->maf_level, cfg->miss_level, cfg->hwe_level, cfg->r2_level};

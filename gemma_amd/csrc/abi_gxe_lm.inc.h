@@ -21,9 +21,55 @@ extern "C" int gemma_hip_lmm_set_env(const double *env) {
   HIPCHK(launch_dgemm('T', 'N', (long)n, 1, (long)n, 1.0, g_ctx.U, (long)n, g_ctx.gxe_env.as<double>(), 1, 0.0,
                       g_ctx.gxe_UtWt.as<double>() + c * n, 1, false, false, 0));
   HIPCHK(hipDeviceSynchronize());
-  const double df = (double)n - (double)(c + 2) - 1.0;
-  g_ctx.gxe_lnbeta = lgamma(df / 2.0) + lgamma(0.5) - lgamma(df / 2.0 + 0.5);
+  g_ctx.gxe_lnbeta = lnbeta_half((double)n - (double)(c + 2) - 1.0);
   g_ctx.gxe_ready = true;
+  return GEMMA_HIP_OK;
+}
+
+// The rotated operands of a GXE block, univariate (below) and multivariate (mvlmm_gxe_batch_d, abi_mvlmm.inc.h) alike, on stream s.
+struct GxeBlock {
+  double *UtX, *UtZ; // U^T x_s and U^T (x_s . env), l rows of leading dimension ldx
+  int *flip;         // the allele flip of every row
+  size_t ldx;
+};
+// x, z = x . env and the flip of the l rows of a SNP-major block (ingest_gxe_kernel), both rotated by fp64 GEMMs (z is real-valued).
+// who: the caller's name for the error text.
+static int gxe_rotate_block(const char *who, int kind, const void *geno, size_t l, size_t ld, hipStream_t s, GxeBlock &b) {
+  const size_t n = g_ctx.cfg.n;
+  const size_t ldx = (n + 1) & ~(size_t)1;
+  if (int rcf = xp_flush(s)) return rcf; // blocks of the two-block pipeline still in flight share these buffers
+  g_ctx.last_UtX = nullptr;
+  if (g_ctx.X.reserve(l * ldx * 8) || g_ctx.UtX.reserve(l * ldx * 8) || g_ctx.gxe_Z.reserve(l * ldx * 8) ||
+      g_ctx.gxe_UtZ.reserve(l * ldx * 8) || g_ctx.gxe_flip.reserve(l * sizeof(int)))
+    return fail(GEMMA_HIP_ENOMEM, "%s: cannot allocate 4 x %zu bytes", who, l * ldx * 8);
+  double *X = g_ctx.X.as<double>(), *Z = g_ctx.gxe_Z.as<double>();
+  b.UtX = g_ctx.UtX.as<double>();
+  b.UtZ = g_ctx.gxe_UtZ.as<double>();
+  b.flip = g_ctx.gxe_flip.as<int>();
+  b.ldx = ldx;
+  {
+    ProfScope ps(GEMMA_STAGE_INGEST, s);
+    IngestGxeArgs a;
+    a.src = geno; a.ld = (long)ld; a.l = (long)l;
+    a.idx_map = g_ctx.have_map ? g_ctx.idx_map.as<int>() : nullptr;
+    a.n = (int)n; a.env = g_ctx.gxe_env.as<double>(); a.X = X; a.Z = Z; a.ldo = (long)ldx;
+    a.flip = b.flip;
+    const unsigned grid = (unsigned)((l + 3) / 4);
+    if (kind == GEMMA_GENO_PLINK_2BIT)
+      hipLaunchKernelGGL(ingest_gxe_kernel<true>, dim3(grid), dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL(ingest_gxe_kernel<false>, dim3(grid), dim3(256), 0, s, a);
+    HIPCHK(hipGetLastError());
+  }
+  {
+    ProfScope ps(GEMMA_STAGE_UTX_GEMM, s); // U^T x_s (:2364) and U^T (x_s . env) (:2366)
+    const double *Ug;
+    long ldu;
+    int rcu = gemm_U(&Ug, &ldu, s);
+    if (rcu) return rcu;
+    HIPCHK(launch_dgemm('N', 'N', (long)l, (long)n, (long)n, 1.0, X, (long)ldx, Ug, ldu, 0.0, b.UtX, (long)ldx, false, false, s));
+    HIPCHK(launch_dgemm('N', 'N', (long)l, (long)n, (long)n, 1.0, Z, (long)ldx, Ug, ldu, 0.0, b.UtZ, (long)ldx, false, false, s));
+  }
   return GEMMA_HIP_OK;
 }
 
@@ -36,49 +82,17 @@ extern "C" int gemma_hip_lmm_gxe_batch_d(int kind, const void *geno, size_t l, s
   int rc = block_geom("lmm_gxe_batch", kind, g_ctx.cfg.n, true, geno, l, ld, out_d);
   if (rc) return rc;
   hipStream_t s = S(stream);
-  const size_t n = g_ctx.cfg.n, c = g_ctx.cfg.n_cvt;
-  const size_t ldx = (n + 1) & ~(size_t)1;
-  if (int rcf = xp_flush(s)) return rcf; // blocks of the two-block pipeline still in flight share these buffers
-  g_ctx.last_UtX = nullptr;
-  if (g_ctx.X.reserve(l * ldx * 8) || g_ctx.UtX.reserve(l * ldx * 8) || g_ctx.gxe_Z.reserve(l * ldx * 8) ||
-      g_ctx.gxe_UtZ.reserve(l * ldx * 8) || g_ctx.gxe_flip.reserve(l * sizeof(int)))
-    return fail(GEMMA_HIP_ENOMEM, "lmm_gxe_batch: cannot allocate 4 x %zu bytes", l * ldx * 8);
-  double *X = g_ctx.X.as<double>(), *UtX = g_ctx.UtX.as<double>();
-  double *Z = g_ctx.gxe_Z.as<double>(), *UtZ = g_ctx.gxe_UtZ.as<double>();
-  {
-    ProfScope ps(GEMMA_STAGE_INGEST, s);
-    IngestGxeArgs a;
-    a.src = geno; a.ld = (long)ld; a.l = (long)l;
-    a.idx_map = g_ctx.have_map ? g_ctx.idx_map.as<int>() : nullptr;
-    a.n = (int)n; a.env = g_ctx.gxe_env.as<double>(); a.X = X; a.Z = Z; a.ldo = (long)ldx;
-    a.flip = g_ctx.gxe_flip.as<int>();
-    const unsigned grid = (unsigned)((l + 3) / 4);
-    if (kind == GEMMA_GENO_PLINK_2BIT)
-      hipLaunchKernelGGL(ingest_gxe_kernel<true>, dim3(grid), dim3(256), 0, s, a);
-    else
-      hipLaunchKernelGGL(ingest_gxe_kernel<false>, dim3(grid), dim3(256), 0, s, a);
-    HIPCHK(hipGetLastError());
-  }
-  {
-    ProfScope ps(GEMMA_STAGE_UTX_GEMM, s); // U^T x_s (:2364) and U^T (x_s . env) (:2366); z is real-valued: fp64 GEMMs
-    const double *Ug;
-    long ldu;
-    int rcu = gemm_U(&Ug, &ldu, s);
-    if (rcu) return rcu;
-    HIPCHK(launch_dgemm('N', 'N', (long)l, (long)n, (long)n, 1.0, X, (long)ldx, Ug, ldu, 0.0, UtX, (long)ldx,
-                        false, false, s));
-    HIPCHK(launch_dgemm('N', 'N', (long)l, (long)n, (long)n, 1.0, Z, (long)ldx, Ug, ldu, 0.0, UtZ, (long)ldx,
-                        false, false, s));
-  }
-  AssocArgs a = g_ctx.assoc_proto;
-  a.UtX = UtX; a.UtZ = UtZ; a.flip = g_ctx.gxe_flip.as<int>();
-  a.ld = (long)ldx; a.l = (long)l;
-  a.eval = g_ctx.eval; a.Uty = g_ctx.Uty; a.UtWt = g_ctx.gxe_UtWt.as<double>();
+  const size_t c = g_ctx.cfg.n_cvt;
+  GxeBlock b;
+  if ((rc = gxe_rotate_block("lmm_gxe_batch", kind, geno, l, ld, s, b))) return rc;
+  AssocArgs a = g_ctx.single.proto;
+  a.UtX = b.UtX; a.UtZ = b.UtZ; a.flip = b.flip;
+  a.ld = (long)b.ldx; a.l = (long)l;
+  a.eval = g_ctx.eval; a.Uty = g_ctx.single.Uty; a.UtWt = g_ctx.gxe_UtWt.as<double>();
   a.out = reinterpret_cast<SumStat *>(out_d);
   a.lnbeta_half_df = g_ctx.gxe_lnbeta; // df = n - (c + 2) - 1
   a.grid_T = nullptr;
   a.have_grid = 0;
-  a.have_logdet_ends = g_ctx.assoc_proto.have_logdet_ends;
   const unsigned grid = (unsigned)((l + 3) / 4);
   {
     ProfScope ps(GEMMA_STAGE_ASSOC, s);
@@ -181,8 +195,7 @@ extern "C" int gemma_hip_lm_setup(int a_mode, size_t n, size_t n_cvt, const doub
   a.n = (int)n;
   a.c = c;
   a.test_mode = a_mode - 50;
-  const double df = (double)n - (double)c - 1.0;
-  a.lnbeta_half_df = lgamma(df / 2.0) + lgamma(0.5) - lgamma(df / 2.0 + 0.5);
+  a.lnbeta_half_df = lnbeta_half((double)n - (double)c - 1.0);
   g_ctx.cfg.n = n; // shared with the ingest / indicator code
   g_ctx.cfg.n_cvt = n_cvt;
   g_ctx.have_map = false;
@@ -250,58 +263,42 @@ extern "C" int gemma_hip_lmm_null(size_t n, size_t n_cvt, const double *eval, co
     return fail(GEMMA_HIP_EINVAL, "lmm_null: bad arguments (n_cvt 1..%d)", GEN_CMAX_WIDE + 1);
   if (!(l_max > l_min) || n_region == 0 || n_region > (size_t)ASSOC_MAX_REGION || n <= n_cvt)
     return fail(GEMMA_HIP_EINVAL, "lmm_null: l_min/l_max/n_region/n");
-  DevBuf dE, dW, dWt, dY, dO;
-  auto cleanup = [&]() { dE.release(); dW.release(); dWt.release(); dY.release(); dO.release(); };
+  ScopedBuf dE, dW, dWt, dY, dO;
   if (dE.reserve(n * 8) || dW.reserve(n * n_cvt * 8) || dWt.reserve(n * n_cvt * 8) || dY.reserve(n * 8) ||
-      dO.reserve(sizeof(NullOut))) {
-    cleanup();
+      dO.reserve(sizeof(NullOut)))
     return fail(GEMMA_HIP_ENOMEM, "lmm_null: allocation");
-  }
-  hipError_t e = hipMemcpy(dE.p, eval, n * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dW.p, UtW, n * n_cvt * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dY.p, Uty, n * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    dim3 grid((unsigned)((n_cvt + 31) / 32), (unsigned)((n + 31) / 32));
-    hipLaunchKernelGGL(transpose_kernel, grid, dim3(32, 8), 0, 0, dW.as<double>(), (long)n, (long)n_cvt,
-                       (long)n_cvt, dWt.as<double>(), (long)n);
-    AssocArgs a;
-    memset(&a, 0, sizeof a);
-    a.n = (int)n; a.n_region = (int)n_region; a.l_min = l_min; a.l_max = l_max;
-    a.eval = dE.as<double>(); a.Uty = dY.as<double>(); a.UtWt = dWt.as<double>();
-    const double lambda_interval = log(l_max / l_min) / (double)n_region;
-    for (size_t i = 0; i <= n_region; ++i) a.lam_grid[i] = l_min * exp(lambda_interval * (double)i);
-    NullOut *o = dO.as<NullOut>();
-    switch (n_cvt) {
-    case 1: hipLaunchKernelGGL(lmm_null_kernel<0>, dim3(1), dim3(64), 0, 0, a, o); break;
-    case 2: hipLaunchKernelGGL(lmm_null_kernel<1>, dim3(1), dim3(64), 0, 0, a, o); break;
-    case 3: hipLaunchKernelGGL(lmm_null_kernel<2>, dim3(1), dim3(64), 0, 0, a, o); break;
-    case 4: hipLaunchKernelGGL(lmm_null_kernel<3>, dim3(1), dim3(64), 0, 0, a, o); break;
-    case 5: hipLaunchKernelGGL(lmm_null_kernel<4>, dim3(1), dim3(64), 0, 0, a, o); break;
-    default:
-      if (n_cvt - 1 > (size_t)GEN_CMAX) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(lmm_null_wide_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)wide_lds_bytes(GEN_CMAX_WIDE));
-        hipLaunchKernelGGL(lmm_null_wide_kernel, dim3(1), dim3(64), wide_lds_bytes(n_cvt - 1), 0, a, (int)n_cvt - 1, o);
-      } else {
-        hipLaunchKernelGGL(lmm_null_generic_kernel, dim3(1), dim3(64), 0, 0, a, (int)n_cvt - 1, o);
-      }
-      break;
+  HIPCHK(hipMemcpy(dE.p, eval, n * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dW.p, UtW, n * n_cvt * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dY.p, Uty, n * 8, hipMemcpyHostToDevice));
+  dim3 grid((unsigned)((n_cvt + 31) / 32), (unsigned)((n + 31) / 32));
+  hipLaunchKernelGGL(transpose_kernel, grid, dim3(32, 8), 0, 0, dW.as<double>(), (long)n, (long)n_cvt,
+                     (long)n_cvt, dWt.as<double>(), (long)n);
+  AssocArgs a;
+  memset(&a, 0, sizeof a);
+  a.n = (int)n; a.n_region = (int)n_region; a.l_min = l_min; a.l_max = l_max;
+  a.eval = dE.as<double>(); a.Uty = dY.as<double>(); a.UtWt = dWt.as<double>();
+  fill_lam_grid(a, l_min, l_max, n_region);
+  NullOut *o = dO.as<NullOut>();
+  switch (n_cvt) {
+  case 1: hipLaunchKernelGGL(lmm_null_kernel<0>, dim3(1), dim3(64), 0, 0, a, o); break;
+  case 2: hipLaunchKernelGGL(lmm_null_kernel<1>, dim3(1), dim3(64), 0, 0, a, o); break;
+  case 3: hipLaunchKernelGGL(lmm_null_kernel<2>, dim3(1), dim3(64), 0, 0, a, o); break;
+  case 4: hipLaunchKernelGGL(lmm_null_kernel<3>, dim3(1), dim3(64), 0, 0, a, o); break;
+  case 5: hipLaunchKernelGGL(lmm_null_kernel<4>, dim3(1), dim3(64), 0, 0, a, o); break;
+  default:
+    if (n_cvt - 1 > (size_t)GEN_CMAX) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(lmm_null_wide_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)wide_lds_bytes(GEN_CMAX_WIDE));
+      hipLaunchKernelGGL(lmm_null_wide_kernel, dim3(1), dim3(64), wide_lds_bytes(n_cvt - 1), 0, a, (int)n_cvt - 1, o);
+    } else {
+      hipLaunchKernelGGL(lmm_null_generic_kernel, dim3(1), dim3(64), 0, 0, a, (int)n_cvt - 1, o);
     }
-    e = hipGetLastError();
+    break;
   }
+  HIPCHK(hipGetLastError());
   NullOut h;
-  if (e == hipSuccess) e = hipMemcpy(&h, dO.p, sizeof h, hipMemcpyDeviceToHost);
-  cleanup();
-  if (e != hipSuccess) return fail(GEMMA_HIP_ERUNTIME, "lmm_null: %s", hipGetErrorString(e));
-  out8[0] = h.l_mle; out8[1] = h.logl_mle; out8[2] = h.l_remle; out8[3] = h.logl_remle;
-  // CalcPve, src/lmm.cpp:2197-2200 (safe_sqrt semantics of src/mathfunc.cpp:122-131)
-  double arg = -1.0 / h.dev2_remle, d1 = arg;
-  if (arg < 0.001) d1 = fabs(arg);
-  const double se = (d1 < 0.0) ? NAN : sqrt(d1);
-  out8[4] = trace_G * h.l_remle / (trace_G * h.l_remle + 1.0);
-  out8[5] = trace_G / ((trace_G * h.l_remle + 1.0) * (trace_G * h.l_remle + 1.0)) * se;
-  out8[7] = h.Pyy_remle / (double)(n - n_cvt); // ve, src/lmm.cpp:2258
-  out8[6] = out8[7] * h.l_remle;               // vg
+  HIPCHK(hipMemcpy(&h, dO.p, sizeof h, hipMemcpyDeviceToHost));
+  null_derive(h, trace_G, n, n_cvt, out8);
   return GEMMA_HIP_OK;
 }
 

@@ -90,39 +90,33 @@ static int eigh_kept_K_impl(const int *indicator_idv, size_t ni_total, double *e
     if (!indicator_idv || indicator_idv[i] != 0) map.push_back((int)i);
   const size_t n = map.size();
   if (n == 0) return fail(GEMMA_HIP_EINVAL, "eigh_kept_K: no analysed individual");
-  DevBuf G, dmap;
+  ScopedBuf G, dmap;
   if (G.reserve(n * n * 8) || dmap.reserve(n * sizeof(int))) {
-    G.release(); dmap.release();
     eigh_abort_if_sharded(sharded, n, nullptr);
     return fail(GEMMA_HIP_ENOMEM, "eigh_kept_K: %zu bytes", n * n * 8);
   }
-  int rc = GEMMA_HIP_OK;
-  hipError_t e = hipMemcpy(dmap.p, map.data(), n * sizeof(int), hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    // the rows / columns ReadFile_kin keeps (src/gemma_io.cpp:1205-1243), then CenterMatrix, then EigenDecomp_Zeroed
+  // the rows / columns ReadFile_kin keeps (src/gemma_io.cpp:1205-1243), then CenterMatrix
+  auto subselect_and_centre = [&]() -> int {
+    HIPCHK(hipMemcpy(dmap.p, map.data(), n * sizeof(int), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(subselect_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)n), dim3(256), 0, 0,
                        g_ctx.kept_K.as<double>(), (long)ni_total, dmap.as<int>(), (long)n, G.as<double>());
-    e = hipGetLastError();
+    HIPCHK(hipGetLastError());
+    return gemma_hip_center_d(G.as<double>(), n, nullptr);
+  };
+  if (int rc = subselect_and_centre()) {
+    eigh_abort_if_sharded(sharded, n, nullptr); // failed on this rank alone: the others are told
+    return rc;
   }
-  if (e == hipSuccess) rc = gemma_hip_center_d(G.as<double>(), n, nullptr);
-  if (e == hipSuccess && rc == GEMMA_HIP_OK) rc = kept_eigh_of(G.as<double>(), n, eval, trace_G, sharded);
-  else eigh_abort_if_sharded(sharded, n, nullptr); // sub-selection or centring failed on this rank alone
-  G.release(); dmap.release();
-  if (e != hipSuccess) return fail(GEMMA_HIP_ERUNTIME, "eigh_kept_K: %s", hipGetErrorString(e));
-  return rc;
+  return kept_eigh_of(G.as<double>(), n, eval, trace_G, sharded); // EigenDecomp_Zeroed
 }
 
 extern "C" int gemma_hip_eigh_keep(const double *G, size_t n, double *eval, double *trace_G) {
   NEED_INIT();
   if (!G || n == 0) return fail(GEMMA_HIP_EINVAL, "eigh_keep: null/empty argument");
-  DevBuf dG;
+  ScopedBuf dG;
   if (dG.reserve(n * n * 8)) return fail(GEMMA_HIP_ENOMEM, "eigh_keep: %zu bytes", n * n * 8);
-  hipError_t e = hipMemcpy(dG.p, G, n * n * 8, hipMemcpyHostToDevice);
-  int rc = GEMMA_HIP_OK;
-  if (e == hipSuccess) rc = kept_eigh_of(dG.as<double>(), n, eval, trace_G);
-  dG.release();
-  if (e != hipSuccess) return fail(GEMMA_HIP_ERUNTIME, "eigh_keep: %s", hipGetErrorString(e));
-  return rc;
+  HIPCHK(hipMemcpy(dG.p, G, n * n * 8, hipMemcpyHostToDevice));
+  return kept_eigh_of(dG.as<double>(), n, eval, trace_G);
 }
 
 extern "C" int gemma_hip_kept_n(size_t *n) {
@@ -173,19 +167,12 @@ extern "C" int gemma_hip_calc_utx_kept(const double *X, size_t n, size_t m, doub
   NEED_INIT();
   if (!g_ctx.kept_n) return fail(GEMMA_HIP_ESTATE, "calc_utx_kept: no kept U");
   if (n != g_ctx.kept_n || !X || !UtX || m == 0) return fail(GEMMA_HIP_EINVAL, "calc_utx_kept: n=%zu, kept U is %zu", n, g_ctx.kept_n);
-  DevBuf dX, dO;
-  if (dX.reserve(n * m * 8) || dO.reserve(n * m * 8)) {
-    dX.release(); dO.release();
-    return fail(GEMMA_HIP_ENOMEM, "calc_utx_kept: %zu bytes", 2 * n * m * 8);
-  }
-  hipError_t e = hipMemcpy(dX.p, X, n * m * 8, hipMemcpyHostToDevice);
-  int rc = GEMMA_HIP_OK;
-  if (e == hipSuccess)
-    rc = gemma_hip_dgemm_d('T', 'N', n, m, n, 1.0, kept_U(), n, dX.as<double>(), m, 0.0, dO.as<double>(), m, nullptr);
-  if (e == hipSuccess && rc == GEMMA_HIP_OK) e = hipMemcpy(UtX, dO.p, n * m * 8, hipMemcpyDeviceToHost);
-  dX.release(); dO.release();
-  if (e != hipSuccess) return fail(GEMMA_HIP_ERUNTIME, "calc_utx_kept: %s", hipGetErrorString(e));
-  return rc;
+  ScopedBuf dX, dO;
+  if (dX.reserve(n * m * 8) || dO.reserve(n * m * 8)) return fail(GEMMA_HIP_ENOMEM, "calc_utx_kept: %zu bytes", 2 * n * m * 8);
+  HIPCHK(hipMemcpy(dX.p, X, n * m * 8, hipMemcpyHostToDevice));
+  if (int rc = gemma_hip_dgemm_d('T', 'N', n, m, n, 1.0, kept_U(), n, dX.as<double>(), m, 0.0, dO.as<double>(), m, nullptr)) return rc;
+  HIPCHK(hipMemcpy(UtX, dO.p, n * m * 8, hipMemcpyDeviceToHost));
+  return GEMMA_HIP_OK;
 }
 
 extern "C" int gemma_hip_lmm_setup_kept(const gemma_lmm_cfg *cfg, const double *UtW, const double *Uty) {

@@ -8,7 +8,7 @@ extern "C" int gemma_hip_kin_begin(size_t n_total, int k_mode) {
   NEED_INIT();
   if (n_total == 0) return fail(GEMMA_HIP_EINVAL, "kin_begin: n_total == 0");
   if (k_mode != 1 && k_mode != 2) return fail(GEMMA_HIP_EINVAL, "kin_begin: k_mode %d", k_mode);
-  g_ctx.qc_G.release(); g_ctx.qc_M.release(); g_ctx.qc_W.release(); g_ctx.qc_O.release(); // the first pass is over
+  qc_release(); // the first pass is over
   g_ctx.kin_ingested_valid = false;
   if (g_ctx.kin_K.reserve(n_total * n_total * 8))
     return fail(GEMMA_HIP_ENOMEM, "kin_begin: cannot allocate K (%zu bytes)", n_total * n_total * 8);

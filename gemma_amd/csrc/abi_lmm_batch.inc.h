@@ -207,7 +207,7 @@ static int lmm_batch_plink_chunked(const void *geno, size_t l, size_t ld, gemma_
       break;
     }
     if ((rc = i8_post_rows(l, d, row0, rows, UtX, ldx, side))) break;
-    if ((rc = launch_assoc(UtX + row0 * ldx, rows, ldx, out_d + row0, side))) break;
+    if ((rc = launch_assoc(g_ctx.single, UtX + row0 * ldx, rows, ldx, out_d + row0, side))) break;
   }
   // whatever happened, the caller's stream is ordered behind the side stream again before this call hands it back
   (void)hipEventRecord(g_ctx.ov_done, side);
@@ -292,7 +292,7 @@ extern "C" int gemma_hip_lmm_batch_pipe_d(int kind, const void *geno, size_t l, 
   HIPCHK(hipStreamWaitEvent(x.Q, x.prod_done[slot], 0));
   double *UtX = g_ctx.UtX.as<double>();
   rc = i8_post_rows(l, d, 0, l, UtX, ldx, x.Q);
-  if (!rc) rc = launch_assoc(UtX, l, ldx, out_d, x.Q);
+  if (!rc) rc = launch_assoc(g_ctx.single, UtX, l, ldx, out_d, x.Q);
   // whatever happened, what was queued on Q is waited for by the next user of this buffer set and by the flush
   (void)hipEventRecord(x.post_done[slot], x.Q);
   x.post_valid[slot] = true;
@@ -319,7 +319,7 @@ extern "C" int gemma_hip_lmm_batch_d(int kind, const void *geno, size_t l, size_
   size_t ldx;
   rc = compute_utx(kind, geno, l, ld, -1, &UtX, &ldx, s);
   if (rc) return rc;
-  return launch_assoc(UtX, l, ldx, out_d, s);
+  return launch_assoc(g_ctx.single, UtX, l, ldx, out_d, s);
 }
 
 // LMM::AnalyzeGene (src/lmm.cpp:1365-1471): rows are phenotypes (gene expression over the analysed individuals), the
@@ -346,9 +346,9 @@ extern "C" int gemma_hip_lmm_gene_batch_d(const double *Y_d, size_t l, size_t ld
     HIPCHK(launch_dgemm('N', 'N', (long)l, (long)n, (long)n, 1.0, Y_d, (long)ld, Ug, ldu, 0.0, UtY, (long)ldx,
                         false, false, s));
   }
-  AssocArgs a = g_ctx.assoc_proto;
+  AssocArgs a = g_ctx.single.proto;
   a.UtX = UtY; a.ld = (long)ldx; a.l = (long)l;
-  a.eval = g_ctx.eval; a.Uty = g_ctx.Uty; a.UtWt = g_ctx.UtWt.as<double>();
+  a.eval = g_ctx.eval; a.Uty = g_ctx.single.Uty; a.UtWt = g_ctx.UtWt.as<double>();
   a.out = reinterpret_cast<SumStat *>(out_d);
   a.grid_T = nullptr;
   a.have_grid = 0;

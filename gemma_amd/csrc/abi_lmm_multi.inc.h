@@ -2,8 +2,8 @@
 // This part: T univariate LMMs over one U^T x (gemma_hip_lmm_multi_*): the phenotype slots, the shared fixed-lambda table.
 //
 // A block costs ingest + U^T x ONCE (50 of 56 ms at n = B = 20 000) and the per-SNP stage per phenotype (3 ms).  What of a setup
-// belongs to the phenotype is a Ctx::PhenoSlot; the per-SNP stage of phenotype t runs with slot t swapped into the live members,
-// i.e. it is launch_assoc as a single-phenotype setup of y_t runs it: same kernels, same arguments, same launch shapes, its own
+// belongs to the phenotype is a Ctx::PhenoSlot; the per-SNP stage of phenotype t is launch_assoc on slot t, as a single-phenotype
+// setup of y_t runs it on the single slot: same kernels, same arguments, same launch shapes, its own
 // PLINK carry chain in block order.  Of the stage's two reads of U^T x the first (the dense fixed-lambda table) depends on the
 // phenotype in nq of its columns only: table_v2_kernel on the weight matrix of a group of multi_G phenotypes and
 // table_multi_reduce_kernel (lmm_grid.hip.h) give the group's tables from one read, bit for bit the tables launch_grid_table
@@ -54,17 +54,17 @@ static int multi_setup_slots(size_t T, const double *l_mle_null, const double *l
   g_ctx.slots.resize(T);
   g_ctx.multi_T = T; // from here on a failure leaves a multi state that lmm_common_setup / the caller's multi_release takes down
   for (size_t t = 0; t < T; ++t) {
-    if (t > 0) {
-      g_ctx.assoc_proto = g_ctx.slots[0].proto; // the setup's part of it (grid, log-determinant ends); make_grid redoes the tables' part
-      if (g_ctx.carry.reserve(4 * 8)) return fail(GEMMA_HIP_ENOMEM, "lmm_multi_setup: carry");
-      HIPCHK(hipMemset(g_ctx.carry.p, 0, 4 * 8));
-      g_ctx.carry_flip = 0;
-    }
-    g_ctx.assoc_proto.l_mle_null = l_mle_null ? l_mle_null[t] : 0.0;
-    g_ctx.assoc_proto.logl_mle_H0 = logl_mle_H0 ? logl_mle_H0[t] : 0.0;
-    g_ctx.Uty = g_ctx.multi_Yt.as<double>() + t * n;
-    const int rc = t == 0 ? make_utwt(UtW_d, s) : make_grid(s);
-    slot_swap(g_ctx.slots[t]); // parked, whatever happened: multi_release finds every buffer in a slot
+    Ctx::PhenoSlot &p = g_ctx.slots[t]; // built in place: whatever happens, multi_release finds every buffer in a slot
+    // the setup's part of the proto: lmm_common_setup's for slot 0, which make_utwt completes (log-determinant ends); slot 0's for
+    // the others, of which make_grid redoes the tables' part
+    p.proto = t == 0 ? g_ctx.single.proto : g_ctx.slots[0].proto;
+    if (p.carry.reserve(4 * 8)) return fail(GEMMA_HIP_ENOMEM, "lmm_multi_setup: carry");
+    HIPCHK(hipMemset(p.carry.p, 0, 4 * 8));
+    p.carry_flip = 0;
+    p.proto.l_mle_null = l_mle_null ? l_mle_null[t] : 0.0;
+    p.proto.logl_mle_H0 = logl_mle_H0 ? logl_mle_H0[t] : 0.0;
+    p.Uty = g_ctx.multi_Yt.as<double>() + t * n;
+    const int rc = t == 0 ? make_utwt(p, UtW_d, s) : make_grid(p, s);
     if (rc == GEMMA_HIP_ENOMEM) {
       const Ctx::PhenoSlot &p0 = g_ctx.slots[0];
       const size_t per = p0.grid_R.cap + p0.grid_F.cap + p0.cheb_R.cap + p0.cheb_F.cap;
@@ -181,10 +181,8 @@ extern "C" int gemma_hip_lmm_multi_batch_d(int kind, const void *geno, size_t l,
       if (rc) shared = false; // an accelerator, not a requirement (launch_assoc): this and the later groups compute their own tables
     }
     for (size_t g = 0; g < Gn; ++g) {
-      Ctx::PhenoSlot &p = g_ctx.slots[t0 + g];
-      slot_swap(p);
-      rc = launch_assoc(UtX, l, ldx, out_d + (t0 + g) * l, s, shared ? g_ctx.multi_T_buf.as<double>() + g * tstride : nullptr);
-      slot_swap(p);
+      rc = launch_assoc(g_ctx.slots[t0 + g], UtX, l, ldx, out_d + (t0 + g) * l, s,
+                        shared ? g_ctx.multi_T_buf.as<double>() + g * tstride : nullptr);
       if (rc) return rc;
     }
   }

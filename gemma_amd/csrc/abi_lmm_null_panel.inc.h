@@ -55,8 +55,7 @@ static int null_panel_launch(size_t n, size_t n_cvt, size_t Tc, const double *ev
   memset(&a, 0, sizeof a);
   a.n = (int)n; a.n_region = (int)n_region; a.l_min = l_min; a.l_max = l_max;
   a.eval = eval_d; a.UtWt = UtWt_d;
-  const double lambda_interval = log(l_max / l_min) / (double)n_region; // the grid of gemma_hip_lmm_null
-  for (size_t i = 0; i <= n_region; ++i) a.lam_grid[i] = l_min * exp(lambda_interval * (double)i);
+  fill_lam_grid(a, l_min, l_max, n_region);
   const int T = (int)Tc, cp = (int)n_cvt - 1;
   const dim3 grid((unsigned)((Tc + NP_WAVES - 1) / NP_WAVES)), block(64 * NP_WAVES);
   switch (n_cvt) {
@@ -98,7 +97,7 @@ extern "C" int gemma_hip_lmm_null_panel_d(size_t n, size_t n_cvt, size_t T, cons
   int rc = null_panel_check(n, n_cvt, T, eval_d, UtW_d, UtY_d, l_min, l_max, n_region, fit_d, beta_d, se_beta_d);
   if (rc) return rc;
   hipStream_t s = S(stream);
-  DevBuf dWt, dYt, dO;
+  ScopedBuf dWt, dYt, dO;
   auto body = [&]() -> int {
     int r = null_panel_wt(n, n_cvt, UtW_d, dWt, s);
     if (r) return r;
@@ -120,8 +119,7 @@ extern "C" int gemma_hip_lmm_null_panel_d(size_t n, size_t n_cvt, size_t T, cons
     return GEMMA_HIP_OK;
   };
   rc = body();
-  if (rc) (void)hipStreamSynchronize(s);
-  dWt.release(); dYt.release(); dO.release();
+  if (rc) (void)hipStreamSynchronize(s); // before the buffers go
   return rc;
 }
 
@@ -131,7 +129,7 @@ extern "C" int gemma_hip_lmm_null_panel(size_t n, size_t n_cvt, size_t T, const 
   NEED_INIT();
   int rc = null_panel_check(n, n_cvt, T, eval, UtW, UtY, l_min, l_max, n_region, fit, beta, se_beta);
   if (rc) return rc;
-  DevBuf dE, dW, dWt, dY, dYt, dO, dB;
+  ScopedBuf dE, dW, dWt, dY, dYt, dO, dB;
   auto body = [&]() -> int {
     if (dE.reserve(n * 8) || dW.reserve(n * n_cvt * 8))
       return fail(GEMMA_HIP_ENOMEM, "lmm_null_panel: eval and U^T W (%zu bytes)", n * 8 + n * n_cvt * 8);
@@ -146,7 +144,6 @@ extern "C" int gemma_hip_lmm_null_panel(size_t n, size_t n_cvt, size_t T, const 
         (beta && dB.reserve(chunk * b_col)))
       return fail(GEMMA_HIP_ENOMEM, "lmm_null_panel: a chunk of %zu phenotypes does not fit (%zu bytes)", chunk, chunk * per_col);
     std::vector<NullOut> h(chunk);
-    const double df = (double)(n - n_cvt);
     for (size_t t0 = 0; t0 < T; t0 += chunk) {
       const size_t Tc = std::min(chunk, T - t0);
       HIPCHK(hipMemcpy2D(dY.p, Tc * 8, UtY + t0, T * 8, Tc * 8, n, hipMemcpyHostToDevice));
@@ -159,24 +156,11 @@ extern "C" int gemma_hip_lmm_null_panel(size_t n, size_t n_cvt, size_t T, const 
         HIPCHK(hipMemcpy(beta + t0 * n_cvt, b_d, Tc * n_cvt * 8, hipMemcpyDeviceToHost));
         HIPCHK(hipMemcpy(se_beta + t0 * n_cvt, s_d, Tc * n_cvt * 8, hipMemcpyDeviceToHost));
       }
-      for (size_t k = 0; k < Tc; ++k) { // the derived fields as gemma_hip_lmm_null forms them
-        const NullOut &o = h[k];
-        gemma_null_fit &f = fit[t0 + k];
-        f.l_mle_null = o.l_mle; f.logl_mle_H0 = o.logl_mle; f.l_remle_null = o.l_remle; f.logl_remle_H0 = o.logl_remle;
-        // CalcPve, src/lmm.cpp:2197-2200 (safe_sqrt semantics of src/mathfunc.cpp:122-131)
-        double arg = -1.0 / o.dev2_remle, d1 = arg;
-        if (arg < 0.001) d1 = fabs(arg);
-        const double se = (d1 < 0.0) ? NAN : sqrt(d1);
-        f.pve = trace_G * o.l_remle / (trace_G * o.l_remle + 1.0);
-        f.pve_se = trace_G / ((trace_G * o.l_remle + 1.0) * (trace_G * o.l_remle + 1.0)) * se;
-        f.ve_remle = o.Pyy_remle / df; // ve, src/lmm.cpp:2258
-        f.vg_remle = f.ve_remle * o.l_remle;
-      }
+      for (size_t k = 0; k < Tc; ++k) null_derive(h[k], trace_G, n, n_cvt, reinterpret_cast<double *>(fit + t0 + k)); // a gemma_null_fit is out8
     }
     return GEMMA_HIP_OK;
   };
   rc = body();
-  if (rc) (void)hipDeviceSynchronize();
-  dE.release(); dW.release(); dWt.release(); dY.release(); dYt.release(); dO.release(); dB.release();
+  if (rc) (void)hipDeviceSynchronize(); // before the buffers go
   return rc;
 }

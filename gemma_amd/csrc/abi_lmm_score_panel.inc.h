@@ -111,7 +111,7 @@ static int launch_score_panel(const double *UtX, size_t l, size_t ld, gemma_scor
   a.Rp = g_ctx.score_R.as<double>();
   a.Pyy = g_ctx.score_Pyy.as<double>();
   a.out = reinterpret_cast<ScoreRec *>(out_d);
-  a.lnbeta_half_df = g_ctx.assoc_proto.lnbeta_half_df;
+  a.lnbeta_half_df = g_ctx.single.proto.lnbeta_half_df;
   const size_t npt = ((size_t)g.ng + 2 * SP_PG - 1) / (2 * SP_PG), nst = (l + 32 * SP_RG - 1) / (32 * SP_RG);
   if (npt * nst > 0x7fffffffUL) return fail(GEMMA_HIP_EINVAL, "lmm_score_panel_batch: %zu x %zu tiles in one block", nst, npt);
   ProfScope ps(GEMMA_STAGE_ASSOC, s);
@@ -186,7 +186,7 @@ static int score_hits_empty(unsigned long long *n_hits_d, gemma_score_best *best
   if (best_d) {
     const ScoreGeom &g = g_ctx.score_geom;
     hipLaunchKernelGGL(score_best_kernel, dim3((unsigned)((g.T + 255) / 256)), dim3(256), 0, s, g, 0L, (const ScoreCell *)nullptr,
-                       g_ctx.score_Pyy.as<double>(), g_ctx.assoc_proto.lnbeta_half_df, reinterpret_cast<ScoreBest *>(best_d));
+                       g_ctx.score_Pyy.as<double>(), g_ctx.single.proto.lnbeta_half_df, reinterpret_cast<ScoreBest *>(best_d));
     HIPCHK(hipGetLastError());
   }
   return GEMMA_HIP_OK;
@@ -202,7 +202,7 @@ static int launch_score_hits(const double *UtX, size_t l, size_t ld, double p_ma
   if (best_d && g_ctx.score_cells.reserve(ntile * (size_t)g.T * sizeof(ScoreCell)))
     return fail(GEMMA_HIP_ENOMEM, "lmm_score_panel_hits: the per-wave best of %zu row tiles x %d phenotypes (%zu bytes)", ntile, g.T,
                 ntile * (size_t)g.T * sizeof(ScoreCell));
-  const double lnb = g_ctx.assoc_proto.lnbeta_half_df;
+  const double lnb = g_ctx.single.proto.lnbeta_half_df;
   if (g_ctx.score_fthr_p != p_max || g_ctx.score_fthr_s != s) { // once per (setup, p_max, stream)
     hipLaunchKernelGGL(score_fcrit_kernel, dim3(1), dim3(64), 0, s, p_max, (double)(g.n - g.c - 1), lnb, g_ctx.score_fthr.as<double>());
     HIPCHK(hipGetLastError());

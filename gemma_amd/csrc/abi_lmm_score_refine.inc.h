@@ -37,7 +37,7 @@ static int refine_setup_dev(const double *UtY_d, const double *logl, hipStream_t
   HIPCHK(hipMemcpyAsync(ends, g_ctx.scratch.p, 16, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   AssocArgs &a = g_ctx.refine_proto;
-  a = g_ctx.assoc_proto; // n, the grid and ln B(df / 2, 1 / 2) of the cfg (lmm_common_setup); no table, no series
+  a = g_ctx.single.proto; // n, the grid and ln B(df / 2, 1 / 2) of the cfg (lmm_common_setup); no table, no series
   a.a_mode = 4;
   a.plink_nan_rule = 0;
   a.l_mle_null = a.logl_mle_H0 = 0.0; // per pair: PairArgs

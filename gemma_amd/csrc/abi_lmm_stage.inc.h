@@ -5,22 +5,8 @@
 // Chebyshev series, launch_assoc.
 
 // ------------------------------------------------------------------------------ LMM
-// Phenotype slots of a multi setup (Ctx::PhenoSlot): the live members <-> a parked slot
-static void slot_swap(Ctx::PhenoSlot &p) {
-  std::swap(g_ctx.assoc_proto, p.proto);
-  std::swap(g_ctx.Uty, p.Uty);
-  std::swap(g_ctx.grid_R, p.grid_R); std::swap(g_ctx.grid_F, p.grid_F);
-  std::swap(g_ctx.cheb_R, p.cheb_R); std::swap(g_ctx.cheb_F, p.cheb_F);
-  std::swap(g_ctx.carry, p.carry);
-  std::swap(g_ctx.carry_flip, p.carry_flip);
-  std::swap(g_ctx.grid_geom, p.grid_geom); std::swap(g_ctx.cheb_geom, p.cheb_geom);
-  std::swap(g_ctx.cheb_mid, p.cheb_mid); std::swap(g_ctx.cheb_inv_half, p.cheb_inv_half);
-  std::swap(g_ctx.cheb_qmask, p.cheb_qmask);
-}
 static void multi_release() {
-  for (auto &p : g_ctx.slots) {
-    p.grid_R.release(); p.grid_F.release(); p.cheb_R.release(); p.cheb_F.release(); p.carry.release();
-  }
+  for (auto &p : g_ctx.slots) p.release();
   g_ctx.slots.clear();
   g_ctx.multi_Yt.release(); g_ctx.multi_R.release(); g_ctx.multi_T_buf.release();
   g_ctx.multi_T = 0;
@@ -40,10 +26,11 @@ static void score_release() {
 static void lmm_release() {
   g_ctx.own_U.release(); g_ctx.own_eval.release(); g_ctx.own_Uty.release(); g_ctx.own_UtW.release();
   g_ctx.UtWt.release(); g_ctx.idx_map.release(); g_ctx.X.release(); g_ctx.UtX.release();
-  g_ctx.stage_in.release(); g_ctx.stage_out.release(); g_ctx.carry.release(); g_ctx.scratch.release();
-  g_ctx.grid_R.release(); g_ctx.grid_F.release(); g_ctx.grid_T.release();
+  g_ctx.stage_in.release(); g_ctx.stage_out.release(); g_ctx.scratch.release();
+  g_ctx.single.release();
+  g_ctx.grid_T.release();
   g_ctx.table_P.release();
-  g_ctx.cheb_R.release(); g_ctx.cheb_F.release(); g_ctx.cheb_T.release(); g_ctx.cheb_slots.release();
+  g_ctx.cheb_T.release(); g_ctx.cheb_slots.release();
   g_ctx.cheb_list.release(); g_ctx.cheb_count.release(); g_ctx.cheb_D.release(); g_ctx.cheb_Ck.release();
   g_ctx.cheb_Gk.release(); g_ctx.cheb_Lk.release(); g_ctx.cheb_iv.release(); g_ctx.cheb_dends.release(); g_ctx.cheb_res.release();
   g_ctx.i8_Bt.release(); g_ctx.i8_q.release(); g_ctx.i8_qinv.release(); g_ctx.i8_cmax.release(); g_ctx.i8_A.release(); g_ctx.i8_C.release();
@@ -56,13 +43,13 @@ static void lmm_release() {
   g_ctx.mv_ready = g_ctx.mv_gxe = false;
   multi_release();
   score_release();
-  g_ctx.U = g_ctx.eval = g_ctx.Uty = nullptr;
+  g_ctx.U = g_ctx.eval = nullptr;
   g_ctx.U_even_of = nullptr;
   g_ctx.U_even.release();
   g_ctx.lmm_active = false;
 }
-// the single-phenotype entry points after a multi setup: the live slot is nobody's
-#define NEED_SINGLE(who)                                                                                                  \
+// the single-phenotype entry points after a multi or score-panel setup: the single slot holds no phenotype
+#define NEED_SINGLE(who)                                                                                                 \
   do {                                                                                                                    \
     if (g_ctx.multi_T)                                                                                                    \
       return fail(GEMMA_HIP_ESTATE, who ": the setup holds %zu phenotypes (gemma_hip_lmm_multi_batch)", g_ctx.multi_T);   \
@@ -70,6 +57,28 @@ static void lmm_release() {
       return fail(GEMMA_HIP_ESTATE, who ": the setup is a score panel of %zu phenotypes (gemma_hip_lmm_score_panel_batch)", \
                   g_ctx.score_T);                                                                                         \
   } while (0)
+
+// The host arithmetic of the univariate null model, once each: the single fit, the panel of fits and the per-SNP setups must agree
+// in every bit (tests/test_gpu_null_panel.py holds the panel to the loop of single fits).
+// lambda grid exactly as src/lmm.cpp:1964-1969
+static void fill_lam_grid(AssocArgs &a, double l_min, double l_max, size_t n_region) {
+  const double lambda_interval = log(l_max / l_min) / (double)n_region;
+  for (size_t i = 0; i <= n_region; ++i) a.lam_grid[i] = l_min * exp(lambda_interval * (double)i);
+}
+// ln B(df / 2, 1 / 2): the p-values' incomplete beta function takes it as a constant of the setup
+static double lnbeta_half(double df) { return lgamma(df / 2.0) + lgamma(0.5) - lgamma(df / 2.0 + 0.5); }
+// out8 of gemma_hip_lmm_null (= gemma_null_fit) from the device's NullOut: the four it carries, then pve, pve_se, vg, ve
+static void null_derive(const NullOut &h, double trace_G, size_t n, size_t n_cvt, double *out8) {
+  out8[0] = h.l_mle; out8[1] = h.logl_mle; out8[2] = h.l_remle; out8[3] = h.logl_remle;
+  // CalcPve, src/lmm.cpp:2197-2200 (safe_sqrt semantics of src/mathfunc.cpp:122-131)
+  double arg = -1.0 / h.dev2_remle, d1 = arg;
+  if (arg < 0.001) d1 = fabs(arg);
+  const double se = (d1 < 0.0) ? NAN : sqrt(d1);
+  out8[4] = trace_G * h.l_remle / (trace_G * h.l_remle + 1.0);
+  out8[5] = trace_G / ((trace_G * h.l_remle + 1.0) * (trace_G * h.l_remle + 1.0)) * se;
+  out8[7] = h.Pyy_remle / (double)(n - n_cvt); // ve, src/lmm.cpp:2258
+  out8[6] = out8[7] * h.l_remle;               // vg
+}
 
 static int lmm_common_setup(const gemma_lmm_cfg *cfg) {
   if (!cfg) return fail(GEMMA_HIP_EINVAL, "lmm_setup: null cfg");
@@ -92,7 +101,8 @@ static int lmm_common_setup(const gemma_lmm_cfg *cfg) {
     if (eigh_pool_idle_bytes_x() > 0 && hipMemGetInfo(&mf, &mt) == hipSuccess && eigh_pool_idle_bytes_x() > mt / 4) (void)eigh_release_x();
   }
   g_ctx.knobs.load(); // the environment switches of the batch path: once per setup
-  AssocArgs &a = g_ctx.assoc_proto;
+  Ctx::PhenoSlot &p = g_ctx.single;
+  AssocArgs &a = p.proto;
   memset(&a, 0, sizeof a);
   a.n = (int)cfg->n;
   a.a_mode = cfg->a_mode;
@@ -102,14 +112,11 @@ static int lmm_common_setup(const gemma_lmm_cfg *cfg) {
   a.l_max = cfg->l_max;
   a.l_mle_null = cfg->l_mle_null;
   a.logl_mle_H0 = cfg->logl_mle_H0;
-  const double df = (double)cfg->n - (double)cfg->n_cvt - 1.0;
-  a.lnbeta_half_df = lgamma(df / 2.0) + lgamma(0.5) - lgamma(df / 2.0 + 0.5);
-  // lambda grid exactly as src/lmm.cpp:1964-1969
-  const double lambda_interval = log(cfg->l_max / cfg->l_min) / (double)cfg->n_region;
-  for (size_t i = 0; i <= cfg->n_region; ++i) a.lam_grid[i] = cfg->l_min * exp(lambda_interval * (double)i);
-  if (g_ctx.carry.reserve(4 * 8)) return fail(GEMMA_HIP_ENOMEM, "lmm_setup: carry");
-  HIPCHK(hipMemset(g_ctx.carry.p, 0, 4 * 8));
-  g_ctx.carry_flip = 0;
+  a.lnbeta_half_df = lnbeta_half((double)cfg->n - (double)cfg->n_cvt - 1.0);
+  fill_lam_grid(a, cfg->l_min, cfg->l_max, cfg->n_region);
+  if (p.carry.reserve(4 * 8)) return fail(GEMMA_HIP_ENOMEM, "lmm_setup: carry");
+  HIPCHK(hipMemset(p.carry.p, 0, 4 * 8));
+  p.carry_flip = 0;
   g_ctx.have_map = false;
   g_ctx.ni_total = 0;
   g_ctx.i8_ready = false; // digits belong to the previous U
@@ -175,12 +182,11 @@ static bool grid_blocks(size_t c, int nq, int *nbx, int *nba) {
 // series of the covariate / phenotype pairs and of g = sum (1 - H).  Needs the fixed-lambda table (the scan reads it) and
 // intervals no longer than the decade the accuracy figures were established on; GEMMA_HIP_ASSOC_CHEB=0 switches it off
 // (every Brent / Newton evaluation then streams the row, as in round 1).
-static int make_cheb(hipStream_t s) {
-  AssocArgs &a = g_ctx.assoc_proto;
+static int make_cheb(Ctx::PhenoSlot &p, hipStream_t s) {
+  AssocArgs &a = p.proto;
   a.have_cheb = 0;
   a.cheb_T = nullptr; a.cheb_F = nullptr; a.cheb_slots = nullptr; a.cheb_res = nullptr;
-  const char *e = getenv("GEMMA_HIP_ASSOC_CHEB");
-  if (e && e[0] == '0') return GEMMA_HIP_OK;
+  if (!g_ctx.knobs.assoc_cheb) return GEMMA_HIP_OK;
   const size_t n = g_ctx.cfg.n, c = g_ctx.cfg.n_cvt;
   const int nreg = (int)g_ctx.cfg.n_region;
   const double width = log(g_ctx.cfg.l_max / g_ctx.cfg.l_min) / (double)nreg;
@@ -189,11 +195,10 @@ static int make_cheb(hipStream_t s) {
   // the fixed-lambda table) -- low-heritability traits stay on the table path; GEMMA_HIP_CHEB_LOWLAMBDA=0 leaves them to the
   // streaming evaluations as in round 2.
   int j0 = 0;
-  const char *elow = getenv("GEMMA_HIP_CHEB_LOWLAMBDA");
-  if (elow && elow[0] == '0')
+  if (!g_ctx.knobs.cheb_lowlambda)
     while (j0 < nreg && a.lam_grid[j0] < CHEB_MIN_LAMBDA * (1.0 - 1e-9)) ++j0;
   const int nint = nreg - j0;
-  g_ctx.cheb_qmask = 0;
+  p.cheb_qmask = 0;
   if (nint <= 0) return GEMMA_HIP_OK;
   GridGeom gg;
   gg.nq = CHEB_N;
@@ -205,7 +210,7 @@ static int make_cheb(hipStream_t s) {
   const size_t r_elems = (size_t)gg.nc * nb * 256;
   const size_t npairs = (c + 1) * (c + 2) / 2;
   const size_t fld = (npairs + 3) * CHEB_N; // pairs, g, log|H|, sum (1 - H)^2
-  if (g_ctx.cheb_R.reserve((size_t)nint * r_elems * 8) || g_ctx.cheb_F.reserve((size_t)nint * fld * 8) ||
+  if (p.cheb_R.reserve((size_t)nint * r_elems * 8) || p.cheb_F.reserve((size_t)nint * fld * 8) ||
       g_ctx.cheb_D.reserve(CHEB_N * CHEB_N * 8) || g_ctx.cheb_Ck.reserve(n * CHEB_N * 8) ||
       g_ctx.cheb_Gk.reserve(2 * n * CHEB_N * 8) || g_ctx.cheb_Lk.reserve(n * CHEB_N * 8) ||
       g_ctx.cheb_iv.reserve(2 * ASSOC_MAX_REGION * 8))
@@ -219,64 +224,59 @@ static int make_cheb(hipStream_t s) {
   HIPCHK(hipStreamSynchronize(s)); // D is a local
   AssocArgs k = a;
   k.eval = g_ctx.eval;
-  k.Uty = g_ctx.Uty;
+  k.Uty = p.Uty;
   k.UtWt = g_ctx.UtWt.as<double>();
   for (int q = 0; q < nint; ++q) {
     const ChebInterval iv = cheb_interval(a.lam_grid[j0 + q], a.lam_grid[j0 + q + 1], CHEB_MARGIN);
-    g_ctx.cheb_mid[q] = iv.mid;
-    g_ctx.cheb_inv_half[q] = 1.0 / iv.half;
+    p.cheb_mid[q] = iv.mid;
+    p.cheb_inv_half[q] = 1.0 / iv.half;
     ChebNodes nd;
     for (int m = 0; m < CHEB_N; ++m) nd.lam[m] = exp(cheb_node(iv, m));
     // Q form by the interval's LOWER end: an interval of a non-default grid that straddles 1e-3 (e.g. [10^-3.5, 10^-2.5]) in
     // plain S form would carry 1e-13 / lambda of relative error in dS/dt at its low end; S0 - lambda Q stays well conditioned up
     // to the interval's upper end (<= a decade above, lambda <= 1e-2).  The default grid's nodes fall on 1e-3 either way.
     const int qform = a.lam_grid[j0 + q] < CHEB_MIN_LAMBDA * (1.0 - 1e-9) ? 1 : 0;
-    if (qform) g_ctx.cheb_qmask |= 1ull << q;
+    if (qform) p.cheb_qmask |= 1ull << q;
     double *G2k = g_ctx.cheb_Gk.as<double>() + n * CHEB_N;
     hipLaunchKernelGGL(cheb_coeff_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, s, g_ctx.eval, (int)n, nd,
                        g_ctx.cheb_D.as<double>(), qform, g_ctx.cheb_Ck.as<double>(), g_ctx.cheb_Gk.as<double>(),
                        g_ctx.cheb_Lk.as<double>(), G2k);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(cheb_weights_kernel, dim3((unsigned)((r_elems + 255) / 256)), dim3(256), 0, s, k, gg, (int)c,
-                       g_ctx.cheb_Ck.as<double>(), g_ctx.cheb_R.as<double>() + (size_t)q * r_elems);
+                       g_ctx.cheb_Ck.as<double>(), p.cheb_R.as<double>() + (size_t)q * r_elems);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(cheb_fixed_kernel, dim3((unsigned)(npairs + 3)), dim3(256), 0, s, k, (int)c,
                        g_ctx.cheb_Ck.as<double>(), g_ctx.cheb_Gk.as<double>(), g_ctx.cheb_Lk.as<double>(), G2k,
-                       g_ctx.cheb_F.as<double>() + (size_t)q * fld);
+                       p.cheb_F.as<double>() + (size_t)q * fld);
     HIPCHK(hipGetLastError());
   }
   {
     std::vector<double> ivs(2 * (size_t)nint);
-    for (int q = 0; q < nint; ++q) { ivs[2 * q] = g_ctx.cheb_mid[q]; ivs[2 * q + 1] = g_ctx.cheb_inv_half[q]; }
+    for (int q = 0; q < nint; ++q) { ivs[2 * q] = p.cheb_mid[q]; ivs[2 * q + 1] = p.cheb_inv_half[q]; }
     HIPCHK(hipMemcpyAsync(g_ctx.cheb_iv.p, ivs.data(), ivs.size() * 8, hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
   }
-  g_ctx.cheb_geom = gg;
+  p.cheb_geom = gg;
   a.cheb_iv = g_ctx.cheb_iv.as<double>();
   a.cheb_logdet_off = (int)((npairs + 1) * CHEB_N);
-  a.cheb_F = g_ctx.cheb_F.as<double>();
+  a.cheb_F = p.cheb_F.as<double>();
   a.cheb_ld = (int)(nb * 16);
   a.cheb_fld = (int)fld;
   a.cheb_xa0 = gg.nbx * 16;
   a.cheb_j0 = j0;
   a.cheb_nint = nint;
-  a.cheb_qmask = g_ctx.cheb_qmask;
-  {
-    // GEMMA_HIP_ASSOC_FINAL_SERIES=0: the final likelihood at lambda-hat streams the SNP's row as in round 2
-    const char *ef = getenv("GEMMA_HIP_ASSOC_FINAL_SERIES");
-    a.cheb_final = (ef && ef[0] == '0') ? 0 : 1;
-  }
+  a.cheb_qmask = p.cheb_qmask;
+  a.cheb_final = g_ctx.knobs.assoc_final_series; // GEMMA_HIP_ASSOC_FINAL_SERIES=0: the final likelihood at lambda-hat streams the row
   a.have_cheb = 1;
   return GEMMA_HIP_OK;
 }
 
-static int make_grid(hipStream_t s) {
-  AssocArgs &a = g_ctx.assoc_proto;
+static int make_grid(Ctx::PhenoSlot &p, hipStream_t s) {
+  AssocArgs &a = p.proto;
   a.have_grid = 0;
   a.grid_T = nullptr;
   a.grid_F = nullptr;
-  const char *e = getenv("GEMMA_HIP_ASSOC_GRID");
-  if (e && e[0] == '0') return GEMMA_HIP_OK;
+  if (!g_ctx.knobs.assoc_grid) return GEMMA_HIP_OK;
   const size_t n = g_ctx.cfg.n, c = g_ctx.cfg.n_cvt;
   GridGeom gg;
   gg.nq = 1 + 2 * ((int)g_ctx.cfg.n_region + 1);
@@ -284,24 +284,24 @@ static int make_grid(hipStream_t s) {
   gg.nc = (int)((n + 15) / 16);
   const size_t nb = (size_t)(gg.nbx + gg.nba);
   const size_t r_elems = (size_t)gg.nc * nb * 256;
-  if (g_ctx.grid_R.reserve(r_elems * 8) || g_ctx.grid_F.reserve((size_t)gg.nq * GRID_FIX_LD * 8))
+  if (p.grid_R.reserve(r_elems * 8) || p.grid_F.reserve((size_t)gg.nq * GRID_FIX_LD * 8))
     return fail(GEMMA_HIP_ENOMEM, "lmm_setup: fixed-lambda table");
   AssocArgs k = a;
   k.eval = g_ctx.eval;
-  k.Uty = g_ctx.Uty;
+  k.Uty = p.Uty;
   k.UtWt = g_ctx.UtWt.as<double>();
   hipLaunchKernelGGL(grid_weights_kernel, dim3((unsigned)((r_elems + 255) / 256)), dim3(256), 0, s, k, gg, (int)c,
-                     g_ctx.grid_R.as<double>());
+                     p.grid_R.as<double>());
   HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(grid_fixed_kernel, dim3((unsigned)gg.nq), dim3(256), 0, s, k, (int)c, g_ctx.grid_F.as<double>());
+  hipLaunchKernelGGL(grid_fixed_kernel, dim3((unsigned)gg.nq), dim3(256), 0, s, k, (int)c, p.grid_F.as<double>());
   HIPCHK(hipGetLastError());
-  g_ctx.grid_geom = gg;
-  a.grid_F = g_ctx.grid_F.as<double>();
+  p.grid_geom = gg;
+  a.grid_F = p.grid_F.as<double>();
   a.grid_ld = (int)(nb * 16);
   a.grid_nq = gg.nq;
   a.grid_xa0 = gg.nbx * 16;
   a.have_grid = 1;
-  return make_cheb(s);
+  return make_cheb(p, s);
 }
 
 // table_v2_kernel + table_reduce_kernel (lmm_grid.hip.h): T = [X.X | X] * R with RG * 16 rows per wave and the K range cut
@@ -355,12 +355,12 @@ static int launch_table_v2(const GridGeom &gg, const double *UtX, size_t l, size
 }
 
 // the per-batch part: T = [X.X | X] * R for the l SNP rows of UtX
-static int launch_grid_table(const double *UtX, size_t l, size_t ld, hipStream_t s) {
-  const GridGeom &gg = g_ctx.grid_geom;
+static int launch_grid_table(Ctx::PhenoSlot &p, const double *UtX, size_t l, size_t ld, hipStream_t s) {
+  const GridGeom &gg = p.grid_geom;
   const size_t nb = (size_t)(gg.nbx + gg.nba);
   if (g_ctx.grid_T.reserve(l * nb * 16 * 8)) return fail(GEMMA_HIP_ENOMEM, "lmm_assoc: fixed-lambda table");
   const unsigned grid = (unsigned)((l + 15) / 16);
-  const double *R = g_ctx.grid_R.as<double>();
+  const double *R = p.grid_R.as<double>();
   double *T = g_ctx.grid_T.as<double>();
   const int n = (int)g_ctx.cfg.n;
   if (table_v2_enabled()) return launch_table_v2(gg, UtX, l, ld, R, T, nullptr, 0, s);
@@ -377,8 +377,8 @@ static int launch_grid_table(const double *UtX, size_t l, size_t ld, hipStream_t
 
 // the per-batch part of the bracket-interval series: which (SNP, interval) pairs exist (scan over the fixed-lambda table),
 // then the table product for exactly those rows.  `a` must already carry grid_T; fills a.cheb_T / a.cheb_slots.
-static int launch_cheb_tables(AssocArgs &a, const double *UtX, size_t l, size_t ld, hipStream_t s) {
-  const GridGeom &gg = g_ctx.cheb_geom;
+static int launch_cheb_tables(Ctx::PhenoSlot &p, AssocArgs &a, const double *UtX, size_t l, size_t ld, hipStream_t s) {
+  const GridGeom &gg = p.cheb_geom;
   const size_t nb = (size_t)(gg.nbx + gg.nba), nint = (size_t)a.cheb_nint;
   if (g_ctx.cheb_T.reserve(nint * l * nb * 16 * 8) || g_ctx.cheb_slots.reserve(l * nint * sizeof(int)) ||
       g_ctx.cheb_list.reserve(nint * l * sizeof(int)) || g_ctx.cheb_count.reserve(ASSOC_MAX_REGION * sizeof(int)) ||
@@ -408,7 +408,7 @@ static int launch_cheb_tables(AssocArgs &a, const double *UtX, size_t l, size_t 
   tg.cap = (long)l;
   tg.rp_stride = (long)gg.nc * (long)nb * 256;
   const dim3 grid((unsigned)((l + 15) / 16), (unsigned)nint);
-  const double *R = g_ctx.cheb_R.as<double>();
+  const double *R = p.cheb_R.as<double>();
   double *T = g_ctx.cheb_T.as<double>();
   const int n = (int)g_ctx.cfg.n;
   if (table_v2_enabled()) {
@@ -426,11 +426,11 @@ static int launch_cheb_tables(AssocArgs &a, const double *UtX, size_t l, size_t 
   ChebSearchArgs sa;
   sa.count = sc.count;
   sa.list = sc.list;
-  sa.qmask = g_ctx.cheb_qmask;
+  sa.qmask = p.cheb_qmask;
   sa.dends = sc.dends;
   sa.res = g_ctx.cheb_res.as<ChebResult>();
-  memcpy(sa.mid, g_ctx.cheb_mid, sizeof sa.mid);
-  memcpy(sa.inv_half, g_ctx.cheb_inv_half, sizeof sa.inv_half);
+  memcpy(sa.mid, p.cheb_mid, sizeof sa.mid);
+  memcpy(sa.inv_half, p.cheb_inv_half, sizeof sa.inv_half);
   const dim3 qgrid((unsigned)((l + 63) / 64), (unsigned)nint, 2);
   switch (c) {
   case 1: hipLaunchKernelGGL(cheb_search_kernel<1>, qgrid, dim3(64), 0, s, a, sa); break;
@@ -444,8 +444,8 @@ static int launch_cheb_tables(AssocArgs &a, const double *UtX, size_t l, size_t 
   return GEMMA_HIP_OK;
 }
 
-// UtW (n x c row-major) -> UtWt (c x n)
-static int make_utwt(const double *UtW_d, hipStream_t s) {
+// UtW (n x c row-major) -> UtWt (c x n), the log-determinant ends into p's proto, then p's tables
+static int make_utwt(Ctx::PhenoSlot &p, const double *UtW_d, hipStream_t s) {
   const size_t n = g_ctx.cfg.n, c = g_ctx.cfg.n_cvt;
   if (g_ctx.UtWt.reserve(c * n * 8)) return fail(GEMMA_HIP_ENOMEM, "lmm_setup: UtWt");
   dim3 grid((unsigned)((c + 31) / 32), (unsigned)((n + 31) / 32));
@@ -460,10 +460,10 @@ static int make_utwt(const double *UtW_d, hipStream_t s) {
   double ends[2];
   HIPCHK(hipMemcpyAsync(ends, g_ctx.scratch.p, 16, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  g_ctx.assoc_proto.logdet_lmin = ends[0];
-  g_ctx.assoc_proto.logdet_lmax = ends[1];
-  g_ctx.assoc_proto.have_logdet_ends = 1;
-  return make_grid(s);
+  p.proto.logdet_lmin = ends[0];
+  p.proto.logdet_lmax = ends[1];
+  p.proto.have_logdet_ends = 1;
+  return make_grid(p, s);
 }
 
 // the three single-phenotype setups after their argument checks; the host forms return with the setup's work done
@@ -472,8 +472,8 @@ static int single_setup(const char *who, SetupSrc src, const gemma_lmm_cfg *cfg,
   const double *UtW_d, *Uty_d;
   int rc = lmm_bind(who, src, cfg, U, eval, UtW, Uty, 1, &UtW_d, &Uty_d);
   if (rc) return rc;
-  g_ctx.Uty = Uty_d;
-  if ((rc = make_utwt(UtW_d, s))) return rc;
+  g_ctx.single.Uty = Uty_d;
+  if ((rc = make_utwt(g_ctx.single, UtW_d, s))) return rc;
   if (src != SetupSrc::Device) HIPCHK(hipDeviceSynchronize());
   g_ctx.lmm_active = true;
   return GEMMA_HIP_OK;
@@ -526,15 +526,16 @@ static bool assoc_takes_tables(const AssocArgs &a, const double *UtX, size_t ld)
   return a.have_grid && sel <= 4 && (ld & 1) == 0 && (reinterpret_cast<uintptr_t>(UtX) & 15) == 0 &&
          a.a_mode != 3; // mode 3 (score only) never searches lambda
 }
-// shared_T: the live slot's fixed-lambda table of these rows, already computed (launch_table_multi); nullptr: computed here
-static int launch_assoc(const double *UtX, size_t l, size_t ld, gemma_sumstat *out_d, hipStream_t s,
+// The per-SNP stage of phenotype p.  shared_T: p's fixed-lambda table of these rows, already computed (launch_table_multi);
+// nullptr: computed here
+static int launch_assoc(Ctx::PhenoSlot &p, const double *UtX, size_t l, size_t ld, gemma_sumstat *out_d, hipStream_t s,
                         const double *shared_T = nullptr) {
-  AssocArgs a = g_ctx.assoc_proto;
+  AssocArgs a = p.proto;
   a.UtX = UtX;
   a.ld = (long)ld;
   a.l = (long)l;
   a.eval = g_ctx.eval;
-  a.Uty = g_ctx.Uty;
+  a.Uty = p.Uty;
   a.UtWt = g_ctx.UtWt.as<double>();
   a.out = reinterpret_cast<SumStat *>(out_d);
   const unsigned grid = (unsigned)((l + 3) / 4);
@@ -547,14 +548,14 @@ static int launch_assoc(const double *UtX, size_t l, size_t ld, gemma_sumstat *o
       // The tables are an accelerator, not a requirement: when their buffers do not fit (the K-slice partial sums are
       // planes x slices x l x 80 doubles -- 1.6 GB at l = n = 20000, c = 1) the batch falls back to the streaming evaluations
       // (the round-1 path, same statistics) instead of failing.
-      int rc = shared_T ? GEMMA_HIP_OK : launch_grid_table(UtX, l, ld, s);
+      int rc = shared_T ? GEMMA_HIP_OK : launch_grid_table(p, UtX, l, ld, s);
       if (rc && rc != GEMMA_HIP_ENOMEM) return rc;
       a.grid_T = rc ? nullptr : (shared_T ? shared_T : g_ctx.grid_T.as<double>());
       a.cheb_T = nullptr;
       a.cheb_slots = nullptr;
       a.cheb_res = nullptr;
       if (!rc && a.have_cheb) {
-        rc = launch_cheb_tables(a, UtX, l, ld, s);
+        rc = launch_cheb_tables(p, a, UtX, l, ld, s);
         if (rc && rc != GEMMA_HIP_ENOMEM) return rc;
         if (rc) { a.cheb_T = nullptr; a.cheb_slots = nullptr; a.cheb_res = nullptr; }
       }
@@ -588,12 +589,12 @@ static int launch_assoc(const double *UtX, size_t l, size_t ld, gemma_sumstat *o
     }
     HIPCHK(hipGetLastError());
     if (g_ctx.cfg.plink_nan_rule && g_ctx.cfg.a_mode == 1) {
-      double *cin = g_ctx.carry.as<double>() + 2 * g_ctx.carry_flip;
-      double *cout = g_ctx.carry.as<double>() + 2 * (1 - g_ctx.carry_flip);
+      double *cin = p.carry.as<double>() + 2 * p.carry_flip;
+      double *cout = p.carry.as<double>() + 2 * (1 - p.carry_flip);
       hipLaunchKernelGGL(plink_carry_kernel, dim3((unsigned)((l + 255) / 256)), dim3(256), 0, s,
                          reinterpret_cast<SumStatRaw *>(out_d), (long)l, cin, cout);
       HIPCHK(hipGetLastError());
-      g_ctx.carry_flip = 1 - g_ctx.carry_flip;
+      p.carry_flip = 1 - p.carry_flip;
     }
   }
   return GEMMA_HIP_OK;
@@ -610,7 +611,7 @@ extern "C" int gemma_hip_lmm_assoc_d(const double *UtX_d, size_t l, size_t ld_ut
     int rcf = xp_flush_fwd(S(stream));
     if (rcf) return rcf;
   }
-  return launch_assoc(UtX_d, l, ld_utx, out_d, S(stream));
+  return launch_assoc(g_ctx.single, UtX_d, l, ld_utx, out_d, S(stream));
 }
 
 // GEMMA_HIP_UTX_I8: 1 (default) = hard-call batches (PLINK 2-bit; fp64 input whose rows hold only 0/1/2 and one

@@ -73,18 +73,15 @@ extern "C" int gemma_hip_mqs_S(size_t n, size_t n_vc, const double *A, const dou
   if (rc) return rc;
   const bool same = (A == K);
   const size_t ldd = (n + 1) & ~(size_t)1, per = n * ldd;
-  DevBuf d;
+  ScopedBuf d;
   if (d.reserve((same ? 1 : 2) * n_vc * per * 8)) return fail(GEMMA_HIP_ENOMEM, "mqs_S: cannot allocate %zu bytes", (same ? 1 : 2) * n_vc * per * 8);
   double *Kd = d.as<double>(), *Ad = same ? Kd : Kd + n_vc * per;
-  hipError_t e = hipSuccess;
-  for (size_t i = 0; i < n_vc && e == hipSuccess; ++i) {
-    e = hipMemcpy2D(Kd + i * per, ldd * 8, K + i * n * ld, ld * 8, n * 8, n, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !same) e = hipMemcpy2D(Ad + i * per, ldd * 8, A + i * n * ld, ld * 8, n * 8, n, hipMemcpyHostToDevice);
+  for (size_t i = 0; i < n_vc; ++i) {
+    HIPCHK(hipMemcpy2D(Kd + i * per, ldd * 8, K + i * n * ld, ld * 8, n * 8, n, hipMemcpyHostToDevice));
+    if (!same) HIPCHK(hipMemcpy2D(Ad + i * per, ldd * 8, A + i * n * ld, ld * 8, n * 8, n, hipMemcpyHostToDevice));
   }
   std::string msg;
-  if (e == hipSuccess) rc = mqs_S_x((long)n, (int)n_vc, Ad, Kd, (long)ldd, (int)n_cvt, S, nullptr, msg);
-  d.release();
-  if (e != hipSuccess) return fail(GEMMA_HIP_ERUNTIME, "mqs_S: %s", hipGetErrorString(e));
+  rc = mqs_S_x((long)n, (int)n_vc, Ad, Kd, (long)ldd, (int)n_cvt, S, nullptr, msg);
   return ret(rc, msg);
 }
 

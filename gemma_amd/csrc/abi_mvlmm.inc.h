@@ -62,18 +62,9 @@ static int mv_null_body(size_t n, size_t n_cvt, size_t d, const double *eval, co
   gemma_mvlmm_opt o;
   mv_default_opt(o, opt);
   const size_t c = n_cvt;
-  DevBuf d_eval, d_Wt, d_Yt, d_Ypair, d_out;
-  struct Rel {
-    DevBuf *b[5];
-    ~Rel() { for (DevBuf *x : b) x->release(); }
-  } rel{{&d_eval, &d_Wt, &d_Yt, &d_Ypair, &d_out}};
+  ScopedBuf d_eval, d_Wt, d_Yt, d_Ypair, d_out, d_scr, d_se;
   constexpr size_t RES_MAX = 2 * (2 * MV_DMAX * MV_DMAX + MV_BMAX + 1);
   constexpr size_t SE_MAX = 2 * (size_t)mv_null_se_doubles(MV_DMAX, MV_CMAX);
-  DevBuf d_scr, d_se;
-  struct Rel2 {
-    DevBuf *b[2];
-    ~Rel2() { for (DevBuf *x : b) x->release(); }
-  } rel2{{&d_scr, &d_se}};
   if (d_eval.reserve(n * 8) || d_out.reserve(RES_MAX * 8) || (se && d_se.reserve(SE_MAX * 8)))
     return fail(GEMMA_HIP_ENOMEM, "mvlmm_null: buffers");
   HIPCHK(hipMemcpy(d_eval.p, eval, n * 8, hipMemcpyHostToDevice));
@@ -233,54 +224,24 @@ static int mv_launch(MvArgs &a, size_t d, size_t rows, hipStream_t s) {
   return GEMMA_HIP_OK;
 }
 
-// MVLMM::AnalyzeBimbamGXE / AnalyzePlinkGXE (src/mvlmm.cpp:3970-4414 / :4416-4870): x, x o env and the allele flip as in the
-// univariate GXE path (ingest_gxe_kernel), both rotated by fp64 GEMMs
+// MVLMM::AnalyzeBimbamGXE / AnalyzePlinkGXE (src/mvlmm.cpp:3970-4414 / :4416-4870): x, x o env and the allele flip are the
+// univariate GXE path's (gxe_rotate_block, abi_gxe_lm.inc.h)
 static int mvlmm_gxe_batch_d(int kind, const void *geno, size_t l, size_t ld, double *out_d, hipStream_t s) {
   if (kind == GEMMA_GENO_F64_IDV_MAJOR) return fail(GEMMA_HIP_EINVAL, "mvlmm_batch (gxe): SNP-major input only");
-  const size_t n = g_ctx.cfg.n, c = g_ctx.cfg.n_cvt;
-  const size_t ldx = (n + 1) & ~(size_t)1;
-  if (int rcf = xp_flush(s)) return rcf; // blocks of the two-block pipeline still in flight share these buffers
-  g_ctx.last_UtX = nullptr;
-  if (g_ctx.X.reserve(l * ldx * 8) || g_ctx.UtX.reserve(l * ldx * 8) || g_ctx.gxe_Z.reserve(l * ldx * 8) ||
-      g_ctx.gxe_UtZ.reserve(l * ldx * 8) || g_ctx.gxe_flip.reserve(l * sizeof(int)))
-    return fail(GEMMA_HIP_ENOMEM, "mvlmm_batch (gxe): cannot allocate 4 x %zu bytes", l * ldx * 8);
-  double *X = g_ctx.X.as<double>(), *UtX = g_ctx.UtX.as<double>();
-  double *Z = g_ctx.gxe_Z.as<double>(), *UtZ = g_ctx.gxe_UtZ.as<double>();
-  {
-    ProfScope ps(GEMMA_STAGE_INGEST, s);
-    IngestGxeArgs ia;
-    ia.src = geno; ia.ld = (long)ld; ia.l = (long)l;
-    ia.idx_map = g_ctx.have_map ? g_ctx.idx_map.as<int>() : nullptr;
-    ia.n = (int)n; ia.env = g_ctx.gxe_env.as<double>(); ia.X = X; ia.Z = Z; ia.ldo = (long)ldx;
-    ia.flip = g_ctx.gxe_flip.as<int>();
-    const unsigned grid = (unsigned)((l + 3) / 4);
-    if (kind == GEMMA_GENO_PLINK_2BIT)
-      hipLaunchKernelGGL(ingest_gxe_kernel<true>, dim3(grid), dim3(256), 0, s, ia);
-    else
-      hipLaunchKernelGGL(ingest_gxe_kernel<false>, dim3(grid), dim3(256), 0, s, ia);
-    HIPCHK(hipGetLastError());
-  }
-  {
-    ProfScope ps(GEMMA_STAGE_UTX_GEMM, s);
-    const double *Ug;
-    long ldu;
-    int rcu = gemm_U(&Ug, &ldu, s);
-    if (rcu) return rcu;
-    HIPCHK(launch_dgemm('N', 'N', (long)l, (long)n, (long)n, 1.0, X, (long)ldx, Ug, ldu, 0.0, UtX, (long)ldx, false, false, s));
-    HIPCHK(launch_dgemm('N', 'N', (long)l, (long)n, (long)n, 1.0, Z, (long)ldx, Ug, ldu, 0.0, UtZ, (long)ldx, false, false, s));
-  }
+  GxeBlock b;
+  if (int rc = gxe_rotate_block("mvlmm_batch (gxe)", kind, geno, l, ld, s, b)) return rc;
   MvArgs a = g_ctx.mv_proto;
-  a.UtX = UtX;
-  a.UtX2 = UtZ;
-  a.flip = g_ctx.gxe_flip.as<int>();
-  a.ld = (long)ldx;
+  a.UtX = b.UtX;
+  a.UtX2 = b.UtZ;
+  a.flip = b.flip;
+  a.ld = (long)b.ldx;
   a.l = (long)l;
   a.eval = g_ctx.eval;
   a.Wt = g_ctx.gxe_UtWt.as<double>(); // W then U^T env
   a.Yt = g_ctx.mv_Yt.as<double>();
   a.out = out_d;
   ProfScope ps(GEMMA_STAGE_ASSOC, s);
-  return mv_launch(a, g_ctx.mv_d, c + 3, s);
+  return mv_launch(a, g_ctx.mv_d, g_ctx.cfg.n_cvt + 3, s);
 }
 
 extern "C" int gemma_hip_mvlmm_batch_d(int kind, const void *geno, size_t l, size_t ld, double *out_d, void *stream) {

@@ -85,7 +85,7 @@ static int mvpairs_run(size_t n, size_t c, size_t T, const double *eval_d, const
   const size_t m = list.size() / 2;
   gemma_mvlmm_opt o;
   mv_default_opt(o, opt);
-  DevBuf dWt, dYt, dStart, dPairs, dYp, dRaw, dFit, dB;
+  ScopedBuf dWt, dYt, dStart, dPairs, dYp, dRaw, dFit, dB;
   auto body = [&]() -> int {
     int r = null_panel_wt(n, c, UtW_d, dWt, s);
     if (r) return r;
@@ -143,8 +143,7 @@ static int mvpairs_run(size_t n, size_t c, size_t T, const double *eval_d, const
     return GEMMA_HIP_OK;
   };
   int rc = body();
-  if (rc) (void)hipStreamSynchronize(s);
-  dWt.release(); dYt.release(); dStart.release(); dPairs.release(); dYp.release(); dRaw.release(); dFit.release(); dB.release();
+  if (rc) (void)hipStreamSynchronize(s); // before the buffers go
   return rc;
 }
 
@@ -174,17 +173,12 @@ extern "C" int gemma_hip_mvlmm_null_pairs(size_t n, size_t n_cvt, size_t T, cons
   if (rc) return rc;
   std::vector<int> list;
   if ((rc = mvpairs_list(T, pairs, m, list))) return rc;
-  DevBuf dE, dW, dY;
-  if (dE.reserve(n * 8) || dW.reserve(n * n_cvt * 8) || dY.reserve(n * T * 8)) {
-    dE.release(); dW.release(); dY.release();
+  ScopedBuf dE, dW, dY;
+  if (dE.reserve(n * 8) || dW.reserve(n * n_cvt * 8) || dY.reserve(n * T * 8))
     return fail(GEMMA_HIP_ENOMEM, "mvlmm_null_pairs: eval, U^T W and U^T Y (%zu bytes)", n * 8 + n * n_cvt * 8 + n * T * 8);
-  }
-  hipError_t e = hipMemcpy(dE.p, eval, n * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dW.p, UtW, n * n_cvt * 8, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(dY.p, UtY, n * T * 8, hipMemcpyHostToDevice);
-  rc = e != hipSuccess ? fail(GEMMA_HIP_ERUNTIME, "mvlmm_null_pairs: %s", hipGetErrorString(e))
-                       : mvpairs_run(n, n_cvt, T, dE.as<double>(), dW.as<double>(), dY.as<double>(), list, l_min, l_max, n_region, opt,
-                                     fit, B, VB, true, 0);
-  dE.release(); dW.release(); dY.release();
-  return rc;
+  HIPCHK(hipMemcpy(dE.p, eval, n * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dW.p, UtW, n * n_cvt * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dY.p, UtY, n * T * 8, hipMemcpyHostToDevice));
+  return mvpairs_run(n, n_cvt, T, dE.as<double>(), dW.as<double>(), dY.as<double>(), list, l_min, l_max, n_region, opt, fit, B, VB,
+                     true, 0);
 }

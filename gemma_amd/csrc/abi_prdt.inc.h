@@ -299,29 +299,28 @@ extern "C" int gemma_hip_prdt_kin_mv(size_t ni, size_t d, const double *G_full, 
   std::string msg;
   double *Gd = nullptr;
   if ((rc = prdt_mv_stage_G_x(G_full, (long)ni, (long)ni, false, &Gd, nullptr, msg))) return ret(rc, msg);
-  ScopedBuf sub, U, small; // small: [eval n | WY n x (c + d) | UtWY n x (c + d)]
   const size_t k = c + d;
-  if (sub.reserve(n * n * 8) || U.reserve(n * n * 8) || small.reserve((n + 2 * n * k) * 8))
-    return fail(GEMMA_HIP_ENOMEM, "prdt_kin_mv: cannot allocate 2 x %zu bytes", n * n * 8);
-  if ((rc = prdt_mv_sub_x(Gd, (long)ni, pos.data(), (long)n, sub.as<double>(), nullptr, msg))) return ret(rc, msg);
-  double *ev_d = small.as<double>(), *WY_d = ev_d + n, *UtWY_d = WY_d + n * k;
-  double trace_G = 0.0;
-  if ((rc = gemma_hip_center_d(sub.as<double>(), n, nullptr)) ||
-      (rc = gemma_hip_eigh_d(sub.as<double>(), n, U.as<double>(), ev_d, &trace_G, nullptr)))
-    return rc;
-  // U'W and U'Y in one product (:1785-1786)
   std::vector<double> WY(n * k), UtWY(n * k), ev(n), UtW(n * c), UtY(n * d);
-  for (size_t a = 0; a < n; ++a) {
-    for (size_t j = 0; j < c; ++j) WY[a * k + j] = W_full[(size_t)pos[a] * c + j];
-    for (size_t j = 0; j < d; ++j) WY[a * k + c + j] = Y_full[(size_t)pos[a] * d + j];
+  { // the device buffers of the decomposition go at the end of this block, before the null fit asks for its own
+    ScopedBuf sub, U, small; // small: [eval n | WY n x (c + d) | UtWY n x (c + d)]
+    if (sub.reserve(n * n * 8) || U.reserve(n * n * 8) || small.reserve((n + 2 * n * k) * 8))
+      return fail(GEMMA_HIP_ENOMEM, "prdt_kin_mv: cannot allocate 2 x %zu bytes", n * n * 8);
+    if ((rc = prdt_mv_sub_x(Gd, (long)ni, pos.data(), (long)n, sub.as<double>(), nullptr, msg))) return ret(rc, msg);
+    double *ev_d = small.as<double>(), *WY_d = ev_d + n, *UtWY_d = WY_d + n * k;
+    double trace_G = 0.0;
+    if ((rc = gemma_hip_center_d(sub.as<double>(), n, nullptr)) ||
+        (rc = gemma_hip_eigh_d(sub.as<double>(), n, U.as<double>(), ev_d, &trace_G, nullptr)))
+      return rc;
+    // U'W and U'Y in one product (:1785-1786)
+    for (size_t a = 0; a < n; ++a) {
+      for (size_t j = 0; j < c; ++j) WY[a * k + j] = W_full[(size_t)pos[a] * c + j];
+      for (size_t j = 0; j < d; ++j) WY[a * k + c + j] = Y_full[(size_t)pos[a] * d + j];
+    }
+    HIPCHK(hipMemcpy(WY_d, WY.data(), n * k * 8, hipMemcpyHostToDevice));
+    if ((rc = gemma_hip_dgemm_d('T', 'N', n, k, n, 1.0, U.as<double>(), n, WY_d, k, 0.0, UtWY_d, k, nullptr))) return rc;
+    HIPCHK(hipMemcpy(UtWY.data(), UtWY_d, n * k * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ev.data(), ev_d, n * 8, hipMemcpyDeviceToHost));
   }
-  HIPCHK(hipMemcpy(WY_d, WY.data(), n * k * 8, hipMemcpyHostToDevice));
-  if ((rc = gemma_hip_dgemm_d('T', 'N', n, k, n, 1.0, U.as<double>(), n, WY_d, k, 0.0, UtWY_d, k, nullptr))) return rc;
-  HIPCHK(hipMemcpy(UtWY.data(), UtWY_d, n * k * 8, hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(ev.data(), ev_d, n * 8, hipMemcpyDeviceToHost));
-  sub.release();
-  U.release();
-  small.release();
   for (size_t a = 0; a < n; ++a) {
     for (size_t j = 0; j < c; ++j) UtW[a * c + j] = UtWY[a * k + j];
     for (size_t j = 0; j < d; ++j) UtY[a * d + j] = UtWY[a * k + c + j];

@@ -13,18 +13,13 @@ extern "C" int gemma_hip_spd_inverse(double *A, size_t n, size_t lda, double *lo
   NEED_INIT();
   if (n == 0 || lda < n || !A) return fail(GEMMA_HIP_EINVAL, "spd_inverse: n = %zu, lda = %zu", n, lda);
   const size_t ld = (n + 1) & ~(size_t)1;
-  DevBuf d;
+  ScopedBuf d;
   if (d.reserve(n * ld * 8)) return fail(GEMMA_HIP_ENOMEM, "spd_inverse: cannot allocate %zu bytes", n * ld * 8);
-  int rc = GEMMA_HIP_OK;
   std::string msg;
-  hipError_t e = hipMemcpy2D(d.p, ld * 8, A, lda * 8, n * 8, n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    rc = spd_inverse_x(d.as<double>(), (long)n, (long)ld, logdet, bad_pivot, nullptr, msg);
-    if (rc == GEMMA_HIP_OK) e = hipMemcpy2D(A, lda * 8, d.p, ld * 8, n * 8, n, hipMemcpyDeviceToHost);
-  }
-  d.release();
-  if (e != hipSuccess) return fail(GEMMA_HIP_ERUNTIME, "spd_inverse: %s", hipGetErrorString(e));
-  return ret(rc, msg);
+  HIPCHK(hipMemcpy2D(d.p, ld * 8, A, lda * 8, n * 8, n, hipMemcpyHostToDevice));
+  if (int rc = spd_inverse_x(d.as<double>(), (long)n, (long)ld, logdet, bad_pivot, nullptr, msg)) return ret(rc, msg);
+  HIPCHK(hipMemcpy2D(A, lda * 8, d.p, ld * 8, n * 8, n, hipMemcpyDeviceToHost));
+  return GEMMA_HIP_OK;
 }
 
 static bool g_vc_ready = false;

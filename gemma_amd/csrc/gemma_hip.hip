@@ -70,9 +70,22 @@ struct Knobs {
   int pipe_cus = 64;       // GEMMA_HIP_PIPE_CUS: CUs of the post partition of gemma_hip_lmm_batch_pipe_d (0: two plain streams, no masks)
   int kin_i8 = 1, kin_upper = 1, kin_lists = 1, kin_lists_oom = 0; // GEMMA_HIP_KIN_I8 / _UPPER / _LISTS / _LISTS_OOM
   long long kin_list_cap = 0;                                       // GEMMA_HIP_KIN_LIST_CAP (0: by block size)
+  // the tables of the per-SNP stage (make_grid / make_cheb): the setup that builds them has loaded these in lmm_common_setup
+  int assoc_grid = 1;         // GEMMA_HIP_ASSOC_GRID: 0 = no fixed-lambda table
+  int assoc_cheb = 1;         // GEMMA_HIP_ASSOC_CHEB: 0 = no bracket-interval series
+  int cheb_lowlambda = 1;     // GEMMA_HIP_CHEB_LOWLAMBDA: 0 = the intervals below lambda = 1e-3 stream (round 2)
+  int assoc_final_series = 1; // GEMMA_HIP_ASSOC_FINAL_SERIES: 0 = the final likelihood at lambda-hat streams the SNP's row (round 2)
   static int geti(const char *name, int dflt) {
     const char *e = getenv(name);
     return (e && *e) ? atoi(e) : dflt;
+  }
+  static int on_unless_0(const char *name) { // by the first character, as every switch of this kind always was
+    const char *e = getenv(name);
+    return (e && e[0] == '0') ? 0 : 1;
+  }
+  static int off_unless_1(const char *name) {
+    const char *e = getenv(name);
+    return (e && e[0] == '1') ? 1 : 0;
   }
   void load() {
     i8.utx_i8 = geti("GEMMA_HIP_UTX_I8", 1);
@@ -80,8 +93,7 @@ struct Knobs {
     i8_digits = (dg == 6 || dg == 7) ? dg : 0;
     const char *es = getenv("GEMMA_HIP_I8_SPARSE");
     i8.sparse = (es && es[0] >= '0' && es[0] <= '2') ? es[0] - '0' : 2;
-    const char *ef = getenv("GEMMA_HIP_I8_FUSE");
-    i8.fuse = (ef && ef[0] == '0') ? 0 : 1;
+    i8.fuse = on_unless_0("GEMMA_HIP_I8_FUSE");
     i8.gm = geti("GEMMA_HIP_I8_GM", 0);
     i8.raster = geti("GEMMA_HIP_I8_RASTER", S2_DEFAULT_RASTER);
     i8.rows = geti("GEMMA_HIP_I8_ROWS", 16) == 32 ? 32 : 16;
@@ -90,38 +102,31 @@ struct Knobs {
     const char *efm = getenv("GEMMA_HIP_I8_FORM");
     i8.mdrop = (efm && strcmp(efm, "7g6m") == 0) ? 1 : 0;
     if (i8.mdrop) i8_digits = 7;
-    const char *ecp = getenv("GEMMA_HIP_I8_COMPLETE");
-    i8.complete = (ecp && ecp[0] == '0') ? 0 : 1;
-    const char *eep = getenv("GEMMA_HIP_I8_EPILOGUE");
-    i8.epilogue = (eep && eep[0] == '0') ? 0 : 1;
+    i8.complete = on_unless_0("GEMMA_HIP_I8_COMPLETE");
+    i8.epilogue = on_unless_0("GEMMA_HIP_I8_EPILOGUE");
     i8.epi_depth = geti("GEMMA_HIP_I8_EPI_DEPTH", 4) <= 1 ? 1 : 4;
-    const char *edr = getenv("GEMMA_HIP_I8_DIRECT");
-    i8.direct = (edr && edr[0] == '0') ? 0 : 1;
-    const char *ed = getenv("GEMMA_HIP_UTX_DOSAGE_I8");
-    dosage_i8 = (ed && ed[0] == '0') ? 0 : 1;
+    i8.direct = on_unless_0("GEMMA_HIP_I8_DIRECT");
+    dosage_i8 = on_unless_0("GEMMA_HIP_UTX_DOSAGE_I8");
     dosage_rows = geti("GEMMA_HIP_DOSAGE_ROWS", 16) == 32 ? 32 : 16;
-    const char *eo = getenv("GEMMA_HIP_OVERLAP");
-    i8.overlap = (eo && eo[0] == '1') ? 1 : 0;
+    i8.overlap = off_unless_1("GEMMA_HIP_OVERLAP");
     i8.chunks = geti("GEMMA_HIP_OVERLAP_CHUNKS", 4);
-    const char *et = getenv("GEMMA_HIP_TABLE_V2");
-    table_v2 = (et && et[0] == '0') ? 0 : 1;
-    const char *ep = getenv("GEMMA_HIP_TABLE_PF");
-    table_pf = (ep && ep[0] == '1') ? 1 : 0;
-    const char *em = getenv("GEMMA_HIP_MULTI_TABLE");
-    multi_table = (em && em[0] == '0') ? 0 : 1;
-    const char *eg = getenv("GEMMA_HIP_FORCE_GENERIC");
-    force_generic = (eg && eg[0] == '1') ? 1 : 0;
+    table_v2 = on_unless_0("GEMMA_HIP_TABLE_V2");
+    table_pf = off_unless_1("GEMMA_HIP_TABLE_PF");
+    multi_table = on_unless_0("GEMMA_HIP_MULTI_TABLE");
+    force_generic = off_unless_1("GEMMA_HIP_FORCE_GENERIC");
     assoc_variant = geti("GEMMA_HIP_ASSOC_VARIANT", 44);
-    const char *er = getenv("GEMMA_HIP_MVLMM_RT");
-    mvlmm_rt = (er && er[0] == '1') ? 1 : 0;
+    mvlmm_rt = off_unless_1("GEMMA_HIP_MVLMM_RT");
     pipe_cus = geti("GEMMA_HIP_PIPE_CUS", 64);
-    const char *k1 = getenv("GEMMA_HIP_KIN_I8"), *k2 = getenv("GEMMA_HIP_KIN_UPPER"), *k3 = getenv("GEMMA_HIP_KIN_LISTS");
-    const char *k4 = getenv("GEMMA_HIP_KIN_LISTS_OOM"), *k5 = getenv("GEMMA_HIP_KIN_LIST_CAP");
-    kin_i8 = (k1 && k1[0] == '0') ? 0 : 1;
-    kin_upper = (k2 && k2[0] == '0') ? 0 : 1;
-    kin_lists = (k3 && k3[0] == '0') ? 0 : 1;
-    kin_lists_oom = (k4 && k4[0] == '1') ? 1 : 0;
-    kin_list_cap = (k5 && *k5) ? atoll(k5) : 0;
+    kin_i8 = on_unless_0("GEMMA_HIP_KIN_I8");
+    kin_upper = on_unless_0("GEMMA_HIP_KIN_UPPER");
+    kin_lists = on_unless_0("GEMMA_HIP_KIN_LISTS");
+    kin_lists_oom = off_unless_1("GEMMA_HIP_KIN_LISTS_OOM");
+    const char *kc = getenv("GEMMA_HIP_KIN_LIST_CAP");
+    kin_list_cap = (kc && *kc) ? atoll(kc) : 0;
+    assoc_grid = on_unless_0("GEMMA_HIP_ASSOC_GRID");
+    assoc_cheb = on_unless_0("GEMMA_HIP_ASSOC_CHEB");
+    cheb_lowlambda = on_unless_0("GEMMA_HIP_CHEB_LOWLAMBDA");
+    assoc_final_series = on_unless_0("GEMMA_HIP_ASSOC_FINAL_SERIES");
   }
 };
 
@@ -179,15 +184,13 @@ struct Ctx {
   // lmm state
   bool lmm_active = false;
   gemma_lmm_cfg cfg;
-  const double *U = nullptr, *eval = nullptr, *Uty = nullptr; // device
+  const double *U = nullptr, *eval = nullptr; // device
   DevBuf own_U, own_eval, own_Uty, own_UtW, UtWt, idx_map;
   size_t ni_total = 0; // PLINK rows cover this many individuals (0 = n)
   bool have_map = false;
-  DevBuf X, UtX, stage_in, stage_out, carry;
-  DevBuf grid_R, grid_F, grid_T; // fixed-lambda table (lmm_grid.hip.h)
-  DevBuf cheb_R, cheb_F, cheb_T, cheb_slots, cheb_list, cheb_count, cheb_D, cheb_Ck, cheb_Gk, cheb_Lk, cheb_iv, cheb_dends, cheb_res; // bracket-interval series
-  double cheb_mid[ASSOC_MAX_REGION], cheb_inv_half[ASSOC_MAX_REGION];
-  GridGeom cheb_geom;
+  DevBuf X, UtX, stage_in, stage_out;
+  DevBuf grid_T; // fixed-lambda table of the batch (lmm_grid.hip.h); its setup half is the phenotype's (PhenoSlot)
+  DevBuf cheb_T, cheb_slots, cheb_list, cheb_count, cheb_D, cheb_Ck, cheb_Gk, cheb_Lk, cheb_iv, cheb_dends, cheb_res; // bracket-interval series
   DevBuf table_P; // K-slice partial sums of the table products (table_v2_kernel)
   DevBuf gxe_env, gxe_UtWt, gxe_Z, gxe_UtZ, gxe_flip; // GXE variants
   bool gxe_ready = false;
@@ -201,7 +204,6 @@ struct Ctx {
     int form = 0, d = 0, rows = 0;
   } mv_last[2]; // the kernel of the last per-SNP launch [0] / the last d-variate null fit [1] (gemma_hip_dbg_last_mvlmm_kernel)
   DevBuf i8_Bt, i8_q, i8_qinv, i8_cmax, i8_A, i8_C, i8_mean; // exact int8-digit U^T x (i8gemm.hip.h)
-  unsigned long long cheb_qmask = 0; // bit k: tabulated interval k is in Q form (ends at or below lambda = 1e-3)
   // (tile_m, tile_n) per workgroup of the records kernel: the cross-XCD raster (i8gemm_sparse2.hip.h).  One map per launch shape,
   // each in its OWN buffer, built once (a block cut into row chunks has two shapes -- full chunks and the last one -- and
   // a single slot was rebuilt, with a stream synchronisation and a blocking copy, twice per batch; a map in use by a kernel on
@@ -224,23 +226,26 @@ struct Ctx {
   bool i8_ready = false;
   size_t i8_ldk = 0, i8_npad = 0;
   int i8_digits = I8_DIGITS;
-  GridGeom grid_geom;
-  int carry_flip = 0;
-  AssocArgs assoc_proto;
-  // What of a setup belongs to the PHENOTYPE (gemma_hip_lmm_multi_setup): the members above of the same names are the live slot --
-  // the only one of a single-phenotype setup -- and slot_swap() exchanges them with a parked one around the per-SNP stage of that
-  // phenotype.  Everything else of the setup (U and its digit planes, eval, UtWt, the log-determinant ends inside the proto, idx_map,
+  // What of a setup belongs to the PHENOTYPE lives in a PhenoSlot and nowhere else: `single` for a single-phenotype setup (and the
+  // setup-wide proto of lmm_common_setup for every family), slots[t] for phenotype t of gemma_hip_lmm_multi_setup.  What builds or
+  // runs the per-SNP stage takes its slot as a parameter.  Everything else of the setup (U and its digit planes, eval, UtWt, idx_map,
   // cheb_iv / cheb_D / cheb_Ck..Lk, the per-batch buffers) exists once.
   struct PhenoSlot {
     AssocArgs proto;               // with its own l_mle_null / logl_mle_H0 and the pointers into this slot's tables
     const double *Uty = nullptr;
-    DevBuf grid_R, grid_F, cheb_R, cheb_F, carry;
+    DevBuf grid_R, grid_F, cheb_R, cheb_F; // the setup half of the fixed-lambda table and of the bracket-interval series
+    DevBuf carry;                  // PLINK NaN rule: the carry chain of this phenotype, in block order
     GridGeom grid_geom, cheb_geom;
     double cheb_mid[ASSOC_MAX_REGION], cheb_inv_half[ASSOC_MAX_REGION];
-    unsigned long long cheb_qmask = 0;
+    unsigned long long cheb_qmask = 0; // bit k: tabulated interval k is in Q form (ends at or below lambda = 1e-3)
     int carry_flip = 0;
+    void release() { // a buffer added above is released here and nowhere else
+      grid_R.release(); grid_F.release(); cheb_R.release(); cheb_F.release(); carry.release();
+      Uty = nullptr;
+    }
   };
-  std::vector<PhenoSlot> slots;    // multi setup: T parked slots (the live members are then nobody's)
+  PhenoSlot single;                // the phenotype of a single-phenotype setup
+  std::vector<PhenoSlot> slots;    // multi setup: the T phenotypes (`single` then holds the setup-wide proto alone)
   size_t multi_T = 0;              // 0: single-phenotype setup
   DevBuf multi_Yt;                 // U^T Y transposed (T x n): slot t's Uty is row t
   DevBuf multi_R, multi_T_buf;     // shared table: a group's weight matrix (one per group, back to back) and its G tables
@@ -370,6 +375,8 @@ static void raster_release() {
     r.used = 0;
   }
 }
+// the buffers gemma_hip_snp_qc keeps between the blocks of a first pass: a failed block, kin_begin and shutdown
+static void qc_release() { g_ctx.qc_G.release(); g_ctx.qc_M.release(); g_ctx.qc_W.release(); g_ctx.qc_O.release(); }
 static void kin_i8_release(); // integer kinship path, defined with kin_begin
 // one release list per state, each beside the entry points that fill it: kinship (abi_kinship.inc.h), LMM (abi_lmm_stage.inc.h), -lm
 // (abi_gxe_lm.inc.h).  A member added to Ctx is released by adding it to its state's list and nowhere else.
@@ -429,7 +436,7 @@ extern "C" void gemma_hip_shutdown(void) {
   (void)hipDeviceSynchronize();
   for (int s = 0; s < GEMMA_STAGE_COUNT; ++s) prof_collect(s);
   kin_release();
-  g_ctx.qc_G.release(); g_ctx.qc_M.release(); g_ctx.qc_W.release(); g_ctx.qc_O.release();
+  qc_release();
   lmm_release(); // every buffer an LMM setup or batch owns: ONE list, beside the members' users (abi_lmm_stage.inc.h)
   lm_release();
   pipe_release(); // pinned slots, copy stream and events of the pipelined host-block path
@@ -527,25 +534,20 @@ extern "C" int gemma_hip_dgemm(char ta, char tb, size_t M, size_t N, size_t K, d
   const bool tA = (ta == 'T' || ta == 't'), tB = (tb == 'T' || tb == 't');
   const size_t a_rows = tA ? K : M, b_rows = tB ? N : K;
   const size_t a_bytes = a_rows * lda * 8, b_bytes = b_rows * ldb * 8, c_bytes = M * ldc * 8;
-  DevBuf dA, dB, dC;
-  if (dA.reserve(a_bytes ? a_bytes : 8) || dB.reserve(b_bytes ? b_bytes : 8) || dC.reserve(c_bytes)) {
-    dA.release(); dB.release(); dC.release();
+  ScopedBuf dA, dB, dC;
+  if (dA.reserve(a_bytes ? a_bytes : 8) || dB.reserve(b_bytes ? b_bytes : 8) || dC.reserve(c_bytes))
     return fail(GEMMA_HIP_ENOMEM, "dgemm: cannot allocate %zu bytes", a_bytes + b_bytes + c_bytes);
-  }
   // the last row of a strided host view may be shorter than ld: copy row-wise via 2D copies
   auto h2d = [&](void *d, const double *h, size_t rows, size_t cols, size_t ld) -> hipError_t {
     if (rows == 0 || cols == 0) return hipSuccess;
     return hipMemcpy2D(d, ld * 8, h, ld * 8, cols * 8, rows, hipMemcpyHostToDevice);
   };
-  hipError_t e = h2d(dA.p, A, a_rows, tA ? M : K, lda);
-  if (e == hipSuccess) e = h2d(dB.p, B, b_rows, tB ? K : N, ldb);
-  if (e == hipSuccess && beta != 0.0) e = h2d(dC.p, C, M, N, ldc);
-  if (e == hipSuccess)
-    e = launch_dgemm(ta, tb, (long)M, (long)N, (long)K, alpha, dA.as<double>(), (long)lda,
-                     dB.as<double>(), (long)ldb, beta, dC.as<double>(), (long)ldc, false, false, 0);
-  if (e == hipSuccess) e = hipMemcpy2D(C, ldc * 8, dC.p, ldc * 8, N * 8, M, hipMemcpyDeviceToHost);
-  dA.release(); dB.release(); dC.release();
-  if (e != hipSuccess) return fail(GEMMA_HIP_ERUNTIME, "dgemm: %s", hipGetErrorString(e));
+  HIPCHK(h2d(dA.p, A, a_rows, tA ? M : K, lda));
+  HIPCHK(h2d(dB.p, B, b_rows, tB ? K : N, ldb));
+  if (beta != 0.0) HIPCHK(h2d(dC.p, C, M, N, ldc));
+  HIPCHK(launch_dgemm(ta, tb, (long)M, (long)N, (long)K, alpha, dA.as<double>(), (long)lda, dB.as<double>(), (long)ldb, beta,
+                      dC.as<double>(), (long)ldc, false, false, 0));
+  HIPCHK(hipMemcpy2D(C, ldc * 8, dC.p, ldc * 8, N * 8, M, hipMemcpyDeviceToHost));
   return GEMMA_HIP_OK;
 }
 
@@ -559,8 +561,8 @@ extern "C" int gemma_hip_dgemm(char ta, char tb, size_t M, size_t N, size_t K, d
 #include "abi_lmm_stage.inc.h"
 #include "abi_utx.inc.h"
 #include "abi_lmm_batch.inc.h"
-#include "abi_mvlmm.inc.h"
 #include "abi_gxe_lm.inc.h"
+#include "abi_mvlmm.inc.h"
 #include "abi_kept_comm.inc.h"
 #include "abi_lmm_multi.inc.h"
 #include "abi_lmm_score_panel.inc.h"
